@@ -28,9 +28,16 @@ Configurations (--config; BASELINE.json configs[1..4], one GPU's share): c3 (def
 512^3), c5 (image-conditioned: per-shape context, L=64, D=64, 512^3).  --workload trace replaces the synthetic decoder's
 own coarse-to-fine queries (8.3 % of 512^3) by the query lists of a trained-model-like thin shell (1.5 %), loops included.
 
-The JSON line carries: `roofline` (the kernel with the most GPU time = forward decoder: ALGORITHMIC flops
-vs the fp16 matrix peak, the issued figure beside it), `roofline_loop` (denoiser weight stream vs HBM), `time_share`,
-`w_trace`, `e2`, `cpu_baseline` (the oracle on this host's cores, bounded sample), and for N > 1 `per_rank`.
+A plain run sets up, warms up, times --steps steps and prints the line; everything else it can measure runs only with
+--full.  The JSON line carries: `roofline` (the kernel with the most GPU time = forward decoder: ALGORITHMIC
+flops vs the fp16 matrix peak, the issued figure beside it), `roofline_loop` (denoiser weight stream vs HBM), `time_share`,
+and for N > 1 `per_rank`, all from the timed steps; with --full also `roofline_loop.one_loop_alone_*` (one loop alone, after
+the clock), `strict_c3`, `trace_e2`, `w_trace`, `e2` and `cpu_baseline` (the oracle on this host's cores, bounded sample).
+--dump-outputs DIR writes what the last timed step computed (latents, sampled grids) as .npy files: with the same arguments
+the inputs are the same in every run, so two builds can be compared output for output.
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full                   # the complete line
+
 Multi-GPU: shapes are independent -> each rank owns its own B shapes per step (weak scaling), no data-path collective;
 ranks meet only at the timing barriers.  --mode grid-shard instead splits every level of ONE shape's grid over the ranks
 (device-side counts, ncclAllGather of the values over xGMI).  Prints ONE JSON line on rank 0.
@@ -123,6 +130,13 @@ def parse():
     ap.add_argument("--strict-steps", type=int, default=0, help="requests timed by the strict-C3 pass (0 = one per step of the headline: the same shapes)")
     ap.add_argument("--no-trace-e2", action="store_true", help="skip the timed W-trace / E2 pass (trained-model-like field through marching cubes)")
     ap.add_argument("--trace-steps", type=int, default=0, help="steps timed by the W-trace / E2 pass (0 = --steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what it does not need: one loop alone (roofline_loop.one_loop_alone_*), the strict-C3 "
+                         "and W-trace / E2 passes, the W-trace decoder timing, the E2 estimate, the CPU baseline, and in grid-shard mode "
+                         "the sharded / fused grid comparison (the --no-* flags above select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (rank 0): latents, a fixed "
+                         "seeded sample of every grid's voxels and gradients, per-grid sums (dump_outputs)")
     a = ap.parse_args()
     if a.loop_chunk < 1:
         ap.error("--loop-chunk must be >= 1 graph replay per loop and turn")
@@ -539,7 +553,10 @@ class Job:
             self.mesher = BandMesher(N, threads=threads, slots=2 * B)
         mesher = self.mesher
 
+        self.last_step = self.last_lat = None
+
         def fill_grids(step, lat):
+            self.last_step, self.last_lat = step, lat          # the step's latents as the caller receives them (--dump-outputs)
             dec.bind_latents(lat.reshape(B, a.latent))
             if trace is not None:                            # W-trace: the decoder kernels over the trained-model-like query lists
                 for k in range(B):
@@ -663,6 +680,30 @@ def decoder_rooflines(m, f16):
                                 "accounting": "2 x forward flops per gradient query"}}
 
 
+DUMP_BUDGET_BYTES = 32 << 20      # voxel samples of --dump-outputs (16 B per sampled voxel and grid: value + gradient)
+
+
+def dump_outputs(out_dir, lat, grids):
+    """--dump-outputs: what the last timed step handed its caller, for output-by-output comparison of two builds.
+    latents.npy [B, 1, L] float32 in full; of every grid (udf [N, N, N], grads [N, N, N, 3]) the same fixed sample of voxel
+    indices (CPU generator seeded 0, sorted; at most DUMP_BUDGET_BYTES over all grids) as udf_sample.npy [G, S] and
+    grads_sample.npy [G, S, 3] float32, and over ALL voxels udf_sum.npy / grads_abs_sum.npy [G] float64 (every voxel counts)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"latents": lat.detach().float().cpu().numpy()}
+    if grids:
+        n_vox = grids[0][0].numel()
+        s = min(n_vox, DUMP_BUDGET_BYTES // (16 * len(grids)))
+        idx = torch.randint(0, n_vox, (s,), generator=torch.Generator().manual_seed(0)).sort().values.to(grids[0][0].device)
+        arrays["udf_sample"] = torch.stack([u.reshape(-1)[idx] for u, _ in grids]).float().cpu().numpy()
+        arrays["grads_sample"] = torch.stack([g.reshape(-1, 3)[idx] for _, g in grids]).float().cpu().numpy()
+        arrays["udf_sum"] = torch.stack([u.sum(dtype=torch.float64) for u, _ in grids]).cpu().numpy()
+        arrays["grads_abs_sum"] = torch.stack([g.abs().sum(dtype=torch.float64) for _, g in grids]).cpu().numpy()
+    for name, ar in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), ar)
+    return {k: list(v.shape) for k, v in arrays.items()}
+
+
 def main():
     a = parse()
     world, rank, local = setup_dist(a.gpus)
@@ -701,20 +742,27 @@ def main():
         for m in timeline:
             print("[timeline] " + json.dumps(m), file=sys.stderr)
     n_fwd, n_grad = fwd_total / (B * a.steps), grad_total / (B * a.steps)
+    lat = job.last_lat
+    if a.dump_outputs and rank == 0:
+        assert job.last_step == a.steps - 1, (job.last_step, a.steps)
+        dumped = dump_outputs(a.dump_outputs, lat, list(zip(job.udf, job.grads)) if job.udf is not None else [])
+        print(f"[bench] --dump-outputs: step {job.last_step} -> {a.dump_outputs}: {dumped}", file=sys.stderr)
     job.close()
-    # ---- untimed extras: one loop alone at the widest batch the schedule used --------------------------------------
+    # ---- untimed extras (--full): one loop alone at the widest batch the schedule used ------------------------------
     dec.set_grid_blocks(0)
-    if a.schedule == "overlap" and a.loop_cus != 256:
-        model.set_cu_budget(256)                         # one loop alone owns the chip
     alone_n = min(loop_batches, max(1, -(-a.steps // n_chains))) if a.schedule == "phased" else 1
     alone_n = min(alone_n, n_steps_max)
-    lat = sample_latents(0, alone_n)                     # (re-)capture outside the timed call
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    lat = sample_latents(0, alone_n)
-    torch.cuda.synchronize()
-    loop_alone_ms = (time.perf_counter() - t1) * 1e3
-    lat = lat[:B]
+    loop_alone_ms = None
+    if a.full:
+        if a.schedule == "overlap" and a.loop_cus != 256:
+            model.set_cu_budget(256)                     # one loop alone owns the chip
+        lat = sample_latents(0, alone_n)                 # (re-)capture outside the timed call
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        lat = sample_latents(0, alone_n)
+        torch.cuda.synchronize()
+        loop_alone_ms = (time.perf_counter() - t1) * 1e3
+        lat = lat[:B]
     sat = sum(m.saturation_count() for m in chains) + dec.saturation_count()
     rccl_ranks = 1
     per_rank = None
@@ -747,7 +795,7 @@ def main():
     f16 = a.decoder_precision == "f16x2"
     # ---- the two other numbers of the line (N = 1 only, each its own timed region after the headline's) --------------
     strict = None
-    if not a.no_strict and world == 1 and a.schedule == "phased" and a.workload == "real" and a.endpoint == "e1":
+    if a.full and not a.no_strict and world == 1 and a.schedule == "phased" and a.workload == "real" and a.endpoint == "e1":
         # BASELINE configs[2] read strictly: ONE batch-8 request in flight per GPU — its reverse loop (8 latents, the conv
         # kernel's latency form), then its 8 grids, request after request on one stream
         sj = Job(a, world, rank, cfg, model, chains, diffusion, dec, noise_bank, ctx_bank, workload="real", endpoint="e1",
@@ -771,7 +819,7 @@ def main():
                   "what": "one batch-8 request in flight per GPU (BASELINE configs[2] = batch 64 over 8 GPUs, read strictly): 1000-step loop over 8 "
                           "latents (latency form of the conv kernel), then the request's 8 grids, sequentially on one stream"}
     trace_e2 = None
-    if not a.no_trace_e2 and world == 1 and a.workload == "real" and a.endpoint == "e1" and a.schedule == "phased":
+    if a.full and not a.no_trace_e2 and world == 1 and a.workload == "real" and a.endpoint == "e1" and a.schedule == "phased":
         # the trained-model-like workload END TO END, timed: wide reverse loops + decoder over the thin-shell query lists + band
         # compaction, pinned D2H and the host mesher, every mesh finished before the clock stops
         torch.cuda.empty_cache()
@@ -794,7 +842,7 @@ def main():
         del tr, tg
         torch.cuda.empty_cache()
     w_trace = None
-    if not a.no_trace:
+    if a.full and not a.no_trace:
         torch.cuda.empty_cache()
         w_trace = time_trace(dec, lat, trace if trace is not None else make_trace(N))
     shapes = world * B * a.steps
@@ -845,7 +893,8 @@ def main():
     roofline_loop = {"kernel": "conv2_kernel x84 (the head's epilogue carries the posterior update and the loop counter) + attn_kernel x16 per denoiser evaluation (hipGraph replay)",
                      "bound": binding,
                      "roof_us_per_evaluation": roof_eval_us, "roof_us_hbm": hbm_us, "roof_us_mfma": mfma_us,
-                     "frac": (n_chains * roof_eval_us * 1e-3 / sched_ms_eval) if sched_ms_eval else (roof_eval_us * 1e-3 / (loop_alone_ms / T)),
+                     "frac": (n_chains * roof_eval_us * 1e-3 / sched_ms_eval) if sched_ms_eval else
+                             (roof_eval_us * 1e-3 / (loop_alone_ms / T)) if loop_alone_ms else None,
                      "frac_means": "roof time of the loops in flight / wall time per evaluation in the schedule, against the binding roof at this width",
                      "hbm": {"achieved": streamed_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": streamed_gbs / HBM_PEAK_GBS},
                      "achieved": (n_chains * flops_eval / (sched_ms_eval * 1e-3) / 1e12) if (sched_ms_eval and binding == "mfma") else streamed_gbs,
@@ -856,9 +905,9 @@ def main():
                      "traffic_from": pmc_note,
                      "algorithmic_bytes_per_evaluation": UNET_WEIGHT_BYTES, "algorithmic_flop_per_evaluation": flops_eval,
                      "latents_per_loop": lat_per_loop, "loops_in_flight": n_chains, "loops": loops,
-                     "one_loop_alone_ms_per_evaluation": loop_alone_ms / T,
-                     "one_loop_alone_frac": roof_eval_us * 1e-3 / (loop_alone_ms / T),
-                     "one_loop_alone_us_per_evaluation_and_latent": loop_alone_ms / T * 1e3 / lat_per_loop,
+                     **({"one_loop_alone_ms_per_evaluation": loop_alone_ms / T,
+                         "one_loop_alone_frac": roof_eval_us * 1e-3 / (loop_alone_ms / T),
+                         "one_loop_alone_us_per_evaluation_and_latent": loop_alone_ms / T * 1e3 / lat_per_loop} if loop_alone_ms is not None else {}),
                      "in_schedule_ms_per_evaluation": loop_ms / max(loops, 1) / T,
                      "in_schedule_us_per_evaluation_and_latent": (loop_phase_ms * 1e3 / (T * B * a.steps)) if loop_phase_ms else None}
     out = {
@@ -925,9 +974,9 @@ def main():
         out["e2"] = {"status": "timed", "value": shapes / elapsed, "unit": "shapes/s", **mesh_stats}
     elif trace_e2 is not None:
         out["e2"] = {"status": "see trace_e2 (timed, trained-model-like field); the synthetic decoder's own field has almost no surface to mesh"}
-    elif not a.no_e2:
+    elif a.full and not a.no_e2:
         out["e2"] = e2_estimate(a, elapsed, shapes, world)
-    if not a.no_cpu_baseline and world == 1:          # a stated baseline of the N=1 line only
+    if a.full and not a.no_cpu_baseline and world == 1:          # a stated baseline of the N=1 line only
         out["cpu_baseline"] = cpu_baseline(T, B, n_fwd, n_grad, a.latent, N)
     print(json.dumps(out))
 
@@ -1028,9 +1077,13 @@ def grid_shard_main(a, world, rank):
     w_acc = world if world > 1 else 8
     buffers_bytes = (4 * sum(shard_caps[0]) + 12 * shard_caps[1]) if shard_caps else None
     bytes_exchanged_per_shape = int(buffers_bytes * (w_acc - 1) / w_acc) if shard_caps else None
-    # the same shapes through the fused single-rank fill, timed the same way: what the sharded path costs by construction
-    fused_ms = None
-    if rank == 0 or world > 1:
+    if a.dump_outputs and rank == 0:
+        # the one grid buffer holds the last shape of the last step: its grid, and the step's latents
+        dumped = dump_outputs(a.dump_outputs, lat, [(udf, grads)])
+        print(f"[bench] --dump-outputs: step {a.steps - 1} (grid of its last shape) -> {a.dump_outputs}: {dumped}", file=sys.stderr)
+    # (--full) the same shapes through the fused single-rank fill, timed the same way: what the sharded path costs by construction
+    fused_ms = shard_ms = None
+    if a.full and (rank == 0 or world > 1):
         ff = GridFiller(N)
         ff.fill_grid(make_udf_func(dec, lat[0], sample=0), 2 ** 16, out=(udf, grads), stats=False)
         torch.cuda.synchronize()
@@ -1039,18 +1092,18 @@ def grid_shard_main(a, world, rank):
             ff.fill_grid(make_udf_func(dec, lat[k], sample=k), 2 ** 16, out=(udf, grads), stats=False)
         torch.cuda.synchronize()
         fused_ms = (time.perf_counter() - t1) * 1e3 / B
-    shard_ms = None
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for k in range(B):
-        if a.shard_path == "native":
-            filler.fill_grid_sharded(make_udf_func(dec, lat[k], sample=k), rank=rank, world=world, out=(udf, grads), stats=False,
-                                     adaptive=not fixed_caps, capacity=a.shard_capacity if fixed_caps else None,
-                                     grad_capacity=a.shard_grad_capacity if fixed_caps else None)
-        else:
-            filler.fill_grid(ShardedField(make_udf_func(dec, lat[k], sample=k)), 2 ** 22, out=(udf, grads), stats=False)
-    torch.cuda.synchronize()
-    shard_ms = (time.perf_counter() - t1) * 1e3 / B
+    if a.full:
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for k in range(B):
+            if a.shard_path == "native":
+                filler.fill_grid_sharded(make_udf_func(dec, lat[k], sample=k), rank=rank, world=world, out=(udf, grads), stats=False,
+                                         adaptive=not fixed_caps, capacity=a.shard_capacity if fixed_caps else None,
+                                         grad_capacity=a.shard_grad_capacity if fixed_caps else None)
+            else:
+                filler.fill_grid(ShardedField(make_udf_func(dec, lat[k], sample=k)), 2 ** 22, out=(udf, grads), stats=False)
+        torch.cuda.synchronize()
+        shard_ms = (time.perf_counter() - t1) * 1e3 / B
     per_rank = None
     if world > 1:
         import torch.distributed as dist
@@ -1083,9 +1136,9 @@ def grid_shard_main(a, world, rank):
                                       "segments of capacity / world points all-gathered (ncclAllGather over xGMI: all_gather_into_tensor), 4 B per point per level + 12 B per gradient point")
                                      if a.shard_path == "native" else
                                      f"grid-shard x{world}: all_gather of 4 B per point per level + 12 B per gradient point over xGMI"},
-           "grid_ms_per_shape": {"sharded": shard_ms, "fused_single_rank_fill": fused_ms,
-                                 "sharded_over_fused": (shard_ms / fused_ms) if fused_ms else None,
-                                 "note": "the shapes of the last step again, grids only, after the timed region"}}
+           **({"grid_ms_per_shape": {"sharded": shard_ms, "fused_single_rank_fill": fused_ms,
+                                     "sharded_over_fused": (shard_ms / fused_ms) if fused_ms else None,
+                                     "note": "the shapes of the last step again, grids only, after the timed region"}} if a.full else {})}
     if per_rank is not None:
         out["per_rank"] = per_rank
     print(json.dumps(out))

@@ -31,6 +31,46 @@ def test_defaults_match_the_driver_contract(bench, monkeypatch):
     assert (a.gpus, a.steps, a.warmup) == (4, 20, 5)
 
 
+def test_full_and_dump_outputs_options(bench, monkeypatch):
+    """A plain run is the headline only (--full off by default); --dump-outputs takes a directory."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (3, 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--full", "--dump-outputs", "out/dir"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out/dir"
+
+
+def test_dump_outputs_writes_the_seeded_sample(bench, tmp_path):
+    """dump_outputs: latents in full, the same seeded voxel sample of every grid (float32), per-grid sums over all voxels
+    (float64), within the size budget; the sample does not depend on the values, so two builds compare voxel for voxel."""
+    B, L, N = 3, 32, 24
+    g = torch.Generator().manual_seed(7)
+    lat = torch.randn(B, 1, L, generator=g)
+    grids = [(torch.rand(N, N, N, generator=g), torch.randn(N, N, N, 3, generator=g)) for _ in range(B)]
+    shapes = bench.dump_outputs(str(tmp_path / "a"), lat, grids)
+    files = {p.name: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert set(files) == {"latents.npy", "udf_sample.npy", "grads_sample.npy", "udf_sum.npy", "grads_abs_sum.npy"}
+    assert shapes["latents"] == [B, 1, L] and files["latents.npy"].dtype == np.float32
+    np.testing.assert_array_equal(files["latents.npy"], lat.numpy())
+    S = min(N ** 3, bench.DUMP_BUDGET_BYTES // (16 * B))
+    assert files["udf_sample.npy"].shape == (B, S) and files["udf_sample.npy"].dtype == np.float32
+    assert files["grads_sample.npy"].shape == (B, S, 3) and files["grads_sample.npy"].dtype == np.float32
+    idx = torch.randint(0, N ** 3, (S,), generator=torch.Generator().manual_seed(0)).sort().values
+    for k, (u, gr) in enumerate(grids):
+        np.testing.assert_array_equal(files["udf_sample.npy"][k], u.reshape(-1)[idx].numpy())
+        np.testing.assert_array_equal(files["grads_sample.npy"][k], gr.reshape(-1, 3)[idx].numpy())
+        assert files["udf_sum.npy"][k] == pytest.approx(float(u.double().sum()), rel=1e-12)
+        assert files["grads_abs_sum.npy"][k] == pytest.approx(float(gr.double().abs().sum()), rel=1e-12)
+    assert files["udf_sum.npy"].dtype == np.float64 and files["grads_abs_sum.npy"].dtype == np.float64
+    assert sum(v.nbytes for v in files.values()) <= 64 << 20
+    # full size: 8 grids of 512^3 stay within the budget
+    assert 8 * (bench.DUMP_BUDGET_BYTES // (16 * 8)) * 16 <= 64 << 20
+    # the trace workload hands out no grids: latents only
+    bench.dump_outputs(str(tmp_path / "b"), lat, [])
+    assert sorted(p.name for p in (tmp_path / "b").iterdir()) == ["latents.npy"]
+
+
 def test_self_launch_builds_a_one_rank_per_gpu_command(bench, monkeypatch):
     """`python bench.py --gpus N` without a launcher must re-execute itself under torch.distributed.run on 127.0.0.1."""
     seen = {}

@@ -20,8 +20,12 @@ def _line(out: str) -> dict:
     return json.loads(rows[0])
 
 
-def test_single_gpu_line_contract():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL, capture_output=True, text=True, timeout=600, cwd=ROOT)
+FULL_ONLY = ("strict_c3", "trace_e2", "w_trace", "e2", "cpu_baseline")
+DUMPED = {"latents.npy", "udf_sample.npy", "grads_sample.npy", "udf_sum.npy", "grads_abs_sum.npy"}
+
+
+def _single_gpu(extra):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL + extra, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _line(out.stdout)
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["unit"] == "shapes/s" and d["value"] > 0 and d["higher_is_better"] and d["scaling"] == "weak"
@@ -30,6 +34,45 @@ def test_single_gpu_line_contract():
     assert r["bound"] == "mfma" and r["frac"] == pytest.approx(r["achieved"] / r["peak"]) and 0 < r["frac"] < 1 and "traffic_from" in r
     assert d["config"]["schedule"] == "phased" and d["config"]["fp16_range_saturations"] == 0
     assert d["time_share"]["loops_frac"] > 0 and d["config"]["decoder_fwd_queries_per_shape"] >= 32 ** 3
+    return d
+
+
+def _dumped(path):
+    import numpy as np
+    files = {name: np.load(os.path.join(path, name)) for name in os.listdir(path)}
+    assert set(files) == DUMPED
+    assert files["latents.npy"].shape == (8, 1, 32) and files["udf_sample.npy"].shape[0] == 8 and files["grads_sample.npy"].shape[-1] == 3
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in files.values())
+    assert sum(v.nbytes for v in files.values()) <= 64 << 20
+    return files
+
+
+@pytest.fixture(scope="module")
+def plain_run(tmp_path_factory):
+    dump = str(tmp_path_factory.mktemp("plain_dump"))
+    return _single_gpu(["--dump-outputs", dump]), dump
+
+
+def test_single_gpu_line_contract(plain_run):
+    d, dump = plain_run
+    assert not [k for k in FULL_ONLY if k in d], "a plain run carries the headline only (the rest needs --full)"
+    assert "one_loop_alone_ms_per_evaluation" not in d["roofline_loop"]
+    _dumped(dump)
+
+
+def test_single_gpu_full_line(plain_run, tmp_path):
+    """--full: the passes after the clock run as before (strict C3, the timed W-trace / E2 pass, one loop alone); the timed
+    steps are the plain run's, so their outputs are the same bits."""
+    d = _single_gpu(["--full", "--dump-outputs", str(tmp_path)])
+    s = d["strict_c3"]
+    assert s["requests"] == 2 and s["value"] > 0 and 0 < s["roofline"]["frac"] < 1
+    assert d["trace_e2"]["status"] == "timed" and d["trace_e2"]["value"] > 0 and d["e2"]["status"].startswith("see trace_e2")
+    assert d["roofline_loop"]["one_loop_alone_ms_per_evaluation"] > 0
+    assert "w_trace" not in d and "cpu_baseline" not in d              # --no-trace / --no-cpu-baseline still select within --full
+    import numpy as np
+    full, plain = _dumped(str(tmp_path)), _dumped(plain_run[1])
+    for name in DUMPED:
+        np.testing.assert_array_equal(full[name], plain[name], err_msg=name)
 
 
 def test_two_ranks_over_gloo_on_one_gpu():

@@ -46,6 +46,7 @@ def import_reference(ref: str):
     mods.model_util, mods.gd, mods.respace = model_util, gaussian_diffusion, respace
     mods.openaimodel, mods.ldm_utils, mods.cfg_sampler = openaimodel, ldm_utils, cfg_sampler
     mods.cbndec, mods.coordsenc, mods.meshudf = cbndec, coordsenc, meshudf
+    mods.root = ref
     return mods
 
 
@@ -490,6 +491,48 @@ def g13_marching_cubes(R, with_512: bool):
     save("g13_marching_cubes", **out)
 
 
+EXT_CASES = [("noisy_blob", 40, 1), ("noisy_blob", 56, 2), ("noisy_blob", 72, 3), ("two_spheres", 33, 0), ("open_sheet", 57, 0)]
+
+
+def g13_extension_cases(R):
+    """The reference extension's output on the grids of tests/test_mcubes_cpu.py::test_bit_exact_vs_reference_extension,
+    for hosts where oracle/_ref cannot be built: SHA-256 of vertices, faces, normals and values for every case, the input
+    grid's hash, full arrays for the cases under 10 000 vertices (the whole set as arrays would be 1.7 MB)."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import mc_fields
+    from oracle import build_ref
+    from surfd_amd import mcubes
+    cy = build_ref.load()
+    assert cy is not None, "oracle/_ref could not be built"
+    out = {}
+    for name, N, seed in EXT_CASES:
+        udf, grads = mc_fields.noisy_blob(N, seed) if name == "noisy_blob" else mc_fields.FIELDS[name](N)
+        arrays = dict(zip(("verts", "faces", "normals", "values"), build_ref.reference_udf_mc(cy, mcubes.lut_tables(), udf, grads)))
+        tag = f"{name}_{N}_{seed}"
+        out[tag + "_input_sha256"] = np.array(hashlib.sha256(udf.tobytes() + grads.tobytes()).hexdigest())
+        for k, ar in arrays.items():
+            ar = np.ascontiguousarray(ar)
+            out[f"{tag}_{k}_sha256"] = np.array(hashlib.sha256(ar.tobytes()).hexdigest())
+            out[f"{tag}_{k}_dtype"] = np.array(str(ar.dtype))
+            out[f"{tag}_{k}_shape"] = np.array(ar.shape)
+            if len(arrays["verts"]) < 10000:
+                out[f"{tag}_{k}"] = ar
+        print(f"  reference marching_cubes_udf {tag}: {len(arrays['verts'])} verts / {len(arrays['faces'])} faces")
+    save("g13_reference_extension", **out)
+
+
+def g16_bpe_merges(R):
+    """CLIP's BPE merges file cut to the part its tokenizer reads (the header line + the first 48 894 merges of
+    CLIP/clip/bpe_simple_vocab_16e6.txt.gz; the vocabulary is built from exactly these), gzip without a time stamp, so the
+    tokenizer tests run where the reference tree is absent."""
+    import gzip
+    lines = gzip.open(os.path.join(R.root, "CLIP", "clip", "bpe_simple_vocab_16e6.txt.gz")).read().decode("utf-8").split("\n")
+    path = os.path.join(OUT, "clip_bpe_merges_48894.txt.gz")
+    with open(path, "wb") as raw, gzip.GzipFile(filename="", fileobj=raw, mode="wb", compresslevel=9, mtime=0) as gz:
+        gz.write(("\n".join(lines[:49152 - 256 - 2 + 1]) + "\n").encode("utf-8"))
+    print(f"  wrote {path}  ({os.path.getsize(path) / 1024:.0f} KB)")
+
+
 def g13_lut_hashes(R):
     """SHA-256 + shape of every case table of the reference's meshudf/_marching_cubes_lewiner_luts.py (base64 int8
     blobs) and of the three edge-corner tables its driver builds (_marching_cubes_lewiner.py:171-224): pins the
@@ -672,7 +715,9 @@ def main():
     jobs = {"g1": lambda: g1_g2(R), "g3": lambda: g3_g4(R), "g5": lambda: g5_g6(R), "g7": lambda: g7_g8(R), "g8flips": lambda: g8_direction_flips(R),
             "g9": lambda: g9(R), "g10": lambda: g10(R, [int(s) for s in a.g10_sizes.split(",")]),
             "g9d64": lambda: g9_d64(R), "g11": lambda: g11_conditioned_loops(R), "g12": lambda: g12_contractive(R),
-            "g13": lambda: g13_marching_cubes(R, a.mc512), "g13luts": lambda: g13_lut_hashes(R), "g15": lambda: g15_image_preprocess(R), "g16": lambda: g16_clip_towers(R), "g17": lambda: g17_spatial_transformer(R), "g14": lambda: g14_cross_attention(R)}
+            "g13": lambda: g13_marching_cubes(R, a.mc512), "g13luts": lambda: g13_lut_hashes(R), "g13ext": lambda: g13_extension_cases(R),
+            "g15": lambda: g15_image_preprocess(R), "g16": lambda: g16_clip_towers(R), "g16bpe": lambda: g16_bpe_merges(R),
+            "g17": lambda: g17_spatial_transformer(R), "g14": lambda: g14_cross_attention(R)}
     only = [s for s in a.only.split(",") if s]
     for name, fn in jobs.items():
         if only and name not in only:
