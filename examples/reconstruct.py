@@ -1,0 +1,173 @@
+#!/usr/bin/env python3
+"""Point clouds -> latents -> meshes on the MI355X path: the counterpart of the reference's
+AutoEncoder/encdec/export_meshes.py (how a trained auto-encoder checkpoint is checked).
+
+    python examples/reconstruct.py --ae_dir ae.pt --output_dir out/ cloud_0.npz cloud_1.npy [more files or directories]
+    python examples/reconstruct.py --ae_dir ae.pt --latents_only --output_dir out/ clouds/      # -> out/latents.npz
+    python examples/reconstruct.py --synthetic --resolution 64 --output_dir out/                 # smoke run, no trained weights
+
+Inputs are point clouds: ``.npz`` files with the reference dataset's ``pcd`` key (AutoEncoder/data/dataset.py:82-83, written
+by preprocess_udfs.py:128-151) or ``.npy`` arrays [N, 3]; the item id is the file name without its extension.  As in
+export_meshes.py:55-100: the encoder and the decoder come from one checkpoint (``ckpt["encoder"]``, ``ckpt["decoder"]``; the
+latent size is read from ``conv_5.weight``), every cloud is resampled to ``--num_points_pcd`` points with
+random_point_sampling on the global RNG (seeded with ``--seed``), encoded by Dgcnn, and its UDF is meshed with
+get_mesh_from_udf (or, with ``--watertight``, the level-set mesher).  The mesh is written as extracted, with no smoothing and
+no component filtering (export_meshes.py:115-151).  ``--latents_only`` skips meshing and writes ``latents.npz`` (item id ->
+latent), the data-export use (training_loop_single.py:107-112,190-194).  ``--synthetic`` writes a synthetic checkpoint holding
+both encoder and decoder (surfd_amd.synth) and, when no input is given, two synthetic clouds.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from surfd_amd import meshproc, synth  # noqa: E402
+from surfd_amd.cbndec import CbnDecoder, CoordsEncoder, make_udf_func  # noqa: E402
+from surfd_amd.dgcnn import Dgcnn, random_point_sampling  # noqa: E402
+from surfd_amd.meshudf import get_mesh_from_udf, get_watertight_mesh  # noqa: E402
+from surfd_amd.rangeguard import run_guarded  # noqa: E402
+from surfd_amd.spec import DecoderConfig  # noqa: E402
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("inputs", nargs="*", help=".npz (key 'pcd') / .npy [N,3] point clouds, or directories holding them")
+    ap.add_argument("--ae_dir", help="auto-encoder checkpoint ({'encoder': state_dict, 'decoder': state_dict, ...})")
+    ap.add_argument("--num_points_pcd", type=int, default=10000)
+    ap.add_argument("--resolution", type=int, default=512)
+    ap.add_argument("--watertight", action="store_true")
+    ap.add_argument("--batch", type=int, default=1, help="clouds per encoder call (export_meshes.py:75 uses 1)")
+    ap.add_argument("--seed", type=int, default=10)
+    ap.add_argument("--output_dir", default="outputs/reconstruct")
+    ap.add_argument("--latents_only", action="store_true", help="write latents.npz and skip meshing")
+    ap.add_argument("--synthetic", action="store_true", help="create a synthetic checkpoint under --output_dir and use it")
+    ap.add_argument("--size_latent", type=int, default=32, help="latent size of the --synthetic checkpoint")
+    return ap.parse_args(argv)
+
+
+def synthetic_checkpoint(out_dir, size_latent):
+    """encoder + decoder in the layout of the reference's auto-encoder checkpoint.  The untrained decoder's logit stays below
+    the level the meshers extract at for the encoder's latents; its output bias is raised by 1 so that the field has a surface."""
+    path = os.path.join(out_dir, "ae_synthetic.pt")
+    dec = synth.synth_decoder_state_dict(DecoderConfig(latent_dim=size_latent))
+    dec["decoder.fc_out.bias"] = dec["decoder.fc_out.bias"] + 1.0
+    torch.save({"epoch": 0, "encoder": synth.synth_dgcnn_state_dict(size_latent), "decoder": dec}, path)
+    return path
+
+
+def synthetic_clouds(out_dir, count=2, n=12000):
+    """points near a torus (R 0.5, r 0.15 + 0.05 i), written in the dataset's npz layout"""
+    paths = []
+    g = torch.Generator().manual_seed(7)
+    for i in range(count):
+        u, v = torch.rand(n, generator=g) * 2 * np.pi, torch.rand(n, generator=g) * 2 * np.pi
+        r = 0.15 + 0.05 * i
+        pcd = torch.stack([(0.5 + r * torch.cos(v)) * torch.cos(u), r * torch.sin(v), (0.5 + r * torch.cos(v)) * torch.sin(u)], 1)
+        path = os.path.join(out_dir, f"synthetic_{i}.npz")
+        np.savez(path, pcd=pcd.numpy().astype(np.float32))
+        paths.append(path)
+    return paths
+
+
+def list_inputs(inputs):
+    files = []
+    for p in inputs:
+        if os.path.isdir(p):
+            files += [os.path.join(p, f) for f in sorted(os.listdir(p)) if f.endswith((".npz", ".npy"))]
+        else:
+            files.append(p)
+    return files
+
+
+def load_cloud(path) -> torch.Tensor:
+    if path.endswith(".npz"):
+        with np.load(path) as z:
+            if "pcd" not in z.files:
+                raise SystemExit(f"{path}: no 'pcd' array (keys: {z.files})")
+            pcd = z["pcd"]
+    else:
+        pcd = np.load(path)
+    if pcd.ndim != 2 or pcd.shape[1] != 3:
+        raise SystemExit(f"{path}: expected a point cloud [N, 3], got {pcd.shape}")
+    return torch.from_numpy(np.ascontiguousarray(pcd, dtype=np.float32))
+
+
+def load_models(ae_dir):
+    ckpt = torch.load(ae_dir, map_location="cpu")
+    for key in ("encoder", "decoder"):
+        if key not in ckpt:
+            raise SystemExit(f"{ae_dir}: no '{key}' state dict (keys: {list(ckpt)})")
+    size_latent = int(ckpt["encoder"]["conv_5.weight"].shape[0])
+    encoder = Dgcnn(size_latent)
+    encoder.load_state_dict(ckpt["encoder"], strict=True)
+    encoder = encoder.cuda().eval()
+    dec_latent = next((v.shape[1] for k, v in ckpt["decoder"].items() if k.endswith("conv_gamma.weight")), None)
+    if dec_latent is not None and dec_latent != size_latent:
+        raise SystemExit(f"{ae_dir}: the encoder makes {size_latent}-d latents, the decoder takes {dec_latent}-d ones")
+    decoder = CbnDecoder(CoordsEncoder().out_dim, size_latent, 512, 5)
+    decoder.load_state_dict(ckpt["decoder"], strict=True)
+    return encoder, decoder.cuda().eval(), size_latent
+
+
+def main(argv=None):
+    return run(parse(argv))
+
+
+def run(a):
+    os.makedirs(a.output_dir, exist_ok=True)
+    inputs = list(a.inputs)
+    if a.synthetic:
+        a.ae_dir = synthetic_checkpoint(a.output_dir, a.size_latent)
+        if not inputs:
+            inputs = synthetic_clouds(a.output_dir)
+    if not a.ae_dir:
+        raise SystemExit("--ae_dir is required (or --synthetic)")
+    files = list_inputs(inputs)
+    if not files:
+        raise SystemExit("no input point clouds")
+    encoder, decoder, size_latent = load_models(a.ae_dir)
+    torch.manual_seed(a.seed)
+
+    ids, latents = [], []
+    for b0 in range(0, len(files), a.batch):
+        chunk = files[b0:b0 + a.batch]
+        pcds = torch.stack([random_point_sampling(load_cloud(f).cuda(), a.num_points_pcd) for f in chunk])   # as export_meshes.py:79-83
+        latents.append(encoder(pcds))
+        ids += [os.path.splitext(os.path.basename(f))[0] for f in chunk]
+    latents = torch.cat(latents)
+    if len(set(ids)) != len(ids):
+        raise SystemExit(f"item ids must be unique: {ids}")
+    if a.latents_only:
+        path = os.path.join(a.output_dir, "latents.npz")
+        np.savez(path, **{i: latents[k].cpu().numpy() for k, i in enumerate(ids)})
+        print(f"{path}: {len(ids)} latents of size {size_latent}")
+        return latents, [path]
+
+    decoder.bind_latents(latents)
+    written = []
+    for k, item in enumerate(ids):
+        field = make_udf_func(decoder, latents[k], sample=k)
+
+        def shape_mesh():
+            if a.watertight:
+                return get_watertight_mesh(field, a.resolution, max_batch=2 ** 16)
+            v, t = get_mesh_from_udf(field, coords_range=(-1, 1), max_dist=0.1, N=a.resolution, max_batch=2 ** 16, differentiable=False)
+            return v.cpu().numpy(), t.cpu().numpy()
+
+        (verts, faces), _ = run_guarded(f"{item} (decoder grids)", shape_mesh, decoder.saturation_count,
+                                        lambda: decoder.set_precision("fp32"))
+        path = os.path.join(a.output_dir, f"{item}_{'watertight' if a.watertight else 'meshudf'}.obj")
+        meshproc.write_obj(path, verts, faces)
+        written.append(path)
+        print(f"{path}: {len(verts)} vertices, {len(faces)} faces")
+    return latents, written
+
+
+if __name__ == "__main__":
+    main()

@@ -376,6 +376,34 @@ int surfd_xattn_set_param(surfd_xattn *a, const char *name, const float *src, co
 int surfd_xattn_forward(surfd_xattn *a, const float *x, const float *context, const unsigned char *mask, float *out,
                         int B, int N, int M, surfd_stream s);
 
+/* ------------------------------------------------------------------------------------ */
+/* Point-cloud encoder: Dgcnn (AutoEncoder/models/dgcnn.py:9-115), eval mode.             */
+/* Used frozen by AutoEncoder/encdec/export_meshes.py:61-100 and training_loop_single.py  */
+/* to turn point clouds into latents.  Plain fp32; bitwise deterministic.                 */
+/* ------------------------------------------------------------------------------------ */
+typedef struct surfd_dgcnn surfd_dgcnn;
+/* Dgcnn(size_latent, k) with aggregate_ops_local = aggregate_ops_global = "max" (AutoEncoder/models/dgcnn.py:27-53); 1 <= k <= 32. */
+int surfd_dgcnn_create(int size_latent, int k, surfd_dgcnn **out);
+void surfd_dgcnn_destroy(surfd_dgcnn *d);
+int surfd_dgcnn_num_params(const surfd_dgcnn *d);
+/* keys and shapes exactly as in Dgcnn(size_latent).state_dict() / ckpt["encoder"] (AutoEncoder/trainers/encdec.py:299-305):
+ * bn_1..bn_5.{weight,bias,running_mean,running_var,num_batches_tracked}, then conv_1..conv_5.weight */
+int surfd_dgcnn_param_info(const surfd_dgcnn *d, int i, const char **key, int64_t shape[4], int *ndim);
+/* fp32 device tensors; num_batches_tracked is accepted and ignored (dev_ptr may be NULL for it) */
+int surfd_dgcnn_set_param(surfd_dgcnn *d, const char *key, const void *dev_ptr, const int64_t *shape, int ndim, surfd_stream s);
+/* after the last set_param: folds BatchNorm (running statistics, eps 1e-5) into a per-channel scale / shift and forms the
+ * factorised EdgeConv weights */
+int surfd_dgcnn_finalize(surfd_dgcnn *d, surfd_stream s);
+/* knn_points(x, x, K=k) (AutoEncoder/models/dgcnn.py:86): pts[B,N,3] -> dists[B,N,k] (squared, fp32; nullable) and idx[B,N,k] (int32), sorted
+ * ascending, each point its own first neighbour, ties broken by the lower index.  N < k is SURFD_ERR_ARG. */
+int surfd_dgcnn_knn(const surfd_dgcnn *d, const float *pts, int B, int N, float *dists, int32_t *idx, surfd_stream s);
+/* Dgcnn.forward(x) (AutoEncoder/models/dgcnn.py:77-115): pts[B,N,3] -> feat[B,size_latent].  Clouds are independent: a cloud's latent has the
+ * same bits whichever batch it is encoded in. */
+int surfd_dgcnn_forward(surfd_dgcnn *d, const float *pts, int B, int N, float *feat, surfd_stream s);
+/* the same, and (when x1234 is not NULL) the per-point features of the four EdgeConv blocks, torch.cat((x1, x2, x3, x4), -1)
+ * [B,N,512] (AutoEncoder/models/dgcnn.py:88-100), the input of conv_5 (for tests and feature export) */
+int surfd_dgcnn_forward_features(surfd_dgcnn *d, const float *pts, int B, int N, float *feat, float *x1234, surfd_stream s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -120,6 +120,15 @@ _SIGS = {
     "surfd_xattn_destroy": (None, [_P]),
     "surfd_xattn_set_param": (C.c_int, [_P, C.c_char_p, _P, c_i64p, C.c_int, _P]),
     "surfd_xattn_forward": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "surfd_dgcnn_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(_P)]),
+    "surfd_dgcnn_destroy": (None, [_P]),
+    "surfd_dgcnn_num_params": (C.c_int, [_P]),
+    "surfd_dgcnn_param_info": (C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), c_i64p, C.POINTER(C.c_int)]),
+    "surfd_dgcnn_set_param": (C.c_int, [_P, C.c_char_p, _P, c_i64p, C.c_int, _P]),
+    "surfd_dgcnn_finalize": (C.c_int, [_P, _P]),
+    "surfd_dgcnn_knn": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "surfd_dgcnn_forward": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
+    "surfd_dgcnn_forward_features": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "surfd_mc_lut_count": (C.c_int, []),
     "surfd_mc_lut": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.POINTER(C.c_byte)), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }

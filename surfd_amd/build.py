@@ -21,6 +21,7 @@ SOURCES = ["core.hip", "decoder.hip", "grid.hip", "unet.hip", "conv_f16x2.hip", 
 # fp32 op sequence (grid coordinates, posterior updates) into FMAs.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-pass-failed", "-ffp-contract=off"]
 FLAGS += os.environ.get("SURFD_EXTRA_HIPCC_FLAGS", "").split()      # debugging builds only (e.g. -DSURFD_DEC_STAMPS)
+SOURCES.insert(SOURCES.index("mcubes.cpp"), "dgcnn.hip")             # the point-cloud encoder (surfd_amd/dgcnn.py)
 
 
 def _hipcc() -> str:

@@ -90,6 +90,43 @@ def synth_cross_attention_state_dict(query_dim: int, context_dim: int, heads: in
     return {k: _normal(s, 0.1 if k.endswith("bias") else 1.5 / s[-1] ** 0.5, "xattn." + k, seed) for k, s in shapes.items()}
 
 
+def dgcnn_param_spec(size_latent: int):
+    """[(key, shape)] of the reference Dgcnn(size_latent).state_dict() in its order (AutoEncoder/models/dgcnn.py:42-53)."""
+    chans = (64, 64, 128, 256, size_latent)
+    spec = []
+    for i, c in enumerate(chans, 1):
+        spec += [(f"bn_{i}.{f}", (c,)) for f in ("weight", "bias", "running_mean", "running_var")]
+        spec.append((f"bn_{i}.num_batches_tracked", ()))
+    for i, (c, cin) in enumerate(zip(chans, (6, 128, 128, 256, 512)), 1):
+        spec.append((f"conv_{i}.weight", (c, cin)))
+    return spec
+
+
+def synth_dgcnn_state_dict(size_latent: int = 64, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """Encoder weights in the layout of ckpt["encoder"].  BN weights are drawn around +-1 so that every block has channels of
+    both signs (the monotone max / min reduction of csrc/dgcnn.hip takes both branches), and channel 3 of every block has a
+    weight of exactly zero; running variances are positive and spread over [0.25, 2.25)."""
+    sd: Dict[str, torch.Tensor] = {}
+    for key, shape in dgcnn_param_spec(size_latent):
+        leaf = key.rsplit(".", 1)[-1]
+        g = _gen(key, seed)
+        if leaf == "num_batches_tracked":
+            sd[key] = torch.tensor(100, dtype=torch.long)
+        elif leaf == "weight" and key.startswith("bn_"):
+            w = (torch.rand(shape, generator=g) * 0.8 + 0.6) * torch.where(torch.rand(shape, generator=g) < 0.3, -1.0, 1.0)
+            w[3] = 0.0
+            sd[key] = w
+        elif leaf == "bias":
+            sd[key] = torch.randn(shape, generator=g) * 0.1
+        elif leaf == "running_mean":
+            sd[key] = torch.randn(shape, generator=g) * 0.1
+        elif leaf == "running_var":
+            sd[key] = torch.rand(shape, generator=g) * 2.0 + 0.25
+        else:
+            sd[key] = torch.randn(shape, generator=g) / shape[1] ** 0.5
+    return sd
+
+
 def synth_noise(num_steps: int, sample_index: int, latent_len: int, seed: int = 1234) -> torch.Tensor:
     """Noise stream of ONE sample: row 0 is x_T, row 1+k is the z drawn at loop step k.
 

@@ -1,0 +1,202 @@
+"""GPU tests of the point-cloud encoder (surfd_amd/dgcnn.py, csrc/dgcnn.hip; run with -m gpu on an MI355X): kNN against
+exact brute force, the EdgeConv features and the latents against the reference's own Dgcnn (tests/golden/g18_dgcnn.npz,
+tools/make_golden.py g18), bitwise determinism / batch independence / permutation invariance, and the reconstruction driver."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from surfd_amd import synth
+from surfd_amd.dgcnn import Dgcnn, knn_points
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+T = torch.from_numpy
+
+
+def _encoder(L):
+    m = Dgcnn(L)
+    m.load_state_dict(synth.synth_dgcnn_state_dict(L, seed=0), strict=True)
+    return m.cuda().eval()
+
+
+def _brute_knn(x, K):
+    """stable (distance, index) order of the fp64 squared distances: (dists fp64, idx int64)"""
+    x = x.double()
+    ds, ids = [], []
+    for q0 in range(0, x.shape[1], 1024):
+        d = ((x[:, q0:q0 + 1024, None, :] - x[:, None, :, :]) ** 2).sum(-1)
+        s, i = torch.sort(d, dim=-1, stable=True)
+        ds.append(s[..., :K]); ids.append(i[..., :K])
+    return torch.cat(ds, 1), torch.cat(ids, 1)
+
+
+def _lattice_cloud(B, N, seed):
+    """points on the 1/8 lattice of [-2, 2]^3 (every fp32 squared distance exact; ties everywhere) plus duplicated points"""
+    g = torch.Generator().manual_seed(seed)
+    side = max(3, int(round((N / 4) ** (1 / 3))))                  # a lattice small enough to hold duplicates
+    p = torch.randint(-side, side + 1, (B, N, 3), generator=g).float() / 8
+    dup = torch.randint(0, N, (B, N // 10), generator=g)
+    p[torch.arange(B)[:, None], torch.randint(0, N, (B, N // 10), generator=g)] = p[torch.arange(B)[:, None], dup]
+    return p
+
+
+def _surface_cloud(B, N, seed):
+    g = torch.Generator().manual_seed(seed)
+    v = torch.randn(B, N, 3, generator=g)
+    v = v / v.norm(dim=-1, keepdim=True) * torch.tensor([0.6, 0.4, 0.5])
+    return (v + torch.randn(B, N, 3, generator=g) * 0.01).float()
+
+
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("N", [20, 777, 10000])
+def test_knn_exact_on_lattice(B, N):
+    x = _lattice_cloud(B, N, seed=N + B)
+    d, i = knn_points(x.cuda(), 20)
+    rd, ri = _brute_knn(x.cuda(), 20)
+    assert i.dtype == torch.int64 and d.dtype == torch.float32
+    assert torch.equal(i, ri), f"{int((i != ri).sum())} indices differ"
+    assert torch.equal(d.double(), rd)
+
+
+@pytest.mark.parametrize("K", [1, 8, 13, 32])
+def test_knn_other_k_exact_on_lattice(K):
+    x = _lattice_cloud(2, 3000, seed=K)
+    d, i = knn_points(x.cuda(), K)
+    rd, ri = _brute_knn(x.cuda(), K)
+    assert torch.equal(i, ri) and torch.equal(d.double(), rd)
+
+
+def test_knn_fixture_clouds(golden):
+    z = golden("g18_dgcnn")
+    for name in ("a", "b"):
+        _, i = knn_points(T(z[f"{name}__pts"])[None].cuda(), 20)
+        assert np.array_equal(i[0].cpu().numpy(), z[f"{name}__knn_idx"].astype(np.int64)), name
+
+
+@pytest.mark.parametrize("seed", [0, 1])
+def test_knn_continuous_against_brute_force(seed):
+    x = _surface_cloud(2, 10000, seed).cuda()
+    d, i = knn_points(x, 20)
+    rd, ri = _brute_knn(x, 21)
+    kth, rkth = d[..., -1].double(), rd[..., 19]
+    rel = float(((kth - rkth).abs() / rkth.clamp_min(1e-30)).max())
+    assert rel <= 1e-6, rel
+    # index sets agree except at near-ties of the boundary: a point in one set and not in the other is within fp32 rounding of
+    # the K-th distance
+    same = (i.sort(-1).values == ri[..., :20].sort(-1).values).all(-1)
+    bad = (~same).nonzero()
+    for b, n in bad.tolist():
+        diff = set(i[b, n].tolist()) ^ set(ri[b, n, :20].tolist())
+        dd = ((x[b, list(diff)].double() - x[b, n].double()) ** 2).sum(-1)
+        assert float((dd - rkth[b, n]).abs().max()) <= 2e-6 * float(rkth[b, n]), (b, n)
+    assert len(bad) <= 20, len(bad)
+
+
+def test_edgeconv_features_against_reference(golden):
+    z = golden("g18_dgcnn")
+    m = _encoder(32)
+    for name in ("a", "b", "c"):
+        x = T(z[f"{name}__pts"])[None].cuda()
+        _, x1234 = m.forward_features(x)
+        got = x1234[0, T(z[f"{name}__rows"]).long().cuda()].cpu()
+        ref = T(z[f"{name}__x1234"])
+        for blk, (c0, c1) in enumerate(((0, 64), (64, 128), (128, 256), (256, 512)), 1):
+            g, r = got[:, c0:c1], ref[:, c0:c1]
+            err = float((g - r).abs().max())
+            assert err <= 1e-5 * float(r.abs().max()) + 1e-6, f"cloud {name} x{blk}: max err {err:.3e} (scale {float(r.abs().max()):.3f})"
+
+
+@pytest.mark.parametrize("L", [32, 64])
+def test_latents_against_reference(golden, L):
+    z = golden("g18_dgcnn")
+    m = _encoder(L)
+    for name in ("a", "b", "c"):
+        x = T(z[f"{name}__pts"])[None].cuda()
+        lat = m(x)[0].double().cpu()
+        r64 = T(z[f"{name}__latent_L{L}_f64"])
+        r32 = T(z[f"{name}__latent_L{L}_f32"]).double()
+        e_gpu = float((lat - r64).abs().max())
+        e_ref = float((r32 - r64).abs().max())
+        bound = 2 * e_ref + 1e-5 * float(r64.abs().max())
+        assert e_gpu <= bound, f"cloud {name} L={L}: GPU vs fp64 {e_gpu:.3e}, reference fp32 vs fp64 {e_ref:.3e}, bound {bound:.3e}"
+        print(f"cloud {name} L={L}: GPU vs fp64 {e_gpu:.3e}, reference fp32 vs fp64 {e_ref:.3e}")
+
+
+def test_latent_index_column():
+    m = _encoder(32)
+    x = _surface_cloud(3, 500, 5).cuda()
+    li = torch.tensor([4.0, 7.0, 9.0], device="cuda")
+    out = m(x, latent_index=li)
+    assert out.shape == (3, 33)
+    assert torch.equal(out[:, :32], m(x)) and torch.equal(out[:, 32], li)
+
+
+def test_bitwise_determinism_batch_independence_and_permutation():
+    m = _encoder(64)
+    for seed in range(11, 21):                 # a cloud without a distance tie at the k-th neighbour (for the permutation)
+        x = _surface_cloud(8, 10000, seed).cuda()
+        d, _ = knn_points(x, 21)
+        if bool((d[..., 19] < d[..., 20]).all()):
+            break
+    else:
+        pytest.fail("no tie-free test cloud among seeds 11..20")
+    outs = torch.stack([m(x) for _ in range(40)])
+    distinct = torch.unique(outs.view(40, -1).view(torch.int32), dim=0).shape[0]
+    assert distinct == 1, f"{distinct} distinct outputs over 40 encodes of B = 8"
+    ref = outs[0]
+    for b in range(8):
+        assert torch.equal(m(x[b:b + 1])[0], ref[b]), f"cloud {b}: alone != in a batch of 8"
+    # permutation of the points: no distance tie at the k-th neighbour, so the same neighbour sets
+    g = torch.Generator().manual_seed(3)
+    perm = torch.randperm(10000, generator=g).cuda()
+    assert torch.equal(m(x[:, perm]), ref)
+
+
+def _write_inputs(tmp_path):
+    g = torch.Generator().manual_seed(21)
+    u, v = torch.rand(6000, generator=g) * 6.2832, torch.rand(6000, generator=g) * 6.2832
+    pcd = torch.stack([(0.5 + 0.2 * torch.cos(v)) * torch.cos(u), 0.2 * torch.sin(v), (0.5 + 0.2 * torch.cos(v)) * torch.sin(u)], 1)
+    np.savez(tmp_path / "shape_a.npz", pcd=pcd.numpy().astype(np.float32), udfs=np.zeros(3, np.float32))
+    np.save(tmp_path / "shape_b.npy", (pcd * 0.8).numpy().astype(np.float32))
+    return [str(tmp_path / "shape_a.npz"), str(tmp_path / "shape_b.npy")]
+
+
+def _driver(args, timeout=600):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "examples", "reconstruct.py")] + args, capture_output=True, text=True,
+                       timeout=timeout, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    return r.stdout
+
+
+def test_reconstruct_driver_meshes(tmp_path):
+    inputs = _write_inputs(tmp_path)
+    out = tmp_path / "out"
+    _driver(["--synthetic", "--resolution", "64", "--num_points_pcd", "4000", "--output_dir", str(out)] + inputs)
+    for item in ("shape_a", "shape_b"):
+        text = (out / f"{item}_meshudf.obj").read_text()
+        assert text.count("\nv ") + text.startswith("v ") > 0 and "\nf " in text, item
+
+
+def test_reconstruct_driver_latents_only(tmp_path):
+    inputs = _write_inputs(tmp_path)
+    out = tmp_path / "lat"
+    _driver(["--synthetic", "--latents_only", "--num_points_pcd", "4000", "--output_dir", str(out)] + inputs)
+    z = np.load(out / "latents.npz")
+    assert sorted(z.files) == ["shape_a", "shape_b"]
+    # the same draws and the same encoder, called directly
+    from surfd_amd.dgcnn import random_point_sampling
+    ckpt = torch.load(out / "ae_synthetic.pt", map_location="cpu")
+    m = Dgcnn(32)
+    m.load_state_dict(ckpt["encoder"], strict=True)
+    m = m.cuda().eval()
+    torch.manual_seed(10)
+    a = torch.from_numpy(np.load(inputs[0])["pcd"]).cuda()
+    b = torch.from_numpy(np.load(inputs[1])).cuda()
+    lat_a = m(random_point_sampling(a, 4000)[None])[0]
+    lat_b = m(random_point_sampling(b, 4000)[None])[0]
+    assert np.array_equal(z["shape_a"], lat_a.cpu().numpy())
+    assert np.array_equal(z["shape_b"], lat_b.cpu().numpy())

@@ -703,6 +703,105 @@ def g14_cross_attention(R):
     save("g14_cross_attention", **out)
 
 
+# ------------------------------------------------------------------------------------
+G18_ROWS = 128
+
+
+def install_knn_stub():
+    """pytorch3d.ops (not installed, no ROCm build) for the reference's Dgcnn (AutoEncoder/models/dgcnn.py:5,86): knn_points
+    as a brute-force torch computation with the kernel's arithmetic (diff = p1 - p2, squared terms summed over d = 0, 1, 2
+    one rounding at a time) and a STABLE sort, so that ties go to the lower index; knn_gather as plain indexing."""
+    def knn_points(p1, p2, K=1, **kw):
+        d_all, i_all = [], []
+        for q0 in range(0, p1.shape[1], 1024):
+            q = p1[:, q0:q0 + 1024]
+            dx = q[:, :, None, 0] - p2[:, None, :, 0]
+            dy = q[:, :, None, 1] - p2[:, None, :, 1]
+            dz = q[:, :, None, 2] - p2[:, None, :, 2]
+            d = dx * dx
+            d = d + dy * dy
+            d = d + dz * dz
+            ds, ids = torch.sort(d, dim=-1, stable=True)
+            d_all.append(ds[..., :K]); i_all.append(ids[..., :K])
+        return torch.cat(d_all, 1), torch.cat(i_all, 1), None
+
+    def knn_gather(x, idx, lengths=None):
+        return x[torch.arange(x.shape[0])[:, None, None], idx]
+
+    pkg = types.ModuleType("pytorch3d")
+    ops = types.ModuleType("pytorch3d.ops")
+    ops.knn_points, ops.knn_gather = knn_points, knn_gather
+    pkg.ops = ops
+    sys.modules["pytorch3d"], sys.modules["pytorch3d.ops"] = pkg, ops
+    return knn_points
+
+
+def g18_surface_cloud(n, seed, jitter=0.004):
+    """n points on a torus (R 0.5, r 0.15) and the surface of a box next to it, with Gaussian jitter"""
+    g = torch.Generator().manual_seed(seed)
+    nt = n * 3 // 5
+    u, v = torch.rand(nt, generator=g) * 2 * np.pi, torch.rand(nt, generator=g) * 2 * np.pi
+    tor = torch.stack([(0.5 + 0.15 * torch.cos(v)) * torch.cos(u), (0.5 + 0.15 * torch.cos(v)) * torch.sin(u), 0.15 * torch.sin(v)], 1)
+    nb = n - nt
+    half = torch.tensor([0.3, 0.2, 0.25])
+    p = (torch.rand(nb, 3, generator=g) * 2 - 1) * half
+    face = torch.randint(0, 3, (nb,), generator=g)
+    sign = torch.where(torch.rand(nb, generator=g) < 0.5, -1.0, 1.0)
+    p[torch.arange(nb), face] = sign * half[face]
+    box = p + torch.tensor([0.1, -0.2, 0.45])
+    pts = torch.cat([tor, box], 0)
+    pts = pts[torch.randperm(n, generator=g)]
+    return (pts + torch.randn(n, 3, generator=g) * jitter).float()
+
+
+G18_CLOUDS = (("a", 2048, 1801), ("b", 2048, 1802), ("c", 10000, 1803))
+
+
+def g18_dgcnn(R):
+    """The auto-encoder's encoder: the reference's own Dgcnn on synth_dgcnn_state_dict weights, fp32 and fp64, on three
+    surface clouds; plus the indices the reference's random_point_sampling draws under torch.manual_seed(10)."""
+    knn = install_knn_stub()
+    from AutoEncoder.models import dgcnn as rdg
+    from utils import utils as rutils
+    out = {}
+    rows_g = torch.Generator().manual_seed(1818)
+    for name, n, seed in G18_CLOUDS:
+        x = g18_surface_cloud(n, seed)[None]
+        _, i32, _ = knn(x, x, K=20)
+        _, i64, _ = knn(x.double(), x.double(), K=20)
+        same = torch.equal(i32.sort(-1).values, i64.sort(-1).values)
+        assert same, f"cloud {name}: fp32 and fp64 neighbour sets differ; pick another seed"
+        out[f"{name}__pts"] = x[0]
+        if n == 2048:
+            out[f"{name}__knn_idx"] = i32[0].to(torch.int16)
+        rows = torch.randperm(n, generator=rows_g)[:G18_ROWS].sort().values
+        out[f"{name}__rows"] = rows.to(torch.int32)
+        for L in (32, 64):
+            sd = synth.synth_dgcnn_state_dict(L, seed=0)
+            for prec, dt in (("f32", torch.float32), ("f64", torch.float64)):
+                m = rdg.Dgcnn(L).eval().to(dt)
+                m.load_state_dict(sd, strict=True)
+                xx = x.to(dt)
+                with torch.no_grad():
+                    out[f"{name}__latent_L{L}_{prec}"] = m(xx)[0]
+                    if L == 32 and prec == "f32":        # blocks 1-4 do not depend on size_latent (same weights for 32 and 64)
+                        feats, f = [], xx
+                        for conv, bn in ((m.conv_1, m.bn_1), (m.conv_2, m.bn_2), (m.conv_3, m.bn_3), (m.conv_4, m.bn_4)):
+                            f = m.block_forward(f, conv, bn, i32, "max")
+                            feats.append(f)
+                        out[f"{name}__x1234"] = torch.cat(feats, -1)[0, rows]
+        print(f"  cloud {name}: N={n}, fp32/fp64 neighbour sets agree")
+    # random_point_sampling: a cloud whose points are their own indices shows which indices were drawn
+    for tag, shape, num in (("larger", (2048, 3), 1000), ("smaller", (500, 3), 1000), ("batched", (2, 700, 3), 256)):
+        pcd = torch.arange(shape[-2]).float()[:, None].expand(*shape).contiguous()
+        torch.manual_seed(10)
+        s = rutils.random_point_sampling(pcd, num)
+        out[f"rps_{tag}__shape"] = np.array(shape)
+        out[f"rps_{tag}__num"] = np.array(num)
+        out[f"rps_{tag}__idx"] = s[..., 0].long()
+    save("g18_dgcnn", **out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
@@ -717,7 +816,8 @@ def main():
             "g9d64": lambda: g9_d64(R), "g11": lambda: g11_conditioned_loops(R), "g12": lambda: g12_contractive(R),
             "g13": lambda: g13_marching_cubes(R, a.mc512), "g13luts": lambda: g13_lut_hashes(R), "g13ext": lambda: g13_extension_cases(R),
             "g15": lambda: g15_image_preprocess(R), "g16": lambda: g16_clip_towers(R), "g16bpe": lambda: g16_bpe_merges(R),
-            "g17": lambda: g17_spatial_transformer(R), "g14": lambda: g14_cross_attention(R)}
+            "g17": lambda: g17_spatial_transformer(R), "g14": lambda: g14_cross_attention(R),
+            "g18": lambda: g18_dgcnn(R)}
     only = [s for s in a.only.split(",") if s]
     for name, fn in jobs.items():
         if only and name not in only:
