@@ -1,0 +1,94 @@
+#!/usr/bin/env python3
+"""Meshes -> training items of the auto-encoder on the MI355X path: the counterpart of the reference's
+AutoEncoder/encdec/preprocess_udfs.py (PrepareOneUDF, lines 118-151).
+
+    python examples/preprocess_udfs.py --output_dir out/ chair.obj meshes/ [more OBJ files or directories]
+    python examples/preprocess_udfs.py --num_surface_points 20000 --num_queries_per_std 5000 4000 500 500 --output_dir out/ a.obj
+
+One ``<name>.npz`` per mesh with the reference's keys and dtypes: ``vertices`` [V, 3] float32, ``triangles`` [F, 3] int64,
+``pcd`` [100 000, 3] float32 (a uniform surface cloud), ``coords`` [500 000, 3] float32 (queries around a second surface cloud
+at sigma 0.003 / 0.01 / 0.1 plus uniform ones), ``labels`` [500 000] float32 (the UDF clipped to 0.1) and ``gradients``
+[500 000, 3] float32.  The defaults are the reference's (100 000 surface points, 250 000 / 200 000 / 25 000 / 25 000 queries).
+The files are inputs of examples/reconstruct.py.  Meshes are taken as already normalised to [-1, 1]^3 (the reference's separate
+normalized_obj.py); a mesh with a vertex outside gets a warning.  The random numbers come from the GPU's global RNG, seeded
+with ``--seed`` before every mesh.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from surfd_amd import meshprep  # noqa: E402
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("inputs", nargs="+", help="OBJ files, or directories holding them")
+    ap.add_argument("--output_dir", default="outputs/udfs")
+    ap.add_argument("--num_surface_points", type=int, default=100_000)
+    ap.add_argument("--num_queries_per_std", type=int, nargs=4, default=[250_000, 200_000, 25_000, 25_000],
+                    metavar=("N_0.003", "N_0.01", "N_0.1", "N_UNIFORM"))
+    ap.add_argument("--max_dist", type=float, default=0.1)
+    ap.add_argument("--seed", type=int, default=0)
+    return ap.parse_args(argv)
+
+
+def list_inputs(inputs):
+    files = []
+    for p in inputs:
+        if os.path.isdir(p):
+            files += [os.path.join(p, f) for f in sorted(os.listdir(p)) if f.lower().endswith(".obj")]
+        else:
+            files.append(p)
+    return files
+
+
+def prepare_one(path, a):
+    v, t = meshprep.read_mesh(path)
+    if len(t) == 0:
+        raise SystemExit(f"{path}: no faces")
+    if float(v.abs().max()) > 1.0:
+        print(f"warning: {path} has vertices outside [-1, 1]^3 (max |coordinate| {float(v.abs().max()):.4g}); queries are clipped "
+              "to that cube, normalise the mesh first", file=sys.stderr)
+    vd, td = v.cuda(), t.cuda()
+    pcd = meshprep.sample_points_uniformly(vd, td, a.num_surface_points)                       # preprocess_udfs.py:126-127
+    coords, labels, gradients = meshprep.compute_udf_from_mesh(vd, td, num_surface_points=a.num_surface_points,
+                                                               num_queries_per_std=list(a.num_queries_per_std), max_dist=a.max_dist)
+    return dict(vertices=v.numpy(), triangles=t.numpy(), pcd=pcd.cpu().numpy(), coords=coords.cpu().numpy(),
+                labels=labels.cpu().numpy(), gradients=gradients.cpu().numpy())
+
+
+def run(a):
+    files = list_inputs(a.inputs)
+    if not files:
+        raise SystemExit("no input meshes")
+    names = [os.path.splitext(os.path.basename(f))[0] for f in files]
+    if len(set(names)) != len(names):
+        raise SystemExit(f"item ids must be unique: {names}")
+    if not torch.cuda.is_available():
+        raise SystemExit("preprocess_udfs.py runs on the GPU (no CPU fallback)")
+    os.makedirs(a.output_dir, exist_ok=True)
+    written = []
+    for path, name in zip(files, names):
+        torch.manual_seed(a.seed)
+        item = prepare_one(path, a)
+        out = os.path.join(a.output_dir, name + ".npz")
+        np.savez(out, **item)
+        written.append(out)
+        print(f"{out}: {len(item['triangles'])} triangles, pcd {item['pcd'].shape[0]}, coords {item['coords'].shape[0]}, "
+              f"mean label {float(item['labels'].mean()):.5f}")
+    return written
+
+
+def main(argv=None):
+    return run(parse(argv))
+
+
+if __name__ == "__main__":
+    main()

@@ -48,6 +48,8 @@ def parse(argv=None):
     ap.add_argument("--latents_only", action="store_true", help="write latents.npz and skip meshing")
     ap.add_argument("--synthetic", action="store_true", help="create a synthetic checkpoint under --output_dir and use it")
     ap.add_argument("--size_latent", type=int, default=32, help="latent size of the --synthetic checkpoint")
+    ap.add_argument("--metrics", action="store_true",
+                    help="for inputs that carry 'vertices' / 'triangles' (examples/preprocess_udfs.py): write metrics.json")
     return ap.parse_args(argv)
 
 
@@ -115,6 +117,30 @@ def load_models(ae_dir):
     return encoder, decoder.cuda().eval(), size_latent
 
 
+def item_metrics(path, verts, faces, field, seed):
+    """what --metrics records for one item, or None where the input carries no mesh: mesh_distance between the reconstruction
+    and the original and, where the file has 'coords' / 'labels', the mean absolute error of the decoder's UDF at those queries"""
+    from surfd_amd import meshprep
+    if not path.endswith(".npz"):
+        return None
+    with np.load(path) as z:
+        if "vertices" not in z.files or "triangles" not in z.files:
+            return None
+        ov, ot = torch.from_numpy(z["vertices"].astype(np.float32)).cuda(), torch.from_numpy(z["triangles"].astype(np.int64)).cuda()
+        coords = torch.from_numpy(z["coords"].astype(np.float32)).cuda() if "coords" in z.files and "labels" in z.files else None
+        labels = torch.from_numpy(z["labels"].astype(np.float32)).cuda() if coords is not None else None
+    out = {"vertices": int(len(verts)), "faces": int(len(faces))}
+    if len(faces):
+        g = torch.Generator(device="cuda").manual_seed(seed)
+        rv, rt = torch.from_numpy(np.ascontiguousarray(verts, dtype=np.float32)).cuda(), torch.from_numpy(np.ascontiguousarray(faces).astype(np.int64)).cuda()
+        d = meshprep.mesh_distance(rv, rt, ov, ot, generator=g)
+        out.update(reconstruction_to_original=d["d12"], original_to_reconstruction=d["d21"], mesh_distance=d["sum"])
+    if coords is not None:
+        pred = torch.cat([field(coords[i:i + 2 ** 16]) for i in range(0, len(coords), 2 ** 16)])
+        out["udf_mean_abs_error"] = float((pred.reshape(-1) - labels).abs().double().mean())
+    return out
+
+
 def main(argv=None):
     return run(parse(argv))
 
@@ -151,6 +177,7 @@ def run(a):
 
     decoder.bind_latents(latents)
     written = []
+    metrics = {}
     for k, item in enumerate(ids):
         field = make_udf_func(decoder, latents[k], sample=k)
 
@@ -166,6 +193,17 @@ def run(a):
         meshproc.write_obj(path, verts, faces)
         written.append(path)
         print(f"{path}: {len(verts)} vertices, {len(faces)} faces")
+        if a.metrics:
+            m = item_metrics(files[k], verts, faces, field, a.seed)
+            if m is not None:
+                metrics[item] = m
+    if a.metrics:
+        import json
+        path = os.path.join(a.output_dir, "metrics.json")
+        with open(path, "w") as f:
+            json.dump(metrics, f, indent=1)
+        written.append(path)
+        print(f"{path}: {len(metrics)} items")
     return latents, written
 
 

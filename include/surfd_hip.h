@@ -404,6 +404,33 @@ int surfd_dgcnn_forward(surfd_dgcnn *d, const float *pts, int B, int N, float *f
  * [B,N,512] (AutoEncoder/models/dgcnn.py:88-100), the input of conv_5 (for tests and feature export) */
 int surfd_dgcnn_forward_features(surfd_dgcnn *d, const float *pts, int B, int N, float *feat, float *x1234, surfd_stream s);
 
+/* ------------------------------------------------------------------------------------ */
+/* Mesh distance: the exact closest point of a triangle mesh for many query points.       */
+/* Stands for open3d's RaycastingScene.compute_closest_points as AutoEncoder/utils.py:223-240 */
+/* uses it (compute_udf_and_gradients, under compute_udf_from_mesh, utils.py:268-314, and */
+/* AutoEncoder/encdec/preprocess_udfs.py:118-151).  Plain fp32; bitwise deterministic.    */
+/* ------------------------------------------------------------------------------------ */
+typedef struct surfd_mesh surfd_mesh;
+#define SURFD_MESH_BRUTE_FORCE 1   /* flags bit 0: test every (query, triangle) pair, no culling */
+/* vertices[V,3] fp32 and triangles[F,3] int32 on the device -> per-triangle records and per-tile bounding spheres (the inputs
+ * are not referenced after the call).  F >= 1; every index must lie in [0, V): checked on the device and reported as
+ * SURFD_ERR_ARG, never as a fault.  Degenerate triangles are legal and count as the segment or point they are; thin ones are
+ * handled at full accuracy (the normals are formed in fp64 once per triangle).  host-sync. */
+int surfd_mesh_create(const float *vertices, int V, const int32_t *triangles, int F, surfd_stream s, surfd_mesh **out);
+void surfd_mesh_destroy(surfd_mesh *m);
+int surfd_mesh_num_triangles(const surfd_mesh *m);
+/* RaycastingScene.compute_closest_points as AutoEncoder/utils.py:228-234 calls it:
+ * queries[Q,3] -> dist[Q] (fp32), closest[Q,3] (fp32, a point of triangle tri[q]), tri[Q] (int32, index into the triangles given
+ * to create); any of the three may be NULL.  The winner of a query is the minimum under (squared distance, triangle index), so
+ * its outputs do not depend on the other queries of the call, and the culled path equals SURFD_MESH_BRUTE_FORCE bit for bit.
+ * Culling skips tiles of 32 consecutive triangles for waves of 64 consecutive queries; it only pays when both are spatially
+ * coherent (e.g. sorted by Morton code, as the Python wrapper does).  skipped_tiles (nullable, int64 on the device) receives
+ * the number of (wave, tile) visits the culled path skipped (waves of 64 consecutive queries, ceil(Q / 64) of them).  Q = 0 is a
+ * no-op.  The handle keeps the call's partial results in a workspace of its own (grown on demand, which syncs the stream): a
+ * handle serves one stream and one host thread at a time; use one handle per stream for concurrent calls. */
+int surfd_mesh_closest(const surfd_mesh *m, const float *queries, int Q, int flags, float *dist, float *closest, int32_t *tri,
+                       int64_t *skipped_tiles, surfd_stream s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,7 @@ SOURCES = ["core.hip", "decoder.hip", "grid.hip", "unet.hip", "conv_f16x2.hip", 
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-pass-failed", "-ffp-contract=off"]
 FLAGS += os.environ.get("SURFD_EXTRA_HIPCC_FLAGS", "").split()      # debugging builds only (e.g. -DSURFD_DEC_STAMPS)
 SOURCES.insert(SOURCES.index("mcubes.cpp"), "dgcnn.hip")             # the point-cloud encoder (surfd_amd/dgcnn.py)
+SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshdist.hip")          # closest point of a mesh (surfd_amd/meshprep.py)
 
 
 def _hipcc() -> str:

@@ -1,0 +1,274 @@
+"""Mesh preprocessing on the MI355X path: mesh -> (surface cloud, query points, UDF labels, gradients), and the distance of
+points or meshes to a mesh.  The counterparts of the reference's open3d-based data preparation:
+
+  read_mesh                  <- AutoEncoder/utils.py:13-38               (OBJ only)
+  sample_points_uniformly    <- open3d TriangleMesh.sample_points_uniformly as used at utils.py:280, preprocess_udfs.py:126
+  sample_points_around_pcd   <- AutoEncoder/utils.py:167-220             (same RNG calls in the same order)
+  closest_points, MeshDistance <- open3d RaycastingScene.compute_closest_points (utils.py:228-234)
+  compute_udf_and_gradients  <- AutoEncoder/utils.py:223-240
+  compute_udf_from_mesh      <- AutoEncoder/utils.py:268-314
+  point_to_mesh_distance, mesh_distance   no counterpart: how far a reconstruction is from the mesh it came from
+
+Where the reference takes an open3d mesh (``mesh_o3d``) these take ``(vertices [V, 3] float32, triangles [F, 3] integer)``.
+The closest-point search runs in csrc/meshdist.hip and nowhere else: device tensors in, device tensors out, CPU tensors are
+refused (no CPU fallback).  The two samplers and read_mesh are plain torch / file plumbing and work on any device.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import List, Optional, Tuple
+
+import torch
+import torch.nn.functional as F
+from torch import Tensor
+
+from . import _native as N
+
+
+# ---- files --------------------------------------------------------------------------------------------------------------------
+def read_mesh(mesh_path, dtype: torch.dtype = torch.float) -> Tuple[Tensor, Tensor]:
+    """OBJ file -> (vertices [V, 3] ``dtype``, triangles [F, 3] int64).  Reads ``v x y z [...]`` and ``f`` lines whose corners
+    are ``v``, ``v/vt``, ``v/vt/vn`` or ``v//vn`` with positive (1-based) or negative (relative to the vertices read so far)
+    indices; polygons are fan-triangulated; every other line is ignored."""
+    mesh_path = str(mesh_path)
+    if not os.path.exists(mesh_path):
+        raise ValueError(f"The mesh file {mesh_path} does not exists.")
+    if not mesh_path.lower().endswith(".obj"):
+        raise ValueError(f"read_mesh reads OBJ files only, got {mesh_path}")
+    verts: List[List[float]] = []
+    tris: List[List[int]] = []
+    with open(mesh_path) as fh:
+        for ln, line in enumerate(fh, 1):
+            parts = line.split()
+            if not parts:
+                continue
+            if parts[0] == "v":
+                if len(parts) < 4:
+                    raise ValueError(f"{mesh_path}:{ln}: a vertex needs three coordinates")
+                verts.append([float(parts[1]), float(parts[2]), float(parts[3])])
+            elif parts[0] == "f":
+                corner = []
+                for tok in parts[1:]:
+                    k = int(tok.split("/")[0])
+                    k = k - 1 if k > 0 else len(verts) + k
+                    if k < 0 or k >= len(verts):
+                        raise ValueError(f"{mesh_path}:{ln}: face corner '{tok}' names a vertex that does not exist")
+                    corner.append(k)
+                if len(corner) < 3:
+                    raise ValueError(f"{mesh_path}:{ln}: a face needs three corners")
+                for i in range(1, len(corner) - 1):
+                    tris.append([corner[0], corner[i], corner[i + 1]])
+    v = torch.tensor(verts, dtype=torch.float64).reshape(-1, 3).to(dtype)
+    t = torch.tensor(tris, dtype=torch.long).reshape(-1, 3)
+    return v, t
+
+
+# ---- checks -------------------------------------------------------------------------------------------------------------------
+def _check_mesh(vertices: Tensor, triangles: Tensor, need_cuda: bool = True) -> None:
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.shape[0] < 1:
+        raise ValueError(f"vertices must be [V, 3] with V >= 1, got {tuple(vertices.shape)}")
+    if vertices.dtype != torch.float32:
+        raise TypeError(f"vertices must be float32, got {vertices.dtype}")
+    if triangles.dim() != 2 or triangles.shape[1] != 3 or triangles.shape[0] < 1:
+        raise ValueError(f"triangles must be [F, 3] with F >= 1, got {tuple(triangles.shape)}")
+    if triangles.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"triangles must be int32 or int64, got {triangles.dtype}")
+    if need_cuda and not (vertices.is_cuda and triangles.is_cuda):
+        raise RuntimeError("the mesh distance runs only on the GPU through libsurfd_hip.so (no CPU fallback): move the mesh with .cuda()")
+
+
+def _check_points(name: str, p: Tensor, need_cuda: bool = True) -> None:
+    if p.dim() != 2 or p.shape[1] != 3:
+        raise ValueError(f"{name} must be [N, 3], got {tuple(p.shape)}")
+    if p.dtype != torch.float32:
+        raise TypeError(f"{name} must be float32, got {p.dtype}")
+    if need_cuda and not p.is_cuda:
+        raise RuntimeError(f"the mesh distance runs only on the GPU through libsurfd_hip.so (no CPU fallback): move {name} with .cuda()")
+
+
+# ---- Morton order -------------------------------------------------------------------------------------------------------------
+def _spread10(x: Tensor) -> Tensor:
+    x = x & 0x3FF
+    x = (x | (x << 16)) & 0x030000FF
+    x = (x | (x << 8)) & 0x0300F00F
+    x = (x | (x << 4)) & 0x030C30C3
+    x = (x | (x << 2)) & 0x09249249
+    return x
+
+
+def morton_order(p: Tensor) -> Tensor:
+    """the permutation that sorts the points [N, 3] by 30-bit Morton code over their own bounding box (stable)"""
+    lo = p.min(0).values
+    ext = (p.max(0).values - lo).max().clamp_min(1e-30)
+    g = ((p - lo) / ext * 1023.0).clamp(0, 1023).long()
+    code = _spread10(g[:, 0]) | (_spread10(g[:, 1]) << 1) | (_spread10(g[:, 2]) << 2)
+    return torch.sort(code, stable=True).indices
+
+
+# ---- closest point ------------------------------------------------------------------------------------------------------------
+class MeshDistance:
+    """The closest-point structure of one mesh, kept for repeated calls (the role of open3d's RaycastingScene).
+
+    The triangles are handed to the library in Morton order of their centroids and every call's queries in Morton order of
+    their positions, so that a wave's queries and a tile's triangles are each compact and the kernel's culling bites; results
+    come back in the caller's order with the caller's triangle indices.  Ties in distance go to the triangle that comes first
+    in the Morton order.  Host syncs: the constructor checks the vertices and the index range (three) and the library's create
+    reads its bad-index flag (one); every ``closest`` call checks that the queries are finite (one).  One stream at a time per
+    object: the library keeps its partial results in a workspace of the handle."""
+
+    def __init__(self, vertices: Tensor, triangles: Tensor):
+        _check_mesh(vertices, triangles)
+        if not bool(torch.isfinite(vertices).all()):
+            raise ValueError("vertices contain NaN or Inf")
+        self._handle = None
+        v = vertices.contiguous()
+        t = triangles.long()
+        if int(t.min()) < 0 or int(t.max()) >= v.shape[0]:
+            raise ValueError(f"triangles name vertices outside [0, {v.shape[0]})")
+        self.device = v.device
+        self._perm = morton_order(v[t].mean(1))
+        ts = t[self._perm].to(torch.int32).contiguous()
+        self.num_triangles = int(t.shape[0])
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            N.check(N.lib().surfd_mesh_create(N.ptr(v), v.shape[0], N.ptr(ts), ts.shape[0], N.stream(), C.byref(h)))
+        self._handle = h
+        assert N.lib().surfd_mesh_num_triangles(h) == self.num_triangles
+        self.last_skipped_tiles: Optional[int] = None
+        self.last_total_tiles: Optional[int] = None
+
+    def closest(self, queries: Tensor, brute_force: bool = False, count_skipped: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
+        """queries [Q, 3] -> (dist [Q] float32, points [Q, 3] float32, tri [Q] int64).  ``brute_force`` tests every pair (the
+        correctness baseline; the same bits).  With ``count_skipped`` the number of (wave, tile) visits that culling skipped is
+        left in ``last_skipped_tiles`` and their total in ``last_total_tiles`` (one host sync)."""
+        _check_points("queries", queries)
+        if queries.device != self.device:
+            raise RuntimeError(f"queries are on {queries.device}, the mesh is on {self.device}")
+        Q = queries.shape[0]
+        dist = torch.empty(Q, device=self.device, dtype=torch.float32)
+        pts = torch.empty(Q, 3, device=self.device, dtype=torch.float32)
+        tri = torch.empty(Q, device=self.device, dtype=torch.int32)
+        if Q == 0:
+            return dist, pts, tri.long()
+        if not bool(torch.isfinite(queries).all()):
+            raise ValueError("queries contain NaN or Inf")
+        order = morton_order(queries)
+        qs = queries[order].contiguous()
+        skipped = torch.zeros(1, device=self.device, dtype=torch.int64) if count_skipped else None
+        with torch.cuda.device(self.device):
+            N.check(N.lib().surfd_mesh_closest(self._handle, N.ptr(qs), Q, 1 if brute_force else 0, N.ptr(dist), N.ptr(pts), N.ptr(tri),
+                                               N.ptr(skipped), N.stream()))
+        if count_skipped:
+            self.last_skipped_tiles = int(skipped.item())
+            self.last_total_tiles = ((Q + 63) // 64) * ((self.num_triangles + 31) // 32)
+        inv = torch.empty_like(order)
+        inv[order] = torch.arange(Q, device=self.device)
+        return dist[inv], pts[inv], self._perm[tri.long()][inv]
+
+    def __del__(self):
+        try:
+            if self._handle is not None:
+                N.lib().surfd_mesh_destroy(self._handle)
+        except Exception:                                       # interpreter shutdown
+            pass
+
+
+def closest_points(vertices: Tensor, triangles: Tensor, queries: Tensor, brute_force: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
+    """(dist [Q], points [Q, 3], tri [Q]): for every query the exact closest point of the mesh, its distance and its triangle"""
+    _check_mesh(vertices, triangles, need_cuda=False)          # shapes and dtypes first, the CPU-tensor refusal last
+    _check_points("queries", queries, need_cuda=False)
+    _check_mesh(vertices, triangles)
+    _check_points("queries", queries)
+    return MeshDistance(vertices, triangles).closest(queries, brute_force=brute_force)
+
+
+# ---- samplers (torch plumbing) ------------------------------------------------------------------------------------------------
+def sample_points_uniformly(vertices: Tensor, triangles: Tensor, number_of_points: int, generator: Optional[torch.Generator] = None) -> Tensor:
+    """``number_of_points`` points uniform on the surface: a triangle drawn with probability proportional to its area, then
+    (1 - sqrt(r1)) a + sqrt(r1) (1 - r2) b + sqrt(r1) r2 c.  The random numbers come from ``generator`` (or the global RNG) of
+    the mesh's device."""
+    _check_mesh(vertices, triangles, need_cuda=False)
+    if number_of_points < 0:
+        raise ValueError("number_of_points must not be negative")
+    t = triangles.long()
+    a, b, c = vertices[t[:, 0]], vertices[t[:, 1]], vertices[t[:, 2]]
+    area = torch.linalg.cross((b - a).double(), (c - a).double()).norm(dim=1)
+    if not float(area.sum()) > 0:
+        raise ValueError("the mesh has no area to sample")
+    dev = vertices.device
+    pick = torch.multinomial(area / area.sum(), number_of_points, replacement=True, generator=generator) if number_of_points else \
+        torch.empty(0, dtype=torch.long, device=dev)
+    r = torch.rand(number_of_points, 2, device=dev, generator=generator).double()
+    s = r[:, 0].sqrt()[:, None]
+    r2 = r[:, 1][:, None]
+    # the combination in fp64, rounded once: the point is off its triangle by half an ulp per coordinate at most
+    return ((1 - s) * a[pick].double() + s * (1 - r2) * b[pick].double() + s * r2 * c[pick].double()).float()
+
+
+def sample_points_around_pcd(pcd: Tensor, stds: List[float], num_points_per_std: List[int], coords_range: Tuple[float, float],
+                             device: str = "cpu") -> Tensor:
+    """AutoEncoder/utils.py:167-220: the cloud's points (repeated, then a random remainder drawn without replacement) plus
+    Gaussian offsets for every sigma, then ``num_points_per_std[-1]`` uniform points; clipped to ``coords_range``.  The random
+    draws are the reference's, in its order: per sigma one multinomial on ``device`` (only where a remainder is needed) and one
+    randn on the host, at the end one rand on the host; so a seeded run gives the reference's bits (tests/golden g19)."""
+    n = pcd.shape[0]
+    lo, hi = coords_range
+    cloud = pcd.to(device)
+    blocks = []
+    for sigma, count in zip(stds, num_points_per_std[:-1]):
+        reps, rest = divmod(count, n)
+        rows = torch.arange(n, device=device).repeat_interleave(reps)           # every point `reps` times in a row
+        if rest:                                                                # then `rest` distinct points, drawn on `device`
+            rows = torch.cat((rows, torch.multinomial(torch.ones(n, device=device), rest, replacement=False)))
+        blocks.append(cloud[rows] + torch.randn(count, 3).to(device) * sigma)  # the noise is drawn on the host, then moved
+    blocks.append(torch.rand(num_points_per_std[-1], 3).to(device) * (hi - lo) + lo)
+    return torch.cat(blocks).clamp(lo, hi)
+
+
+# ---- UDF labels ---------------------------------------------------------------------------------------------------------------
+def _as_mesh_distance(vertices, triangles) -> MeshDistance:
+    return vertices if isinstance(vertices, MeshDistance) and triangles is None else MeshDistance(vertices, triangles)
+
+
+def compute_udf_and_gradients(vertices: Tensor, triangles: Tensor, queries: Tensor) -> Tuple[Tensor, Tensor]:
+    """AutoEncoder/utils.py:223-240: udf = |q - c| and gradients = F.normalize(q - c) for the closest point c of the mesh (a
+    query on the surface gets a zero gradient through F.normalize's eps).  ``vertices`` may be a MeshDistance (triangles None)."""
+    offset = queries - _as_mesh_distance(vertices, triangles).closest(queries)[1]
+    return offset.norm(dim=-1), F.normalize(offset, dim=-1)
+
+
+def compute_udf_from_mesh(vertices: Tensor, triangles: Tensor, num_surface_points: int = 100_000, num_queries_on_surface: int = 10_000,
+                          queries_stds: List[float] = [0.003, 0.01, 0.1], num_queries_per_std: List[int] = [5_000, 4_000, 500, 500],
+                          coords_range: Tuple[float, float] = (-1.0, 1.0), max_dist: float = 0.1, convert_to_bce_labels: bool = False,
+                          use_cuda: bool = True, input_queries: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """AutoEncoder/utils.py:268-314 -> (queries, values, gradients): a surface cloud, queries around it (or ``input_queries``),
+    their UDF clipped to [0, max_dist] and its gradients.  Everything stays on the mesh's device (the reference moves the queries
+    to the CPU for open3d); ``num_queries_on_surface`` and ``convert_to_bce_labels`` are unused, as in the reference."""
+    _check_mesh(vertices, triangles)
+    if not use_cuda:
+        raise RuntimeError("compute_udf_from_mesh runs only on the GPU through libsurfd_hip.so (no CPU fallback)")
+    queries = input_queries
+    if queries is None:
+        cloud = sample_points_uniformly(vertices, triangles, num_surface_points)
+        queries = sample_points_around_pcd(cloud, queries_stds, num_queries_per_std, coords_range, vertices.device)
+    udf, gradients = compute_udf_and_gradients(vertices, triangles, queries)
+    return queries, udf.clamp(0, max_dist), gradients
+
+
+# ---- measurement --------------------------------------------------------------------------------------------------------------
+def point_to_mesh_distance(points: Tensor, vertices: Tensor, triangles: Tensor) -> Tensor:
+    """[N] exact distances of the points to the mesh (``vertices`` may be a MeshDistance, triangles None)"""
+    return _as_mesh_distance(vertices, triangles).closest(points)[0]
+
+
+def mesh_distance(v1: Tensor, t1: Tensor, v2: Tensor, t2: Tensor, n: int = 100_000, generator: Optional[torch.Generator] = None) -> dict:
+    """The two directed mean distances between two meshes and their sum: ``n`` points sampled on the surface of one mesh,
+    exact distance to the other.  {"d12": mesh 1 -> mesh 2, "d21": mesh 2 -> mesh 1, "sum": d12 + d21}"""
+    _check_mesh(v1, t1)
+    _check_mesh(v2, t2)
+    p1 = sample_points_uniformly(v1, t1, n, generator=generator)
+    p2 = sample_points_uniformly(v2, t2, n, generator=generator)
+    d12 = float(point_to_mesh_distance(p1, v2, t2).double().mean())
+    d21 = float(point_to_mesh_distance(p2, v1, t1).double().mean())
+    return {"d12": d12, "d21": d21, "sum": d12 + d21}

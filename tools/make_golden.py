@@ -802,6 +802,23 @@ def g18_dgcnn(R):
     save("g18_dgcnn", **out)
 
 
+def g19_meshprep(R):
+    """sample_points_around_pcd of the reference itself (AutoEncoder/utils.py:167-220; pure torch + einops, imported under the
+    open3d mock) on the CPU under a fixed seed: a cloud larger than one sigma's count, one smaller (repeats plus a remainder)
+    and one that divides it exactly."""
+    from AutoEncoder import utils as rutils
+    out = {}
+    g = torch.Generator().manual_seed(1919)
+    for tag, n, counts in (("larger", 3000, [2000, 1500, 700, 300]), ("smaller", 700, [2500, 1800, 300, 400]), ("exact", 500, [1000, 500, 250, 100])):
+        pcd = (torch.rand(n, 3, generator=g) * 1.9 - 0.95).float()
+        torch.manual_seed(19)
+        coords = rutils.sample_points_around_pcd(pcd, [0.003, 0.01, 0.1], counts, (-1.0, 1.0), "cpu")
+        out[f"{tag}__pcd"] = pcd
+        out[f"{tag}__counts"] = np.array(counts)
+        out[f"{tag}__coords"] = coords
+    save("g19_meshprep", **out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
@@ -817,7 +834,7 @@ def main():
             "g13": lambda: g13_marching_cubes(R, a.mc512), "g13luts": lambda: g13_lut_hashes(R), "g13ext": lambda: g13_extension_cases(R),
             "g15": lambda: g15_image_preprocess(R), "g16": lambda: g16_clip_towers(R), "g16bpe": lambda: g16_bpe_merges(R),
             "g17": lambda: g17_spatial_transformer(R), "g14": lambda: g14_cross_attention(R),
-            "g18": lambda: g18_dgcnn(R)}
+            "g18": lambda: g18_dgcnn(R), "g19": lambda: g19_meshprep(R)}
     only = [s for s in a.only.split(",") if s]
     for name, fn in jobs.items():
         if only and name not in only:
