@@ -1,0 +1,120 @@
+#!/usr/bin/env python3
+"""Scores generated shapes against a held-out set, or reconstructions against their originals, on the MI355X path
+(surfd_amd/cloudmetrics.py).  The reference ships no evaluation code; the protocol is that of Achlioptas et al. 2018 as used in
+PointFlow: clouds of ``--num_points`` points, Chamfer distance = sum of the two directed means of squared nearest-neighbour
+distances.
+
+    python examples/evaluate.py --generated outputs/meshes --reference data/heldout --output metrics.json
+    python examples/evaluate.py --generated outputs/rec --reference data/items --paired --output pairs.json
+
+Each directory holds ``.obj`` meshes (sampled uniformly on their surface) and / or ``.npz`` files with a ``pcd`` or ``points``
+array as examples/preprocess_udfs.py writes them (subsampled at random without replacement; a smaller cloud is an error).  All
+random numbers come from one CPU generator seeded with ``--seed``, used file by file in sorted order, the generated directory
+first.  Default: the set metrics MMD-CD, COV-CD and 1-NNA-CD in one JSON with the counts and the options used.  ``--paired``:
+files are matched by stem and every pair gets ``cd``, ``fscore``, ``precision``, ``recall`` (generated = prediction), plus their
+means.  The earth mover's distance is not computed.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from surfd_amd import cloudmetrics, meshprep  # noqa: E402
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--generated", required=True, help="directory of .obj / .npz files")
+    ap.add_argument("--reference", required=True, help="directory of .obj / .npz files")
+    ap.add_argument("--paired", action="store_true", help="match files by stem and score every pair")
+    ap.add_argument("--num_points", type=int, default=2048)
+    ap.add_argument("--normalize", choices=("none", "unit_sphere", "bbox"), default="bbox")
+    ap.add_argument("--f_threshold", type=float, default=0.01, help="distance threshold of the F-score (--paired)")
+    ap.add_argument("--chunk", type=int, default=None, help="clouds per kernel launch (results do not depend on it)")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--output", default="metrics.json")
+    return ap.parse_args(argv)
+
+
+def list_items(directory):
+    """{stem: path} of the .obj / .npz files of a directory, sorted by stem"""
+    if not os.path.isdir(directory):
+        raise SystemExit(f"{directory} is not a directory")
+    items = {}
+    for f in sorted(os.listdir(directory)):
+        stem, ext = os.path.splitext(f)
+        if ext.lower() in (".obj", ".npz"):
+            if stem in items:
+                raise SystemExit(f"{directory}: item id '{stem}' appears twice")
+            items[stem] = os.path.join(directory, f)
+    if not items:
+        raise SystemExit(f"{directory}: no .obj or .npz files")
+    return dict(sorted(items.items()))
+
+
+def load_cloud(path, num_points, generator):
+    """one file -> [num_points, 3] float32 on the CPU"""
+    if path.lower().endswith(".obj"):
+        v, t = meshprep.read_mesh(path)
+        if len(t) == 0:
+            raise SystemExit(f"{path}: no faces")
+        return meshprep.sample_points_uniformly(v, t, num_points, generator=generator)
+    z = np.load(path)
+    key = next((k for k in ("pcd", "points") if k in z.files), None)
+    if key is None:
+        raise SystemExit(f"{path}: neither 'pcd' nor 'points' inside")
+    p = torch.from_numpy(np.asarray(z[key], dtype=np.float32)).reshape(-1, 3)
+    if len(p) < num_points:
+        raise SystemExit(f"{path}: {len(p)} points, fewer than --num_points {num_points}")
+    return p[torch.randperm(len(p), generator=generator)[:num_points]].contiguous()
+
+
+def load_set(items, a, generator):
+    x = torch.stack([load_cloud(p, a.num_points, generator) for p in items.values()])
+    if not bool(torch.isfinite(x).all()):
+        raise SystemExit("a cloud contains NaN or Inf")
+    return cloudmetrics.normalize_clouds(x, a.normalize).contiguous()
+
+
+def run(a):
+    if not torch.cuda.is_available():
+        raise SystemExit("evaluate.py runs on the GPU (no CPU fallback)")
+    gen_items, ref_items = list_items(a.generated), list_items(a.reference)
+    if a.paired:
+        if list(gen_items) != list(ref_items):
+            raise SystemExit(f"--paired needs the same item ids on both sides; unmatched: {sorted(set(gen_items) ^ set(ref_items))}")
+    g = torch.Generator().manual_seed(a.seed)
+    gen = load_set(gen_items, a, g).cuda()
+    ref = load_set(ref_items, a, g).cuda()
+    out = {"options": {"num_points": a.num_points, "normalize": a.normalize, "seed": a.seed, "paired": bool(a.paired)},
+           "num_generated": len(gen_items), "num_reference": len(ref_items)}
+    if a.paired:
+        out["options"]["f_threshold"] = a.f_threshold
+        r = {k: v.cpu().tolist() for k, v in cloudmetrics.chamfer_distance(gen, ref, f_threshold=a.f_threshold).items()}
+        keys = ("cd", "fscore", "precision", "recall")
+        out["items"] = {name: {k: r[k][i] for k in keys} for i, name in enumerate(gen_items)}
+        out["mean"] = {k: float(np.mean(r[k], dtype=np.float64)) for k in keys}
+    else:
+        m = cloudmetrics.compute_all_metrics(gen, ref, chunk=a.chunk)
+        out["metrics"] = {"mmd_cd": m["mmd_cd"], "cov_cd": m["cov_cd"], "1nna_cd": m["1nna_cd"]}
+        out["detail"] = {k: m[k] for k in ("mmd_smp_cd", "1nna_cd_gen", "1nna_cd_ref")}
+    os.makedirs(os.path.dirname(os.path.abspath(a.output)), exist_ok=True)
+    with open(a.output, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(out.get("metrics", out.get("mean"))))
+    return out
+
+
+def main(argv=None):
+    return run(parse(argv))
+
+
+if __name__ == "__main__":
+    main()

@@ -431,6 +431,28 @@ int surfd_mesh_num_triangles(const surfd_mesh *m);
 int surfd_mesh_closest(const surfd_mesh *m, const float *queries, int Q, int flags, float *dist, float *closest, int32_t *tri,
                        int64_t *skipped_tiles, surfd_stream s);
 
+/* ------------------------------------------------------------------------------------ */
+/* Point-cloud metrics: nearest neighbours between clouds and the matrix of directed      */
+/* Chamfer means between two sets of clouds.  No reference counterpart (the reference     */
+/* ships no evaluation code): stands for pytorch3d's knn_points(p1, p2, K=1) /            */
+/* chamfer_distance and for the distance matrices of the MMD / COV / 1-NNA protocol of    */
+/* Achlioptas et al. 2018 as used in PointFlow.  Plain fp32; bitwise deterministic.       */
+/* ------------------------------------------------------------------------------------ */
+/* no reference counterpart; pytorch3d's knn_points(a, b, K=1):
+ * a[B,Na,3], b[B,Nb,3] -> d2[B,Na] (fp32, nullable), idx[B,Na] (int32 into b's cloud, nullable): for every point of a_i its
+ * nearest point of b_i.  d2 = (dx dx + dy dy) + dz dz with diff = a - b, every operation rounded once; the winner is the minimum
+ * under (d2, index): ties go to the lower index.  Na, Nb >= 1.  B = 0 is a no-op. */
+int surfd_cloud_nn(const float *a, const float *b, int B, int Na, int Nb, float *d2, int32_t *idx, surfd_stream s);
+/* no reference counterpart; one direction of pytorch3d's chamfer_distance for every pair of two sets (the matrices behind MMD /
+ * COV / 1-NNA):
+ * a[M,Na,3], b[R,Nb,3] -> mean[M,R] (fp32): mean[i,j] = (1/Na) * sum over p in a_i of min over q in b_j of |p - q|^2;
+ * below[M,R] (int32, nullable): how many points of a_i have that minimum < tau2 (strict; fp32 compare on the fp32 d2).
+ * The sum over a cloud's points is taken in fp64, in a fixed order that depends on Na only, and rounded to fp32 once after
+ * the division: entry (i,j) has the same bits whatever M and R it is computed in, and under any permutation of b_j's points.
+ * The other direction is a second call with the roles swapped. */
+int surfd_cloud_nn_matrix(const float *a, int M, int Na, const float *b, int R, int Nb, float tau2,
+                          float *mean, int32_t *below, surfd_stream s);
+
 #ifdef __cplusplus
 }
 #endif

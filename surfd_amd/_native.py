@@ -133,6 +133,8 @@ _SIGS = {
     "surfd_mesh_destroy": (None, [_P]),
     "surfd_mesh_num_triangles": (C.c_int, [_P]),
     "surfd_mesh_closest": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "surfd_cloud_nn": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "surfd_cloud_nn_matrix": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_float, _P, _P, _P]),
     "surfd_mc_lut_count": (C.c_int, []),
     "surfd_mc_lut": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.POINTER(C.c_byte)), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }

@@ -23,6 +23,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-pass-faile
 FLAGS += os.environ.get("SURFD_EXTRA_HIPCC_FLAGS", "").split()      # debugging builds only (e.g. -DSURFD_DEC_STAMPS)
 SOURCES.insert(SOURCES.index("mcubes.cpp"), "dgcnn.hip")             # the point-cloud encoder (surfd_amd/dgcnn.py)
 SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshdist.hip")          # closest point of a mesh (surfd_amd/meshprep.py)
+SOURCES.insert(SOURCES.index("mcubes.cpp"), "cloudnn.hip")           # nearest neighbours / Chamfer matrices of clouds (surfd_amd/cloudmetrics.py)
+# cloudnn.hip: without SLP vectorisation the pair test stays 8 plain fp32 instructions + half a v_min3; with it the compiler packs
+# half of them into v_pk_*_f32 (issued at half rate, so nothing is gained) and pads the loop with s_nop
+FILE_FLAGS = {"cloudnn.hip": ["-fno-slp-vectorize"]}
 
 
 def _hipcc() -> str:
@@ -57,7 +61,7 @@ def build_library(force: bool = False, verbose: bool = True) -> str:
         if src.endswith(".cpp"):      # host-only translation unit: no offload
             cmd = [hipcc, "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-x", "c++", "-c", src, "-o", obj]
         else:
-            cmd = [hipcc] + FLAGS + ["-c", src, "-o", obj]
+            cmd = [hipcc] + FLAGS + FILE_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"hipcc failed on {src}:\n{r.stderr[-4000:]}")
