@@ -50,6 +50,8 @@ def parse(argv=None):
     ap.add_argument("--size_latent", type=int, default=32, help="latent size of the --synthetic checkpoint")
     ap.add_argument("--metrics", action="store_true",
                     help="for inputs that carry 'vertices' / 'triangles' (examples/preprocess_udfs.py): write metrics.json")
+    ap.add_argument("--preview", type=int, default=0, metavar="N",
+                    help="also write N orbit views (shaded / depth / normal PNGs, surfd_amd.render) of every mesh; 0 = none")
     return ap.parse_args(argv)
 
 
@@ -193,6 +195,11 @@ def run(a):
         meshproc.write_obj(path, verts, faces)
         written.append(path)
         print(f"{path}: {len(verts)} vertices, {len(faces)} faces")
+        if a.preview > 0:
+            from surfd_amd import render
+            views = render.render_mesh(torch.as_tensor(np.ascontiguousarray(verts, dtype=np.float32)).cuda(),
+                                       torch.as_tensor(np.ascontiguousarray(faces, dtype=np.int64)).reshape(-1, 3).cuda(), n_views=a.preview, size=512)
+            written += render.save_views(a.output_dir, os.path.splitext(os.path.basename(path))[0], views)
         if a.metrics:
             m = item_metrics(files[k], verts, faces, field, a.seed)
             if m is not None:

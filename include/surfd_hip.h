@@ -453,6 +453,47 @@ int surfd_cloud_nn(const float *a, const float *b, int B, int Na, int Nb, float 
 int surfd_cloud_nn_matrix(const float *a, int M, int Na, const float *b, int R, int Nb, float tau2,
                           float *mean, int32_t *below, surfd_stream s);
 
+/* ------------------------------------------------------------------------------------ */
+/* Mesh renderer: a two-sided z-buffer rasteriser (depth, barycentrics, normals, masks,   */
+/* headlight shading) and contour images, for condition images / sketches, view-based     */
+/* evaluation and previews.  No reference counterpart (the reference looks at meshes in   */
+/* open3d / pymeshlab windows).  fp32 + integer; bitwise deterministic.                   */
+/* ------------------------------------------------------------------------------------ */
+typedef struct surfd_raster surfd_raster;
+#define SURFD_RASTER_FORCE_SMALL 1   /* flags bit 0: every triangle is rasterised by its set-up lane */
+#define SURFD_RASTER_FORCE_LARGE 2   /* flags bit 1: every triangle goes through the list, one wave each (excludes bit 0) */
+#define SURFD_RASTER_CAMERA_FLOATS 18
+/* no reference counterpart; an offscreen render target of open3d / pymeshlab:
+ * the handle owns the 64-bit key buffer [max_views, H, W], the device copy of a call's cameras and a workspace (projected
+ * vertices, list of large triangles) that grows on demand.  1 <= H, W <= 2048; 1 <= max_views <= 64.  One stream and one host
+ * thread at a time per handle. */
+int surfd_raster_create(int H, int W, int max_views, surfd_raster **out);
+void surfd_raster_destroy(surfd_raster *r);
+/* no reference counterpart; rendering a triangle mesh to per-pixel buffers:
+ * vertices[V,3] fp32 and faces[F,3] int32 on the device; vertex_normals[V,3] fp32 (world space) on the device or NULL (geometric
+ * face normals); cameras[n_views,18] fp32 on the HOST (copied before the call returns): the row-major 3x4 world->camera
+ * matrix (x right, y down, z forward), then mode (0 perspective, 1 orthographic), fx, fy, cx, cy in pixels, near (>= 0; > 0 in
+ * perspective mode).  light[3] on the host (camera space; NULL = the headlight (0, 0, -1)); ambient in [0, 1].
+ * Outputs on the device, each nullable, [n_views, H, W] row-major (row j = image line, pixel centres at integer + 0.5):
+ * face int32 (-1 background), depth fp32 (metric camera z, +inf background), bary fp32 x3 (perspective-correct, in the
+ * caller's vertex order), normal fp32 x3 (camera space, unit or zero, turned to the viewer: n_z <= 0), mask uint8,
+ * shaded fp32 = ambient + (1 - ambient) |n . light| (0 background); dropped_per_view int32 [n_views]: triangles left out
+ * because a vertex has camera z <= near, projects outside +-2^22 / 256 pixels or is an index outside [0, V) (there is no
+ * near-plane clipping).  Coverage is exact (integer edge functions on a 1/256-pixel grid, top-left rule, both windings);
+ * a pixel's winner is the minimum of (compared depth, face index), so the buffers do not depend on face order beyond exact
+ * depth ties, on the batch of views, on flags or on launch geometry.  V, F >= 0 (F = 0 gives the empty image);
+ * 1 <= n_views <= max_views; n_views * V and n_views * F < 2^31. */
+int surfd_raster_render(surfd_raster *r, const float *vertices, int V, const int32_t *faces, int F, const float *vertex_normals,
+                        const float *cameras, int n_views, int flags, const float *light, float ambient,
+                        int32_t *face, float *depth, float *bary, float *normal, unsigned char *mask, float *shaded,
+                        int32_t *dropped_per_view, surfd_stream s);
+/* no reference counterpart; a line drawing of a rendered view:
+ * mask / depth / normal [n_views, H, W(, 3)] as surfd_raster_render wrote them -> ink[n_views, H, W] uint8: 1 where the pixel's
+ * mask differs from a 4-neighbour's, or both are covered and their depths differ by more than depth_jump (>= 0) or their
+ * normals' dot product is below cos_crease (in [-1, 1]).  Neighbours outside the image are background. */
+int surfd_raster_contours(const surfd_raster *r, const unsigned char *mask, const float *depth, const float *normal, int n_views,
+                          float depth_jump, float cos_crease, unsigned char *ink, surfd_stream s);
+
 #ifdef __cplusplus
 }
 #endif
