@@ -13,6 +13,13 @@ random numbers come from one CPU generator seeded with ``--seed``, used file by 
 first.  Default: the set metrics MMD-CD, COV-CD and 1-NNA-CD in one JSON with the counts and the options used.  ``--paired``:
 files are matched by stem and every pair gets ``cd``, ``fscore``, ``precision``, ``recall`` (generated = prediction), plus their
 means.  The earth mover's distance is not computed.
+
+``--paired --voxel_iou R`` adds the volumetric IoU of every pair on an R^3 grid over ``--voxel_bounds`` (surfd_amd/voxelize.py):
+``--voxel_mode surface`` (voxels the triangles touch), ``solid`` (parity fill | surface; each item's ``odd_columns`` is recorded,
+0 for a closed mesh) or ``points`` (voxels that hold a vertex of the mesh or a point of the .npz cloud, all of them, no
+subsampling).  Both items of a pair are voxelised in ONE frame: with ``--normalize bbox`` / ``unit_sphere`` the transform of the
+REFERENCE item (from its vertices or points) is applied to both.  ``.npz`` clouds are scored in ``points`` mode only; elsewhere
+the pair is listed under ``skipped``.
 """
 from __future__ import annotations
 
@@ -39,6 +46,9 @@ def parse(argv=None):
     ap.add_argument("--f_threshold", type=float, default=0.01, help="distance threshold of the F-score (--paired)")
     ap.add_argument("--chunk", type=int, default=None, help="clouds per kernel launch (results do not depend on it)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--voxel_iou", type=int, default=0, metavar="R", help="--paired: also score volumetric IoU on an R^3 grid (0 = off)")
+    ap.add_argument("--voxel_bounds", type=float, nargs=2, default=(-1.0, 1.0), metavar=("LO", "HI"))
+    ap.add_argument("--voxel_mode", choices=("surface", "solid", "points"), default="surface")
     ap.add_argument("--output", default="metrics.json")
     return ap.parse_args(argv)
 
@@ -83,7 +93,62 @@ def load_set(items, a, generator):
     return cloudmetrics.normalize_clouds(x, a.normalize).contiguous()
 
 
+def load_geometry(path):
+    """one file -> (points or vertices [N, 3] float32, faces [F, 3] or None) on the CPU, nothing sampled"""
+    if path.lower().endswith(".obj"):
+        v, t = meshprep.read_mesh(path)
+        return torch.as_tensor(np.asarray(v, dtype=np.float32)).reshape(-1, 3), torch.as_tensor(np.asarray(t).astype(np.int32)).reshape(-1, 3)
+    z = np.load(path)
+    key = next((k for k in ("pcd", "points") if k in z.files), None)
+    if key is None:
+        raise SystemExit(f"{path}: neither 'pcd' nor 'points' inside")
+    return torch.from_numpy(np.asarray(z[key], dtype=np.float32)).reshape(-1, 3), None
+
+
+def reference_frame(x, mode):
+    """(centre [3], radius) of cloudmetrics.normalize_clouds(x, mode), to be applied to both items of a pair"""
+    if mode == "none":
+        return torch.zeros(3), 1.0
+    if mode == "unit_sphere":
+        c = x.mean(0)
+        r = float((x - c).norm(dim=-1).amax())
+    else:
+        lo, hi = x.amin(0), x.amax(0)
+        c = (lo + hi) / 2
+        r = float((hi - lo).amax()) / 2
+    return c, (r if r > 0 else 1.0)
+
+
+def voxel_scores(gen_items, ref_items, a):
+    """-> (per-item dict, skipped ids) of --voxel_iou"""
+    from surfd_amd import voxelize
+    R, bounds = a.voxel_iou, tuple(a.voxel_bounds)
+    items, skipped = {}, []
+    for name in gen_items:
+        (gv, gf), (rv, rf) = load_geometry(gen_items[name]), load_geometry(ref_items[name])
+        if a.voxel_mode != "points" and (gf is None or rf is None or not len(gf) or not len(rf)):
+            skipped.append(name)
+            continue
+        c, r = reference_frame(rv, a.normalize)
+        entry, grids = {}, []
+        for v, f, side in ((gv, gf, "generated"), (rv, rf, "reference")):
+            v = ((v - c) / r).contiguous().cuda()
+            if a.voxel_mode == "points":
+                grids.append(voxelize.voxelize_points(v, R, bounds))
+            elif a.voxel_mode == "surface":
+                grids.append(voxelize.voxelize_surface(v, f.cuda(), R, bounds))
+            else:
+                grid, odd = voxelize.voxelize_solid(v, f.cuda(), R, bounds)
+                grids.append(grid)
+                entry[f"odd_columns_{side}"] = odd
+        entry["voxel_iou"] = float(voxelize.voxel_iou(grids[0], grids[1]))
+        items[name] = entry
+    return items, skipped
+
+
 def run(a):
+    if a.voxel_iou and not a.paired:
+        raise SystemExit("--voxel_iou scores pairs: it needs --paired")
     if not torch.cuda.is_available():
         raise SystemExit("evaluate.py runs on the GPU (no CPU fallback)")
     gen_items, ref_items = list_items(a.generated), list_items(a.reference)
@@ -101,6 +166,14 @@ def run(a):
         keys = ("cd", "fscore", "precision", "recall")
         out["items"] = {name: {k: r[k][i] for k in keys} for i, name in enumerate(gen_items)}
         out["mean"] = {k: float(np.mean(r[k], dtype=np.float64)) for k in keys}
+        if a.voxel_iou:
+            out["options"].update(voxel_iou=a.voxel_iou, voxel_bounds=list(a.voxel_bounds), voxel_mode=a.voxel_mode)
+            scores, skipped = voxel_scores(gen_items, ref_items, a)
+            for name, s in scores.items():
+                out["items"][name].update(s)
+            if scores:
+                out["mean"]["voxel_iou"] = float(np.mean([s["voxel_iou"] for s in scores.values()], dtype=np.float64))
+            out["skipped"] = skipped
     else:
         m = cloudmetrics.compute_all_metrics(gen, ref, chunk=a.chunk)
         out["metrics"] = {"mmd_cd": m["mmd_cd"], "cov_cd": m["cov_cd"], "1nna_cd": m["1nna_cd"]}

@@ -494,6 +494,60 @@ int surfd_raster_render(surfd_raster *r, const float *vertices, int V, const int
 int surfd_raster_contours(const surfd_raster *r, const unsigned char *mask, const float *depth, const float *normal, int n_views,
                           float depth_jump, float cos_crease, unsigned char *ink, surfd_stream s);
 
+/* ------------------------------------------------------------------------------------ */
+/* Voxelisation and volumetric IoU: occupancy grids of meshes (surface, solid) and clouds, */
+/* and intersection over union between grids.  No reference counterpart (the reference    */
+/* ships no evaluation code): stands for the occupancy grids and the IoU of the           */
+/* single-view reconstruction protocol (Choy et al. 2016, 3D-R2N2; Mescheder et al. 2019, */
+/* Occupancy Networks).  One fp32 step (the snap), then int64: exact and bitwise          */
+/* deterministic for any face order, winding, batch, path and launch geometry.            */
+/* ------------------------------------------------------------------------------------ */
+/* the two flags are test switches (they prove the paths bit-identical); FORCE_SMALL makes one lane walk a triangle's whole box,
+ * however large: not for large triangles on fine grids */
+#define SURFD_VOXEL_FORCE_SMALL 1   /* flags bit 0: every triangle is voxelised by its set-up lane */
+#define SURFD_VOXEL_FORCE_LARGE 2   /* flags bit 1: every triangle goes through the list, one wave each (excludes bit 0) */
+#define SURFD_VOXEL_MAX_RESOLUTION 512
+/* The grid of every entry below: the cube [lo, hi]^3 cut into R^3 voxels, 1 <= R <= 512, hi > lo; voxel (i, j, k) is the CLOSED
+ * box [i, i+1] x [j, j+1] x [k, k+1] in voxel units, axes (x, y, z) = (i, j, k).  bits[R, R, W] uint32 on the device,
+ * W = ceil(R / 32): bit k & 31 of word k >> 5 of column (i, j) is voxel k; padding bits are never set.  bits is ACCUMULATED
+ * into (atomicOr): the caller zeroes it, several meshes or clouds may be OR-ed into one grid.  A coordinate x is snapped as
+ * q = rint((x - lo) * s), s = fp32(256 R / (hi - lo)) (units of 1/256 voxel, ties to even); it is invalid when it is NaN or
+ * |q| > 2^19.  R outside 1 .. 512, hi <= lo, both force flags, 3 V or 3 F >= 2^31 and null pointers are SURFD_ERR_ARG, found
+ * before any HIP call.
+ * The workspace is passed by the caller (the library keeps no handle and no state for these entries): at least
+ * surfd_voxel_workspace_bytes(F, R) bytes on the device, contents irrelevant before and after a call; it holds the counters,
+ * the list of large triangles and, for the solid fill, the XOR buffer and the crossing parities.  One workspace serves one
+ * stream at a time. */
+/* no reference counterpart; the scratch size of a voxelisation call:
+ * bytes = 4 (16 + F + R R W + R R); 0 for arguments out of range */
+int64_t surfd_voxel_workspace_bytes(int F, int R);
+/* no reference counterpart; the conservative surface voxelisation of a triangle mesh (binvox -e, trimesh's voxelize):
+ * vertices[V,3] fp32, faces[F,3] int32 on the device.  Voxel (i, j, k) is set iff the snapped triangle intersects the closed
+ * box: the 13-axis separating-axis test (Akenine-Moller) on integers, an axis separates on strict inequality only, so touching
+ * counts.  dropped (int32 on the device, nullable): triangles left out because a vertex is invalid or an index lies outside
+ * [0, V) (never a fault); degenerate (nullable): triangles whose snapped doubled area vector is zero (skipped).  F = 0 is legal. */
+int surfd_voxel_surface(const float *vertices, int V, const int32_t *faces, int F, float lo, float hi, int R, int flags, void *workspace,
+                        uint32_t *bits, int32_t *dropped, int32_t *degenerate, surfd_stream s);
+/* no reference counterpart; the parity (ray-stabbing) fill of a closed mesh along +z (binvox's default, trimesh's fill):
+ * voxel (i, j, k) is filled iff an odd number of triangles cross the column through (256 i + 128, 256 j + 128) strictly below
+ * the voxel centre 256 k + 128.  A column's crossings are decided with integer edge functions and the top-left rule, so one
+ * on a shared edge or through a vertex counts once; triangles of zero projected area contribute nothing.  bits |= fill, and
+ * also |= the surface voxelisation above when include_surface != 0.  odd_columns (int32 on the device, nullable): the number
+ * of columns whose crossing total is odd — 0 exactly when the snapped mesh is closed over the grid's columns.  dropped as above. */
+int surfd_voxel_solid(const float *vertices, int V, const int32_t *faces, int F, float lo, float hi, int R, int flags, void *workspace,
+                      int include_surface, uint32_t *bits, int32_t *odd_columns, int32_t *dropped, surfd_stream s);
+/* no reference counterpart; the occupancy grid of a point cloud:
+ * points[P,3] fp32 on the device; a point sets voxel floor(q / 256) per axis, a point exactly on the upper grid face belongs to
+ * the last voxel.  outside (int32 on the device, nullable): points outside the grid or invalid (skipped).  No workspace. */
+int surfd_voxel_points(const float *points, int P, float lo, float hi, int R, uint32_t *bits, int32_t *outside, surfd_stream s);
+/* no reference counterpart; volumetric intersection over union of occupancy grids:
+ * a[M, R, R, W], b[N, R, R, W] packed grids on the device.  paired == 0: inter / uni (int32) and iou (fp32) are [M, N], entry
+ * (m, n) from a_m and b_n; paired != 0 (M = N): [M], entry m from a_m and b_m.  inter = popcount(a & b), uni = popcount(a | b),
+ * iou = fp32(inter) / fp32(uni) rounded once, 1.0 when uni = 0.  Integer sums: an entry has the same bits whatever M and N it
+ * is computed in.  All three outputs are required (the counts are the accumulators); the number of pairs must stay below 2^31. */
+int surfd_voxel_iou(const uint32_t *a, int M, const uint32_t *b, int N, int R, int paired, int32_t *inter, int32_t *uni, float *iou,
+                    surfd_stream s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,6 +140,11 @@ _SIGS = {
     "surfd_raster_render": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, c_f32p, C.c_int, C.c_int, c_f32p, C.c_float,
                                       _P, _P, _P, _P, _P, _P, _P, _P]),
     "surfd_raster_contours": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_float, C.c_float, _P, _P]),
+    "surfd_voxel_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "surfd_voxel_surface": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "surfd_voxel_solid": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
+    "surfd_voxel_points": (C.c_int, [_P, C.c_int, C.c_float, C.c_float, C.c_int, _P, _P, _P]),
+    "surfd_voxel_iou": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "surfd_mc_lut_count": (C.c_int, []),
     "surfd_mc_lut": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.POINTER(C.c_byte)), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
