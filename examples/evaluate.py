@@ -14,6 +14,12 @@ first.  Default: the set metrics MMD-CD, COV-CD and 1-NNA-CD in one JSON with th
 files are matched by stem and every pair gets ``cd``, ``fscore``, ``precision``, ``recall`` (generated = prediction), plus their
 means.  The earth mover's distance is not computed.
 
+``--sampling even`` replaces the random draws by clouds that cover their shape evenly: an ``.obj`` item is sampled with
+``meshprep.sample_points_evenly`` (``--init_factor`` x ``--num_points`` uniform candidates, then farthest point sampling), an
+``.npz`` cloud with more than ``--num_points`` points is reduced by farthest point sampling from its first point instead of a
+random subset (surfd_amd/cloudsample.py).  The output JSON then records ``sampling`` and ``init_factor`` among its options;
+the default, ``uniform``, is the behaviour described above and leaves the JSON as it was.
+
 ``--paired --voxel_iou R`` adds the volumetric IoU of every pair on an R^3 grid over ``--voxel_bounds`` (surfd_amd/voxelize.py):
 ``--voxel_mode surface`` (voxels the triangles touch), ``solid`` (parity fill | surface; each item's ``odd_columns`` is recorded,
 0 for a closed mesh) or ``points`` (voxels that hold a vertex of the mesh or a point of the .npz cloud, all of them, no
@@ -33,7 +39,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from surfd_amd import cloudmetrics, meshprep  # noqa: E402
+from surfd_amd import cloudmetrics, cloudsample, meshprep  # noqa: E402
 
 
 def parse(argv=None):
@@ -46,6 +52,9 @@ def parse(argv=None):
     ap.add_argument("--f_threshold", type=float, default=0.01, help="distance threshold of the F-score (--paired)")
     ap.add_argument("--chunk", type=int, default=None, help="clouds per kernel launch (results do not depend on it)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--sampling", choices=("uniform", "even"), default="uniform",
+                    help="uniform: random surface samples / random subsets; even: farthest point sampling (see above)")
+    ap.add_argument("--init_factor", type=int, default=5, help="--sampling even: uniform candidates per kept point of an .obj item")
     ap.add_argument("--voxel_iou", type=int, default=0, metavar="R", help="--paired: also score volumetric IoU on an R^3 grid (0 = off)")
     ap.add_argument("--voxel_bounds", type=float, nargs=2, default=(-1.0, 1.0), metavar=("LO", "HI"))
     ap.add_argument("--voxel_mode", choices=("surface", "solid", "points"), default="surface")
@@ -69,12 +78,14 @@ def list_items(directory):
     return dict(sorted(items.items()))
 
 
-def load_cloud(path, num_points, generator):
+def load_cloud(path, num_points, generator, sampling="uniform", init_factor=5):
     """one file -> [num_points, 3] float32 on the CPU"""
     if path.lower().endswith(".obj"):
         v, t = meshprep.read_mesh(path)
         if len(t) == 0:
             raise SystemExit(f"{path}: no faces")
+        if sampling == "even":
+            return meshprep.sample_points_evenly(v, t, num_points, init_factor=init_factor, generator=generator)
         return meshprep.sample_points_uniformly(v, t, num_points, generator=generator)
     z = np.load(path)
     key = next((k for k in ("pcd", "points") if k in z.files), None)
@@ -83,11 +94,15 @@ def load_cloud(path, num_points, generator):
     p = torch.from_numpy(np.asarray(z[key], dtype=np.float32)).reshape(-1, 3)
     if len(p) < num_points:
         raise SystemExit(f"{path}: {len(p)} points, fewer than --num_points {num_points}")
+    if sampling == "even" and len(p) > num_points:
+        if not bool(torch.isfinite(p).all()):
+            raise SystemExit(f"{path}: the cloud contains NaN or Inf")
+        return cloudsample.sample_farthest_points(p[None].contiguous().cuda(), num_points)[0][0].cpu()
     return p[torch.randperm(len(p), generator=generator)[:num_points]].contiguous()
 
 
 def load_set(items, a, generator):
-    x = torch.stack([load_cloud(p, a.num_points, generator) for p in items.values()])
+    x = torch.stack([load_cloud(p, a.num_points, generator, a.sampling, a.init_factor) for p in items.values()])
     if not bool(torch.isfinite(x).all()):
         raise SystemExit("a cloud contains NaN or Inf")
     return cloudmetrics.normalize_clouds(x, a.normalize).contiguous()
@@ -151,6 +166,8 @@ def run(a):
         raise SystemExit("--voxel_iou scores pairs: it needs --paired")
     if not torch.cuda.is_available():
         raise SystemExit("evaluate.py runs on the GPU (no CPU fallback)")
+    if a.init_factor < 1:
+        raise SystemExit("--init_factor must be at least 1")
     gen_items, ref_items = list_items(a.generated), list_items(a.reference)
     if a.paired:
         if list(gen_items) != list(ref_items):
@@ -160,6 +177,8 @@ def run(a):
     ref = load_set(ref_items, a, g).cuda()
     out = {"options": {"num_points": a.num_points, "normalize": a.normalize, "seed": a.seed, "paired": bool(a.paired)},
            "num_generated": len(gen_items), "num_reference": len(ref_items)}
+    if a.sampling != "uniform":
+        out["options"].update(sampling=a.sampling, init_factor=a.init_factor)
     if a.paired:
         out["options"]["f_threshold"] = a.f_threshold
         r = {k: v.cpu().tolist() for k, v in cloudmetrics.chamfer_distance(gen, ref, f_threshold=a.f_threshold).items()}

@@ -454,6 +454,32 @@ int surfd_cloud_nn_matrix(const float *a, int M, int Na, const float *b, int R, 
                           float *mean, int32_t *below, surfd_stream s);
 
 /* ------------------------------------------------------------------------------------ */
+/* Farthest point sampling: K points of a cloud, each the one farthest from every pick    */
+/* before it, and the squared covering radius after every pick.  No reference counterpart */
+/* (the reference samples at random): stands for pytorch3d's sample_farthest_points.      */
+/* Plain fp32; the index sequence is bitwise a function of the input.                     */
+/* ------------------------------------------------------------------------------------ */
+/* no reference counterpart; the scratch size of a farthest-point-sampling call:
+ * bytes = 4 B max(0, N - 32768): the running minima of the points beyond the 32 768 a workgroup keeps on chip; 0 for arguments
+ * out of range */
+int64_t surfd_cloud_fps_workspace_bytes(int B, int N);
+/* no reference counterpart; pytorch3d's sample_farthest_points(points, lengths, K):
+ * points[B,N,3] -> idx_out[B,K] (int32 into the cloud), cover2_out[B,K] (fp32, nullable).  Per cloud b with n = lengths[b]
+ * valid points (lengths int32 [B] on the device, NULL = N everywhere): mind[i] = +inf; s = start[b] (int32 [B] on the device,
+ * NULL = 0); for k < K: idx[b,k] = s; mind[i] = min(mind[i], d2(p_i, p_s)) with d2 = (dx dx + dy dy) + dz dz, diff = p_i - p_s,
+ * every operation rounded once; s = the i < n with the largest mind[i], the LOWER index on ties; cover2[b,k] = mind[s], the
+ * squared covering radius of the first k + 1 picks (non-increasing in k, 0 once every point is taken).  For k >= n:
+ * idx[b,k] = -1, cover2[b,k] = 0.  Duplicated points are legal (once mind is 0 everywhere the lowest index is picked again).
+ * Clouds are independent: a row has the same bits whichever batch it is computed in.  1 <= K; 1 <= N <= 1 048 576 and
+ * B <= 1 048 576 (beyond: SURFD_ERR_UNSUPPORTED); B = 0 is a no-op.  lengths[b] outside 1 .. N and start[b] outside
+ * 0 .. n - 1 are the caller's to refuse: the kernel clamps them into range rather than read out of bounds; points beyond
+ * lengths[b] are never read; NaN has no place in the order.  workspace: at least surfd_cloud_fps_workspace_bytes(B, N) bytes
+ * on the device (NULL when that is 0), contents irrelevant before and after; one workspace serves one stream at a time.
+ * Stream-ordered, no host sync, no state kept in the library. */
+int surfd_cloud_fps(const float *points, int B, int N, const int32_t *lengths, const int32_t *start, int K, int32_t *idx_out,
+                    float *cover2_out, void *workspace, surfd_stream s);
+
+/* ------------------------------------------------------------------------------------ */
 /* Mesh renderer: a two-sided z-buffer rasteriser (depth, barycentrics, normals, masks,   */
 /* headlight shading) and contour images, for condition images / sketches, view-based     */
 /* evaluation and previews.  No reference counterpart (the reference looks at meshes in   */

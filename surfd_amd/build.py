@@ -26,6 +26,7 @@ SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshdist.hip")          # closest p
 SOURCES.insert(SOURCES.index("mcubes.cpp"), "cloudnn.hip")           # nearest neighbours / Chamfer matrices of clouds (surfd_amd/cloudmetrics.py)
 SOURCES.insert(SOURCES.index("mcubes.cpp"), "raster.hip")            # mesh renderer: depth / normal / mask / contour views (surfd_amd/render.py)
 SOURCES.insert(SOURCES.index("mcubes.cpp"), "voxel.hip")             # occupancy grids and volumetric IoU (surfd_amd/voxelize.py)
+SOURCES.insert(SOURCES.index("mcubes.cpp"), "cloudfps.hip")          # farthest point sampling (surfd_amd/cloudsample.py)
 # cloudnn.hip: without SLP vectorisation the pair test stays 8 plain fp32 instructions + half a v_min3; with it the compiler packs
 # half of them into v_pk_*_f32 (issued at half rate, so nothing is gained) and pads the loop with s_nop
 FILE_FLAGS = {"cloudnn.hip": ["-fno-slp-vectorize"]}

@@ -3,6 +3,7 @@ points or meshes to a mesh.  The counterparts of the reference's open3d-based da
 
   read_mesh                  <- AutoEncoder/utils.py:13-38               (OBJ only)
   sample_points_uniformly    <- open3d TriangleMesh.sample_points_uniformly as used at utils.py:280, preprocess_udfs.py:126
+  sample_points_evenly       no counterpart: open3d's sample_points_poisson_disk; uniform candidates + cloudsample.farthest_point_sampling
   sample_points_around_pcd   <- AutoEncoder/utils.py:167-220             (same RNG calls in the same order)
   closest_points, MeshDistance <- open3d RaycastingScene.compute_closest_points (utils.py:228-234)
   compute_udf_and_gradients  <- AutoEncoder/utils.py:223-240
@@ -204,6 +205,25 @@ def sample_points_uniformly(vertices: Tensor, triangles: Tensor, number_of_point
     r2 = r[:, 1][:, None]
     # the combination in fp64, rounded once: the point is off its triangle by half an ulp per coordinate at most
     return ((1 - s) * a[pick].double() + s * (1 - r2) * b[pick].double() + s * r2 * c[pick].double()).float()
+
+
+def sample_points_evenly(vertices: Tensor, triangles: Tensor, number_of_points: int, init_factor: int = 5,
+                         generator: Optional[torch.Generator] = None) -> Tensor:
+    """``number_of_points`` points that cover the surface evenly, [K, 3]: ``sample_points_uniformly(init_factor * K)`` as the
+    candidates (already in random order), then farthest point sampling down to K from candidate 0 (surfd_amd/cloudsample.py,
+    csrc/cloudfps.hip).  The counterpart of open3d's ``sample_points_poisson_disk(number_of_points, init_factor=5)``.  The mesh
+    may live on any device: the candidates are drawn on the mesh's device with ``generator`` (so a CPU mesh and a CPU generator
+    give the same candidates as ``sample_points_uniformly``), moved to the GPU for the farthest point sampling, which has no
+    CPU path, and the result is moved back to the mesh's device.  ``init_factor = 1`` returns the candidates reordered."""
+    from .cloudsample import farthest_point_sampling
+    if number_of_points < 1:
+        raise ValueError("number_of_points must be positive")
+    if isinstance(init_factor, bool) or not isinstance(init_factor, int) or init_factor < 1:
+        raise ValueError(f"init_factor must be a positive int, got {init_factor}")
+    candidates = sample_points_uniformly(vertices, triangles, init_factor * number_of_points, generator=generator)
+    on_gpu = candidates.cuda().contiguous()
+    idx, _ = farthest_point_sampling(on_gpu[None], number_of_points)
+    return on_gpu[idx[0]].to(vertices.device)
 
 
 def sample_points_around_pcd(pcd: Tensor, stds: List[float], num_points_per_std: List[int], coords_range: Tuple[float, float],
