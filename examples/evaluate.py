@@ -26,6 +26,12 @@ the default, ``uniform``, is the behaviour described above and leaves the JSON a
 subsampling).  Both items of a pair are voxelised in ONE frame: with ``--normalize bbox`` / ``unit_sphere`` the transform of the
 REFERENCE item (from its vertices or points) is applied to both.  ``.npz`` clouds are scored in ``points`` mode only; elsewhere
 the pair is listed under ``skipped``.
+
+``--paired --normal_consistency`` adds the normal consistency of every pair: normals are estimated on both final clouds (after
+sampling and normalisation, so ``.obj`` and ``.npz`` items are treated alike, as a scan would be) from their ``--normals_k``
+nearest neighbours (surfd_amd/cloudnormals.py), and every point's normal is compared with that of its nearest neighbour in the
+other cloud: the mean of |<n, n'>| in both directions, averaged (cloudmetrics.normal_consistency; 1 = the same orientation
+everywhere).  The JSON then records ``normal_consistency`` and ``normals_k`` among its options.
 """
 from __future__ import annotations
 
@@ -39,7 +45,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from surfd_amd import cloudmetrics, cloudsample, meshprep  # noqa: E402
+from surfd_amd import cloudmetrics, cloudnormals, cloudsample, meshprep  # noqa: E402
 
 
 def parse(argv=None):
@@ -58,6 +64,8 @@ def parse(argv=None):
     ap.add_argument("--voxel_iou", type=int, default=0, metavar="R", help="--paired: also score volumetric IoU on an R^3 grid (0 = off)")
     ap.add_argument("--voxel_bounds", type=float, nargs=2, default=(-1.0, 1.0), metavar=("LO", "HI"))
     ap.add_argument("--voxel_mode", choices=("surface", "solid", "points"), default="surface")
+    ap.add_argument("--normal_consistency", action="store_true", help="--paired: also score the normal consistency of every pair")
+    ap.add_argument("--normals_k", type=int, default=16, metavar="K", help="--normal_consistency: neighbours per estimated normal (3 .. 64)")
     ap.add_argument("--output", default="metrics.json")
     return ap.parse_args(argv)
 
@@ -164,6 +172,10 @@ def voxel_scores(gen_items, ref_items, a):
 def run(a):
     if a.voxel_iou and not a.paired:
         raise SystemExit("--voxel_iou scores pairs: it needs --paired")
+    if a.normal_consistency and not a.paired:
+        raise SystemExit("--normal_consistency scores pairs: it needs --paired")
+    if a.normal_consistency and not (cloudnormals.K_MIN <= a.normals_k <= min(cloudnormals.K_MAX, a.num_points)):
+        raise SystemExit(f"--normals_k must lie in {cloudnormals.K_MIN} .. {cloudnormals.K_MAX} and not exceed --num_points")
     if not torch.cuda.is_available():
         raise SystemExit("evaluate.py runs on the GPU (no CPU fallback)")
     if a.init_factor < 1:
@@ -193,6 +205,13 @@ def run(a):
             if scores:
                 out["mean"]["voxel_iou"] = float(np.mean([s["voxel_iou"] for s in scores.values()], dtype=np.float64))
             out["skipped"] = skipped
+        if a.normal_consistency:
+            out["options"].update(normal_consistency=True, normals_k=a.normals_k)
+            n_gen, n_ref = cloudnormals.estimate_normals(gen, k=a.normals_k)[0], cloudnormals.estimate_normals(ref, k=a.normals_k)[0]
+            nc = cloudmetrics.normal_consistency(gen, n_gen, ref, n_ref)["nc"].cpu().tolist()
+            for i, name in enumerate(gen_items):
+                out["items"][name]["normal_consistency"] = nc[i]
+            out["mean"]["normal_consistency"] = float(np.mean(nc, dtype=np.float64))
     else:
         m = cloudmetrics.compute_all_metrics(gen, ref, chunk=a.chunk)
         out["metrics"] = {"mmd_cd": m["mmd_cd"], "cov_cd": m["cov_cd"], "1nna_cd": m["1nna_cd"]}

@@ -121,7 +121,10 @@ def load_models(ae_dir):
 
 def item_metrics(path, verts, faces, field, seed):
     """what --metrics records for one item, or None where the input carries no mesh: mesh_distance between the reconstruction
-    and the original, the IoU of their surface voxels on a 64^3 grid over [-1, 1]^3 (voxel_iou_surface_64) and, where the file has 'coords' / 'labels', the mean absolute error of the decoder's UDF at those queries"""
+    and the original; the IoU of their surface voxels on a 64^3 grid over [-1, 1]^3 (voxel_iou_surface_64); the normal
+    consistency of 16 Ki = 16 384 surface points per mesh with their face normals, unsigned (normal_consistency_16: the number
+    counts samples, no neighbourhood size enters); and, where the file has 'coords' / 'labels', the mean absolute error of the
+    decoder's UDF at those queries"""
     from surfd_amd import meshprep
     if not path.endswith(".npz"):
         return None
@@ -139,6 +142,10 @@ def item_metrics(path, verts, faces, field, seed):
         out.update(reconstruction_to_original=d["d12"], original_to_reconstruction=d["d21"], mesh_distance=d["sum"])
         from surfd_amd import voxelize
         out["voxel_iou_surface_64"] = float(voxelize.voxel_iou(voxelize.voxelize_surface(rv, rt, 64), voxelize.voxelize_surface(ov, ot, 64)))
+        from surfd_amd import cloudmetrics
+        rp, rn, _ = meshprep.sample_points_with_normals(rv, rt, 16384, generator=g)
+        op, on, _ = meshprep.sample_points_with_normals(ov, ot, 16384, generator=g)
+        out["normal_consistency_16"] = float(cloudmetrics.normal_consistency(rp[None], rn[None], op[None], on[None])["nc"])
     if coords is not None:
         pred = torch.cat([field(coords[i:i + 2 ** 16]) for i in range(0, len(coords), 2 ** 16)])
         out["udf_mean_abs_error"] = float((pred.reshape(-1) - labels).abs().double().mean())

@@ -480,6 +480,30 @@ int surfd_cloud_fps(const float *points, int B, int N, const int32_t *lengths, c
                     float *cover2_out, void *workspace, surfd_stream s);
 
 /* ------------------------------------------------------------------------------------ */
+/* Normals of point clouds: K nearest neighbours within a cloud, the covariance of every  */
+/* neighbourhood and its eigen-decomposition (normal, surface variation).  No reference   */
+/* counterpart (the reference ships no evaluation code): stands for open3d's              */
+/* estimate_normals / pytorch3d's estimate_pointcloud_normals.  fp32 pair arithmetic,     */
+/* fp64 moments and Jacobi sweeps; every output is bitwise a function of the input.       */
+/* ------------------------------------------------------------------------------------ */
+/* no reference counterpart; pytorch3d's estimate_pointcloud_normals(points, neighborhood_size=K) with its knn_points:
+ * x[B,N,3] -> normals[B,N,3], eigenvalues[B,N,3] (fp32, ascending), knn_idx[B,N,K] (int32 into the cloud, nullable).  Per
+ * cloud b with n = lengths[b] valid points (int32 [B] on the device, NULL = N everywhere) and per point i < n:
+ * (1) d = x_j - x_i per coordinate in fp32, d2 = (dx dx + dy dy) + dz dz, every operation rounded once; (2) the neighbourhood
+ * is the K smallest j < n under (d2, j): the point itself is a candidate like any other, ties go to the lower index, knn_idx
+ * lists them in that order; (3) in fp64 and rank order s1_a += d_a, s2_ab += d_a d_b, then m = s1 / K, C_ab = s2_ab / K - m_a m_b;
+ * (4) six cyclic Jacobi sweeps over (0,1), (0,2), (1,2) in fp64 (+ - * / sqrt only; the formulas are in csrc/cloudnormals.hip);
+ * (5) eigenvalues = the three lambda sorted ascending (stably), rounded once to fp32, not clamped; (6) normal = the column of
+ * the smallest, rounded once to fp32, not renormalised, negated as a whole if its component of largest magnitude (lowest axis on
+ * a tie) is negative; (7) rows i >= n are zeros, and -1 in knn_idx; their input is never read.  Clouds and points are
+ * independent: a row has the same bits whichever batch or launch it is computed in.  3 <= K <= 64, K <= N, N <= 1 048 576
+ * (beyond: SURFD_ERR_UNSUPPORTED); B = 0 is a no-op.  lengths[b] outside K .. N is the caller's to refuse: the kernel clamps it
+ * into 0 .. N and writes a cloud with fewer than K points as padding rather than read out of bounds.  NaN has no place in the
+ * order.  Stream-ordered, no host sync, no workspace, no state kept in the library. */
+int surfd_cloud_normals(const float *x, int B, int N, const int32_t *lengths, int K, float *normals, float *eigenvalues,
+                        int32_t *knn_idx, surfd_stream s);
+
+/* ------------------------------------------------------------------------------------ */
 /* Mesh renderer: a two-sided z-buffer rasteriser (depth, barycentrics, normals, masks,   */
 /* headlight shading) and contour images, for condition images / sketches, view-based     */
 /* evaluation and previews.  No reference counterpart (the reference looks at meshes in   */

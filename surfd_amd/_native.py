@@ -137,6 +137,7 @@ _SIGS = {
     "surfd_cloud_nn_matrix": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_float, _P, _P, _P]),
     "surfd_cloud_fps_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "surfd_cloud_fps": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P]),
+    "surfd_cloud_normals": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
     "surfd_raster_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "surfd_raster_destroy": (None, [_P]),
     "surfd_raster_render": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, c_f32p, C.c_int, C.c_int, c_f32p, C.c_float,

@@ -5,6 +5,7 @@ evaluation code, so nothing here has a counterpart there; the pair arithmetic is
 
   nearest_neighbors    per-point nearest neighbour of paired clouds                (csrc/cloudnn.hip, cn_nn_kernel)
   chamfer_distance     d_ab, d_ba, cd, precision, recall, fscore of paired clouds  (the same kernel, both directions)
+  normal_consistency   nc_ab, nc_ba, nc: agreement of the normals of paired clouds (nearest_neighbors + torch, fp64)
   chamfer_matrix       [M, R] Chamfer distances between every cloud of two sets    (csrc/cloudnn.hip, cn_matrix_kernel)
   mmd_cov, one_nna     the set metrics on distance matrices (pure torch, any device, fp32 or fp64)
   compute_all_metrics  two sets of clouds -> {"mmd_cd", "cov_cd", "1nna_cd"}
@@ -99,6 +100,49 @@ def chamfer_distance(a: Tensor, b: Tensor, f_threshold: float = 0.01) -> Dict[st
     pr = precision + recall
     fscore = torch.where(pr > 0, 2 * precision * recall / pr.clamp_min(1e-30), torch.zeros_like(pr))
     return {"d_ab": d_ab, "d_ba": d_ba, "cd": d_ab + d_ba, "precision": precision, "recall": recall, "fscore": fscore}
+
+
+def _normals64(name: str, n: Tensor, like: Tensor) -> Tensor:
+    if not isinstance(n, Tensor) or n.shape != like.shape:
+        raise ValueError(f"{name} must have the shape of its cloud, {tuple(like.shape)}, got "
+                         f"{tuple(n.shape) if isinstance(n, Tensor) else type(n).__name__}")
+    if not n.is_floating_point():
+        raise ValueError(f"{name} must be a floating-point tensor, got {n.dtype}")
+    if n.device != like.device:
+        raise ValueError(f"{name} is on {n.device}, its cloud on {like.device}")
+    return n.double()
+
+
+def _dot3(p: Tensor, q: Tensor) -> Tensor:
+    return (p[..., 0] * q[..., 0] + p[..., 1] * q[..., 1]) + p[..., 2] * q[..., 2]
+
+
+def _cosines(n: Tensor, m: Tensor, idx: Tensor) -> Tensor:
+    """n [B, Na, 3], m [B, Nb, 3] float64, idx [B, Na] into m -> [B, Na]: <n, m'> / sqrt(<n, n> <m', m'>), m' = m[idx]: both
+    vectors normalised in fp64, with one division, so that a vector against itself scores exactly 1 (sqrt(s s) = s in binary
+    floating point); 0 where either vector is zero"""
+    mm = torch.gather(m, 1, idx[:, :, None].expand(-1, -1, 3))
+    scale = (_dot3(n, n) * _dot3(mm, mm)).sqrt()
+    ok = scale > 0
+    return torch.where(ok, _dot3(n, mm) / torch.where(ok, scale, torch.ones_like(scale)), torch.zeros_like(scale))
+
+
+def normal_consistency(a: Tensor, na: Tensor, b: Tensor, nb: Tensor, oriented: bool = False) -> Dict[str, Tensor]:
+    """Paired clouds a [B, Na, 3], b [B, Nb, 3] with normals na [B, Na, 3], nb [B, Nb, 3] (cloudnormals.estimate_normals,
+    meshprep.sample_points_with_normals) -> [B] float64 tensors: ``nc_ab`` the mean over the points of a of |<n, n'>| between
+    the point's normal and the normal of its nearest neighbour in b (``nearest_neighbors``: ties to the lower index),
+    ``nc_ba`` the same from b to a, ``nc`` their average.  ``oriented``: the signed dot product instead of its magnitude, for
+    normals that carry an orientation.  Both normals are normalised in fp64; a zero vector scores 0.  1 = the normals agree
+    everywhere (the normal consistency MeshUDF reports)."""
+    _check_pair(a, b, paired=True)
+    na64, nb64 = _normals64("na", na, a), _normals64("nb", nb, b)
+    _, iab = nearest_neighbors(a, b)
+    _, iba = nearest_neighbors(b, a)
+    dab, dba = _cosines(na64, nb64, iab), _cosines(nb64, na64, iba)
+    if not oriented:
+        dab, dba = dab.abs(), dba.abs()
+    nc_ab, nc_ba = dab.mean(1), dba.mean(1)
+    return {"nc_ab": nc_ab, "nc_ba": nc_ba, "nc": (nc_ab + nc_ba) / 2}
 
 
 # ---- Chamfer matrix of two sets -------------------------------------------------------------------------------------------------

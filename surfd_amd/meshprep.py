@@ -3,6 +3,7 @@ points or meshes to a mesh.  The counterparts of the reference's open3d-based da
 
   read_mesh                  <- AutoEncoder/utils.py:13-38               (OBJ only)
   sample_points_uniformly    <- open3d TriangleMesh.sample_points_uniformly as used at utils.py:280, preprocess_udfs.py:126
+  sample_points_with_normals no counterpart: the same draw as sample_points_uniformly, with the face normal of every point
   sample_points_evenly       no counterpart: open3d's sample_points_poisson_disk; uniform candidates + cloudsample.farthest_point_sampling
   sample_points_around_pcd   <- AutoEncoder/utils.py:167-220             (same RNG calls in the same order)
   closest_points, MeshDistance <- open3d RaycastingScene.compute_closest_points (utils.py:228-234)
@@ -205,6 +206,34 @@ def sample_points_uniformly(vertices: Tensor, triangles: Tensor, number_of_point
     r2 = r[:, 1][:, None]
     # the combination in fp64, rounded once: the point is off its triangle by half an ulp per coordinate at most
     return ((1 - s) * a[pick].double() + s * (1 - r2) * b[pick].double() + s * r2 * c[pick].double()).float()
+
+
+def sample_points_with_normals(vertices: Tensor, triangles: Tensor, n: int,
+                               generator: Optional[torch.Generator] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """``n`` points uniform on the surface with the normal of the triangle each was drawn on -> (points [n, 3] float32, normals
+    [n, 3] float32, tri [n] int64: the triangle of every point).  The same random calls in the same order as
+    ``sample_points_uniformly``: for the same generator state the points are the same bits.  A face normal is
+    (b - a) x (c - a) / |(b - a) x (c - a)| in fp64, rounded once to float32; its sign follows the winding; a triangle without
+    area has the zero normal (and, with probability 0, is never drawn)."""
+    _check_mesh(vertices, triangles, need_cuda=False)
+    if n < 0:
+        raise ValueError("n must not be negative")
+    t = triangles.long()
+    a, b, c = vertices[t[:, 0]], vertices[t[:, 1]], vertices[t[:, 2]]
+    cross = torch.linalg.cross((b - a).double(), (c - a).double())
+    area = cross.norm(dim=1)
+    if not float(area.sum()) > 0:
+        raise ValueError("the mesh has no area to sample")
+    dev = vertices.device
+    pick = torch.multinomial(area / area.sum(), n, replacement=True, generator=generator) if n else \
+        torch.empty(0, dtype=torch.long, device=dev)
+    r = torch.rand(n, 2, device=dev, generator=generator).double()
+    s = r[:, 0].sqrt()[:, None]
+    r2 = r[:, 1][:, None]
+    points = ((1 - s) * a[pick].double() + s * (1 - r2) * b[pick].double() + s * r2 * c[pick].double()).float()
+    length = (cross * cross).sum(1, keepdim=True).sqrt()
+    face_normals = torch.where(length > 0, cross / torch.where(length > 0, length, torch.ones_like(length)), torch.zeros_like(cross)).float()
+    return points, face_normals[pick], pick
 
 
 def sample_points_evenly(vertices: Tensor, triangles: Tensor, number_of_points: int, init_factor: int = 5,
