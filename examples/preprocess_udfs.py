@@ -12,6 +12,13 @@ at sigma 0.003 / 0.01 / 0.1 plus uniform ones), ``labels`` [500 000] float32 (th
 The files are inputs of examples/reconstruct.py.  Meshes are taken as already normalised to [-1, 1]^3 (the reference's separate
 normalized_obj.py); a mesh with a vertex outside gets a warning.  The random numbers come from the GPU's global RNG, seeded
 with ``--seed`` before every mesh.
+
+    python examples/preprocess_udfs.py --signed --output_dir out/ closed.obj
+
+``--signed`` writes the signed items of the reference's compute_sdf_from_mesh (AutoEncoder/utils.py:317-363) instead: ``labels``
+is the signed distance clipped to +-0.1, negative inside, ``gradients`` carries its sign, and ``--num_queries_on_surface``
+(10 000) points of the surface with label 0 and gradient 0 come first in ``coords``.  The sign is the parity of the mesh's
+crossings along +z from the query and means something for a closed mesh only.  Without the flag nothing changes.
 """
 from __future__ import annotations
 
@@ -36,6 +43,8 @@ def parse(argv=None):
                     metavar=("N_0.003", "N_0.01", "N_0.1", "N_UNIFORM"))
     ap.add_argument("--max_dist", type=float, default=0.1)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--signed", action="store_true", help="signed distances (negative inside) instead of unsigned ones; closed meshes only")
+    ap.add_argument("--num_queries_on_surface", type=int, default=10_000, help="with --signed: on-surface queries put in front")
     return ap.parse_args(argv)
 
 
@@ -58,8 +67,13 @@ def prepare_one(path, a):
               "to that cube, normalise the mesh first", file=sys.stderr)
     vd, td = v.cuda(), t.cuda()
     pcd = meshprep.sample_points_uniformly(vd, td, a.num_surface_points)                       # preprocess_udfs.py:126-127
-    coords, labels, gradients = meshprep.compute_udf_from_mesh(vd, td, num_surface_points=a.num_surface_points,
-                                                               num_queries_per_std=list(a.num_queries_per_std), max_dist=a.max_dist)
+    if a.signed:
+        coords, labels, gradients = meshprep.compute_sdf_from_mesh(vd, td, num_surface_points=a.num_surface_points,
+                                                                   num_queries_on_surface=a.num_queries_on_surface,
+                                                                   num_queries_per_std=list(a.num_queries_per_std), max_dist=a.max_dist)
+    else:
+        coords, labels, gradients = meshprep.compute_udf_from_mesh(vd, td, num_surface_points=a.num_surface_points,
+                                                                   num_queries_per_std=list(a.num_queries_per_std), max_dist=a.max_dist)
     return dict(vertices=v.numpy(), triangles=t.numpy(), pcd=pcd.cpu().numpy(), coords=coords.cpu().numpy(),
                 labels=labels.cpu().numpy(), gradients=gradients.cpu().numpy())
 

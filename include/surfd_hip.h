@@ -432,6 +432,49 @@ int surfd_mesh_closest(const surfd_mesh *m, const float *queries, int Q, int fla
                        int64_t *skipped_tiles, surfd_stream s);
 
 /* ------------------------------------------------------------------------------------ */
+/* Ray casting on a mesh: first hit per ray and the number of triangles a ray meets.      */
+/* Stands for the ray half of open3d's RaycastingScene (cast_rays, count_intersections)   */
+/* and, through the crossing count, for compute_signed_distance as AutoEncoder/utils.py:242-264 */
+/* calls it (compute_sdf_and_gradients, under compute_sdf_from_mesh, utils.py:317-363).   */
+/* fp32 in, fp64 pair arithmetic; bitwise deterministic.                                  */
+/* ------------------------------------------------------------------------------------ */
+typedef struct surfd_rayscene surfd_rayscene;
+#define SURFD_RAY_BRUTE_FORCE 1     /* flags bit 0: test every (ray, triangle) pair, no culling */
+#define SURFD_RAY_COUNT_SKIPPED 2   /* flags bit 1: count the (wave, tile) visits that culling skips (surfd_rayscene_skipped) */
+/* vertices[V,3] fp32 and triangles[F,3] int32 on the device -> the triangles' corners and per-tile bounding spheres (the
+ * inputs are not referenced after the call).  F >= 1; every index must lie in [0, V): checked on the device and reported as
+ * SURFD_ERR_ARG, never as a fault.  Degenerate triangles are legal and are never hit.  host-sync. */
+int surfd_rayscene_create(const float *vertices, int V, const int32_t *triangles, int F, surfd_stream s, surfd_rayscene **out);
+void surfd_rayscene_destroy(surfd_rayscene *m);
+int surfd_rayscene_num_triangles(const surfd_rayscene *m);
+/* no reference counterpart; open3d's RaycastingScene.cast_rays, of which the reference uses the distance queries only:
+ * rays[R,6] (origin, direction; the direction need not have unit length and t counts in units of it) -> per ray the first triangle met with tmin <= t < tmax: t[R] (fp32), tri[R] (int32, index into the triangles given to
+ * create), uv[R,2] (the weights of the triangle's second and third corner at the hit), normal[R,3] (the triangle's unit normal
+ * by its winding, not turned towards the ray); any of the four may be NULL.  A miss is t = +inf, tri = -1, uv = normal = 0, and
+ * so is a ray with a NaN, an Inf or a zero direction.  The pair test is the shear-and-scale form of Woop, Benthin and Wald in
+ * fp64, two-sided, with the top-left rule on edges that a ray meets exactly: every operation and its order are fixed (header of
+ * csrc/raycast.hip) and the numpy restatement tests/raycast_ref.py gives the same bits.  The winner is the minimum under (bits
+ * of t, triangle index), so a ray's outputs do not depend on the other rays of the call, on the order of the triangles other
+ * than through that index, or on culling: the culled path equals SURFD_RAY_BRUTE_FORCE bit for bit.  Culling skips tiles of 32
+ * consecutive triangles for waves of 64 consecutive rays; it pays when both are spatially coherent (the Python wrapper sorts
+ * both by Morton code).  tmin must be finite and >= 0, tmax must not be a NaN (SURFD_ERR_ARG).  R = 0 is a no-op.  The handle
+ * keeps the call's partial results in a workspace of its own (grown on demand, which syncs the stream): a handle serves one
+ * stream and one host thread at a time. */
+int surfd_rayscene_cast(surfd_rayscene *m, const float *rays, int R, float tmin, float tmax, int flags, float *t, int32_t *tri,
+                        float *uv, float *normal, surfd_stream s);
+/* RaycastingScene.count_intersections, whose parity is the sign of compute_signed_distance at AutoEncoder/utils.py:251:
+ * count[R] (int32) = the number of triangles the ray meets with tmin <= t < tmax under
+ * the same pair test.  A ray through an edge shared by two triangles, or through a vertex, is counted once where the surface
+ * crosses it and 0 or 2 times where the surface folds back, so the parity of the count from a point tells inside from outside
+ * on a closed mesh. */
+int surfd_rayscene_count(surfd_rayscene *m, const float *rays, int R, float tmin, float tmax, int flags, int32_t *count,
+                         surfd_stream s);
+/* no reference counterpart; a measurement of the culling:
+ * the number of (wave, tile) visits the last call with SURFD_RAY_COUNT_SKIPPED skipped, and how many it had in all (waves of 64
+ * consecutive rays, tiles of 32 consecutive triangles), to host memory.  host-sync.  Measurement only. */
+int surfd_rayscene_skipped(surfd_rayscene *m, int64_t *skipped, int64_t *total, surfd_stream s);
+
+/* ------------------------------------------------------------------------------------ */
 /* Point-cloud metrics: nearest neighbours between clouds and the matrix of directed      */
 /* Chamfer means between two sets of clouds.  No reference counterpart (the reference     */
 /* ships no evaluation code): stands for pytorch3d's knn_points(p1, p2, K=1) /            */

@@ -1,0 +1,541 @@
+// Ray casting on a triangle mesh: first hit per ray and the number of triangles a ray meets.  The ray half of open3d's
+// RaycastingScene (cast_rays, count_intersections, and through the crossing count compute_occupancy / compute_signed_distance,
+// which the reference's AutoEncoder/utils.py:242-264 calls); the closest-point half is meshdist.hip.  fp32 in, fp64 pair
+// arithmetic on the VALU, no MFMA, no atomics except the integer one of the skipped-tile count.
+//
+// The contract of one (ray, triangle) pair: rc_ray() and rc_pair(), restated operation for operation in tests/raycast_ref.py.
+// Every operation is ONE fp64 IEEE rounding (the library is built with -ffp-contract=off; nothing in the pair test is an fma)
+// and only + - * / occur.  The form is the shear-and-scale test of Woop, Benthin and Wald (Watertight Ray/Triangle
+// Intersection, JCGT 2013):
+//   ray     ok = all six components finite and d != 0.  kz = the axis of the largest |d| (lower axis on a tie), kx = kz + 1,
+//           ky = kz + 2 (mod 3), exchanged when d[kz] < 0 so that the winding survives;  Sx = d[kx] / d[kz], Sy = d[ky] / d[kz],
+//           Sz = 1 / d[kz].
+//   vertex  Pz = P[kz] - o[kz];  Px = (P[kx] - o[kx]) - Sx Pz;  Py = (P[ky] - o[ky]) - Sy Pz: a function of the vertex and the
+//           ray alone.
+//   edges   U = Cx By - Cy Bx, V = Ax Cy - Ay Cx, W = Bx Ay - By Ax.  The triangle on the other side of an edge forms the same
+//           two products and subtracts them the other way round, so its value is the exact negative: no ray slips between two
+//           triangles, none is counted by both.  det = (U + V) + W; det == 0 (no area in the ray's frame) is never a hit.
+//           s = sign(det); a hit needs s U, s V, s W each > 0, or == 0 on an edge that owns its zero.  After the
+//           normalisation by s the triangle runs counter-clockwise along eU = s (B - C), eV = s (C - A), eW = s (A - B) (sheared
+//           x, y); an edge owns its zero when e.y < 0 or (e.y == 0 and e.x < 0): the top-left rule.  The neighbour's edge vector
+//           is the exact negative, so exactly one of the two owns a shared edge where the surface crosses the ray; where it
+//           folds back both or neither do (count 2 or 0).
+//   t       T = (U Az + V Bz) + W Cz;  t = float((Sz T) / det), -0 made +0;  a hit needs tmin <= t < tmax on that fp32 value.
+//   winner  of a cast: the minimum of the 64-bit key bits(t) << 32 | triangle (t >= +0: its bits order like its value).
+//   finish  for the winner only: uv = float(V / det), float(W / det);  normal = (B - A) x (C - A) in fp64, divided by its fp64
+//           length (sqrt of (nx nx + ny ny) + nz nz), rounded to fp32; zero where that length is 0.
+//   miss    t = +inf, tri = -1, uv = normal = 0, count = 0; also for a ray that is not ok, whose components are never used.
+// The key of a pair does not depend on the traversal, and the minimum of a total order does not depend on the order in which
+// it is taken: any split count, tile order or culling gives the same bits.
+//
+// Kernels:
+//   rc_gather_kernel   (vertices, triangles) -> three float4 per triangle (A, B, C); an index outside [0, V) raises a flag.
+//   rc_bounds_kernel   one bounding sphere per tile of 32 triangles and per chunk of 8 tiles.
+//   rc_trace_kernel    one ray per lane, 256 rays per workgroup; kz, the shear and the origin stay in registers.  The triangles
+//                      of one split stream through LDS in chunks of 256; all lanes of a wave read the same triangle at the same
+//                      time (a broadcast).  grid.y = the splits of the triangle range.  <CULL>: a chunk is not staged when no
+//                      lane of the workgroup can hit its sphere, a tile is skipped when no lane of the wave can.  <COUNT>:
+//                      counts hits instead of keeping the smallest key.
+//   rc_finish_*_kernel the minimum key / the sum of the counts over the splits; the cast one evaluates the winner once more.
+//
+// Culling bound (rc_cannot_hit), derived, not tuned.  u = 2^-24.  A sphere (c, rs) of a tile: c = the middle of the bounding
+// box, r~ = the largest computed vertex distance (>= r (1 - 4u), r the true one), rs = r~ (1 + 2^-12) + 2^-60.  A lane may
+// only vote for a skip when its ray is TAME: |o_i| <= 2^20 and 2^-20 <= max |d_i| <= 2^20, and a sphere with a |c_i| > 2^20 or a
+// radius that is not finite gets rs = +inf and is never skipped; inside these ranges no product below overflows and the
+// absolute error of an underflowing product (<= 2^-149) reaches the results by at most 2^-84, which the 2^-60 in rs covers.
+// A pair that the test accepts has the true line within the pair test's own fp64 rounding (2^-50 relative to |P - o|, see the
+// caveat) of a point of the triangle, hence of the sphere, and its t~ = (Sz T) / det is a combination of Sz Az, Sz Bz, Sz Cz
+// with the computed weights U / det .. >= 0 that sum to 1: it lies between the smallest and the largest of the three.
+//   1  line: w = fl(c - o), s = fl(fl(w.d) / fl(d.d)), D~2 = |fl(w - s d)|^2, all fp32.  |s - s*| |d| <= 8.1u |w| (the dot
+//      products carry 3u |w| |d| and 3u |d|^2, w itself u |w|, the division u), the difference vector 2u (|w| + D) more, its
+//      squared length 3u: D~ <= D (1 + 5u) + 11u |w| for the true distance D from c to the line.  A hit has D <= r <= rho with
+//      rho = rs / (1 + 2^-13) (r <= r~ / (1 - 4u)), and (rho (1 + 5u) + y)^2 <= rho^2 (1 + 5u)^2 (1 + 2^-11) + y^2 (1 + 2^11)
+//      with y = 11u |w|:
+//      y^2 (1 + 2^11) = 121 * 2049 * 2^-48 |w|^2 < 2^-30 |w|^2.  The test skips when D~2 > rs^2 (1 + 2^-10) + 2^-27 fl(w.w):
+//      a factor 2 on the first term's margin and 8 on the second in hand for the roundings of the right-hand side itself.
+//   2  slab along kz: q = fl(fl(c[kz] - o[kz]) * fl(1 / d[kz])) is within 3u |q| of the centre's parameter, h = fl(rs |1 / d[kz]|)
+//      is above the half width r / |d[kz]| of the parameters of everything in the sphere, so every t~ of the tile lies in
+//      [q - h, q + h] and its fp32 value within u (|q| + h) of that.  With e = 2^-20 (|q| + h) + 2^-100 (the roundings listed and
+//      those of the test's own three operations stay below 2^-21 (|q| + h)) the test skips when (q - h) - e > hi or
+//      (q + h) + e < tmin;  hi = tmax, or in a cast the lane's best t so far: strict, so a pair that ties the best t and might
+//      win on the index is never skipped.
+//   A NaN or Inf anywhere in the test makes its compares false: no skip.
+//   Caveat: the pair test itself rounds (2^-53 (|Px Qy| + |Py Qx|) per edge function).  A triangle whose sheared area is below
+//   that, a needle seen edge-on, can be reported hit by a ray that passes its supporting line outside the triangle; the culled
+//   and the brute-force path can differ for such a pair only.  The restatement and SURFD_RAY_BRUTE_FORCE always agree.
+//
+// Bounds: ray n >= R reads ray R - 1 and writes nothing.  Staging reads records below F only; LDS is indexed with u < cnt <= 256.
+// The sphere arrays are indexed with c < nchunk and c * 8 + tt < ntile.  Partial results [S, R] live in the handle's workspace:
+// one stream at a time per handle.  Hazards: the LDS chunk is bracketed by a barrier on both sides.
+#include "common.h"
+#include <cfloat>
+#include <climits>
+#include <cmath>
+#include <algorithm>
+
+namespace surfd {
+
+constexpr int RC_TILE = 32;                       // triangles per bounding sphere
+constexpr int RC_CHUNK_TILES = 8;
+constexpr int RC_CHUNK = RC_TILE * RC_CHUNK_TILES;    // triangles per LDS chunk, and rays per workgroup
+constexpr int RC_MAX_SPLITS = 64;
+constexpr int RC_REC4 = 3;                        // float4 per triangle: A, B, C
+constexpr unsigned long long RC_MISS = 0xFFFFFFFFFFFFFFFFull;
+constexpr float RC_TAME_HI = 1048576.f;           // 2^20
+constexpr float RC_TAME_LO = 9.5367431640625e-07f;   // 2^-20
+constexpr float RC_RADIUS_REL = 2.44140625e-04f;  // 2^-12
+constexpr float RC_RADIUS_ABS = 8.67361737988403547e-19f;   // 2^-60
+constexpr float RC_R2_MARGIN = 9.765625e-04f;     // 2^-10
+constexpr float RC_W2_MARGIN = 7.450580596923828125e-09f;   // 2^-27
+constexpr float RC_T_REL = 9.5367431640625e-07f;  // 2^-20
+constexpr float RC_T_ABS = 7.88860905221011805e-31f;        // 2^-100
+
+struct RcRay {
+    double ox, oy, oz;       // the origin, permuted to (kx, ky, kz)
+    double Sx, Sy, Sz;
+    int kx, ky, kz;
+    bool ok;
+};
+
+__host__ __device__ __forceinline__ float rc_sel(float x, float y, float z, int k) { return k == 0 ? x : (k == 1 ? y : z); }
+
+__host__ __device__ __forceinline__ bool rc_finite(float x) { return x - x == 0.f; }
+
+__host__ __device__ __forceinline__ RcRay rc_ray(float ox, float oy, float oz, float dx, float dy, float dz) {
+    RcRay r;
+    r.ok = rc_finite(ox) && rc_finite(oy) && rc_finite(oz) && rc_finite(dx) && rc_finite(dy) && rc_finite(dz) &&
+           (dx != 0.f || dy != 0.f || dz != 0.f);
+    if (!r.ok) { ox = oy = oz = dx = dy = 0.f; dz = 1.f; }
+    const float ax = __builtin_fabsf(dx), ay = __builtin_fabsf(dy), az = __builtin_fabsf(dz);
+    const int kz = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
+    int kx = kz == 2 ? 0 : kz + 1;
+    int ky = kx == 2 ? 0 : kx + 1;
+    const double dk = (double)rc_sel(dx, dy, dz, kz);
+    if (dk < 0.0) { const int t = kx; kx = ky; ky = t; }
+    r.kx = kx; r.ky = ky; r.kz = kz;
+    r.ox = (double)rc_sel(ox, oy, oz, kx);
+    r.oy = (double)rc_sel(ox, oy, oz, ky);
+    r.oz = (double)rc_sel(ox, oy, oz, kz);
+    r.Sx = (double)rc_sel(dx, dy, dz, kx) / dk;
+    r.Sy = (double)rc_sel(dx, dy, dz, ky) / dk;
+    r.Sz = 1.0 / dk;
+    return r;
+}
+
+__host__ __device__ __forceinline__ bool rc_owns(double s, double ex, double ey) {
+    ex = s * ex; ey = s * ey;
+    return ey < 0.0 || (ey == 0.0 && ex < 0.0);
+}
+
+// The pair test.  true = a hit with tmin <= t < tmax; V, W, det feed the finish (dead code elsewhere).
+__host__ __device__ __forceinline__ bool rc_pair(const RcRay &r, float4 a, float4 b, float4 c, float tmin, float tmax, float &t,
+                                                 double &V, double &W, double &det) {
+    const double Az = (double)rc_sel(a.x, a.y, a.z, r.kz) - r.oz;
+    const double Ax = ((double)rc_sel(a.x, a.y, a.z, r.kx) - r.ox) - r.Sx * Az;
+    const double Ay = ((double)rc_sel(a.x, a.y, a.z, r.ky) - r.oy) - r.Sy * Az;
+    const double Bz = (double)rc_sel(b.x, b.y, b.z, r.kz) - r.oz;
+    const double Bx = ((double)rc_sel(b.x, b.y, b.z, r.kx) - r.ox) - r.Sx * Bz;
+    const double By = ((double)rc_sel(b.x, b.y, b.z, r.ky) - r.oy) - r.Sy * Bz;
+    const double Cz = (double)rc_sel(c.x, c.y, c.z, r.kz) - r.oz;
+    const double Cx = ((double)rc_sel(c.x, c.y, c.z, r.kx) - r.ox) - r.Sx * Cz;
+    const double Cy = ((double)rc_sel(c.x, c.y, c.z, r.ky) - r.oy) - r.Sy * Cz;
+    const double U = Cx * By - Cy * Bx;
+    V = Ax * Cy - Ay * Cx;
+    W = Bx * Ay - By * Ax;
+    det = (U + V) + W;
+    const double s = det > 0.0 ? 1.0 : -1.0;
+    const double nU = s * U, nV = s * V, nW = s * W;
+    const bool in = (nU > 0.0 || (nU == 0.0 && rc_owns(s, Bx - Cx, By - Cy))) &&
+                    (nV > 0.0 || (nV == 0.0 && rc_owns(s, Cx - Ax, Cy - Ay))) &&
+                    (nW > 0.0 || (nW == 0.0 && rc_owns(s, Ax - Bx, Ay - By)));
+    if (!in || !(det != 0.0)) return false;
+    const double T = (U * Az + V * Bz) + W * Cz;
+    t = (float)((r.Sz * T) / det);
+    t = t + 0.f;                                            // -0 -> +0 (not folded: the library is not built with fast-math)
+    return t >= tmin && t < tmax;
+}
+
+__host__ __device__ __forceinline__ unsigned rc_float_bits(float x) {
+    union { float f; unsigned u; } v;
+    v.f = x;
+    return v.u;
+}
+
+__host__ __device__ __forceinline__ float rc_bits_float(unsigned x) {
+    union { float f; unsigned u; } v;
+    v.u = x;
+    return v.f;
+}
+
+__device__ __forceinline__ float rc_dot(float ax, float ay, float az, float bx, float by, float bz) {
+    return fmaf(az, bz, fmaf(ay, by, ax * bx));
+}
+
+// what a lane needs of its ray to vote on a sphere (fp32)
+struct RcCull {
+    float ox, oy, oz, dx, dy, dz;
+    float dd;            // d.d
+    float ok_z, iz;      // o[kz], 1 / d[kz]
+    int kz;
+    bool dead;           // no ray here, or a ray that hits nothing: always votes for the skip
+    bool tame;           // the bound holds for this ray (header); otherwise it never votes for a skip
+};
+
+__device__ __forceinline__ RcCull rc_cull_setup(float ox, float oy, float oz, float dx, float dy, float dz, int kz, bool live) {
+    RcCull q;
+    q.ox = ox; q.oy = oy; q.oz = oz; q.dx = dx; q.dy = dy; q.dz = dz;
+    q.dd = rc_dot(dx, dy, dz, dx, dy, dz);
+    q.kz = kz;
+    q.ok_z = rc_sel(ox, oy, oz, kz);
+    const float dk = rc_sel(dx, dy, dz, kz);
+    q.iz = __fdiv_rn(1.f, dk);
+    q.dead = !live;
+    const float adk = fabsf(dk);
+    q.tame = fabsf(ox) <= RC_TAME_HI && fabsf(oy) <= RC_TAME_HI && fabsf(oz) <= RC_TAME_HI && adk >= RC_TAME_LO && adk <= RC_TAME_HI;
+    return q;
+}
+
+// true where no triangle inside the sphere (c.xyz, rs = c.w) can be a hit of this lane's ray with tmin <= t < (or, in a cast,
+// <=) hi: the two tests of the header
+__device__ __forceinline__ bool rc_cannot_hit(float4 c, const RcCull &q, float tmin, float hi) {
+    const float wx = c.x - q.ox, wy = c.y - q.oy, wz = c.z - q.oz;
+    const float s = __fdiv_rn(rc_dot(wx, wy, wz, q.dx, q.dy, q.dz), q.dd);
+    const float ex = wx - s * q.dx, ey = wy - s * q.dy, ez = wz - s * q.dz;
+    const float D2 = rc_dot(ex, ey, ez, ex, ey, ez);
+    const float W2 = rc_dot(wx, wy, wz, wx, wy, wz);
+    const float r2 = c.w * c.w;
+    const float rhs = fmaf(W2, RC_W2_MARGIN, fmaf(r2, RC_R2_MARGIN, r2));
+    const bool off_line = D2 > rhs && D2 < INFINITY;
+    const float z = rc_sel(c.x, c.y, c.z, q.kz) - q.ok_z;
+    const float p = z * q.iz;
+    const float h = c.w * fabsf(q.iz);
+    const float e = fmaf(fabsf(p) + h, RC_T_REL, RC_T_ABS);
+    const bool off_range = (p - h) - e > hi || (p + h) + e < tmin;
+    return q.dead || (q.tame && (off_line || off_range));
+}
+
+// one thread per triangle
+__global__ __launch_bounds__(256) void rc_gather_kernel(const float *__restrict__ vtx, int V, const int *__restrict__ tri, int F,
+                                                        float4 *__restrict__ rec, int *__restrict__ bad) {
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    if (f >= F) return;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        int k = tri[(long)f * 3 + c];
+        if (k < 0 || k >= V) { atomicOr(bad, 1); k = 0; }
+        rec[(long)f * RC_REC4 + c] = make_float4(vtx[(long)k * 3], vtx[(long)k * 3 + 1], vtx[(long)k * 3 + 2], 0.f);
+    }
+}
+
+// one thread per sphere: sphere s holds the triangles [s * per, min(F, (s + 1) * per))
+__global__ __launch_bounds__(64) void rc_bounds_kernel(const float4 *__restrict__ rec, int F, int per, int count, float4 *__restrict__ sph) {
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= count) return;
+    const long e0 = (long)s * per * RC_REC4, e1 = (long)min(F, (s + 1) * per) * RC_REC4;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (long e = e0; e < e1; ++e) {
+        const float4 p = rec[e];
+        lo[0] = fminf(lo[0], p.x); lo[1] = fminf(lo[1], p.y); lo[2] = fminf(lo[2], p.z);
+        hi[0] = fmaxf(hi[0], p.x); hi[1] = fmaxf(hi[1], p.y); hi[2] = fmaxf(hi[2], p.z);
+    }
+    const float cx = 0.5f * lo[0] + 0.5f * hi[0], cy = 0.5f * lo[1] + 0.5f * hi[1], cz = 0.5f * lo[2] + 0.5f * hi[2];
+    float r2 = 0.f;
+    bool finite = true;
+    for (long e = e0; e < e1; ++e) {
+        const float4 p = rec[e];
+        const float x = p.x - cx, y = p.y - cy, z = p.z - cz;
+        const float d2 = rc_dot(x, y, z, x, y, z);
+        finite = finite && d2 < INFINITY;                     // false for a NaN as well
+        r2 = fmaxf(r2, d2);
+    }
+    const float r = __fsqrt_rn(r2);
+    float rs = fmaf(r, RC_RADIUS_REL, r) + RC_RADIUS_ABS;
+    const bool tame = finite && fabsf(cx) <= RC_TAME_HI && fabsf(cy) <= RC_TAME_HI && fabsf(cz) <= RC_TAME_HI;
+    if (!tame) rs = INFINITY;
+    sph[s] = make_float4(tame ? cx : 0.f, tame ? cy : 0.f, tame ? cz : 0.f, rs);
+}
+
+// rays [R, 6]; split blockIdx.y covers the chunks [y * span, min(nchunk, (y + 1) * span)); partial results pk / pc [S, R]
+template <bool CULL, bool COUNT>
+__global__ __launch_bounds__(256) void rc_trace_kernel(const float4 *__restrict__ rec, int F, const float4 *__restrict__ tile_sph,
+                                                       const float4 *__restrict__ chunk_sph, int nchunk, int span,
+                                                       const float *__restrict__ rays, int R, float tmin, float tmax,
+                                                       unsigned long long *__restrict__ pk, int *__restrict__ pc,
+                                                       unsigned long long *__restrict__ skipped) {
+    __shared__ float4 lds[RC_CHUNK * RC_REC4];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int n = blockIdx.x * RC_CHUNK + tid;
+    const long nr = n < R ? n : R - 1;
+    const float ox = rays[nr * 6], oy = rays[nr * 6 + 1], oz = rays[nr * 6 + 2];
+    const float dx = rays[nr * 6 + 3], dy = rays[nr * 6 + 4], dz = rays[nr * 6 + 5];
+    const RcRay r = rc_ray(ox, oy, oz, dx, dy, dz);
+    const bool live = n < R && r.ok;
+    RcCull q;
+    if constexpr (CULL) q = rc_cull_setup(ox, oy, oz, dx, dy, dz, r.kz, live);
+    unsigned long long key = RC_MISS;
+    int hits = 0;
+    float hi = tmax;
+    unsigned nskip = 0;
+    const int c0 = blockIdx.y * span, c1 = min(nchunk, c0 + span);
+#pragma unroll 1
+    for (int c = c0; c < c1; ++c) {
+        const int f0 = c * RC_CHUNK;
+        const int cnt = min(RC_CHUNK, F - f0);
+        const int tiles = (cnt + RC_TILE - 1) / RC_TILE;
+        if constexpr (CULL) {
+            // a barrier (every lane is done with the previous chunk) that also tells whether any lane needs this chunk
+            const int need = __syncthreads_or(!rc_cannot_hit(chunk_sph[c], q, tmin, hi));
+            if (!need) { nskip += tiles; continue; }         // the same in every lane of the workgroup
+        } else {
+            __syncthreads();
+        }
+#pragma unroll
+        for (int i = 0; i < RC_REC4; ++i) {
+            const int e = tid + 256 * i;
+            if (e < cnt * RC_REC4) lds[e] = rec[(long)f0 * RC_REC4 + e];
+        }
+        __syncthreads();
+#pragma unroll 1
+        for (int tt = 0; tt < tiles; ++tt) {
+            const int u0 = tt * RC_TILE, u1 = min(cnt, u0 + RC_TILE);
+            if constexpr (CULL) {
+                if (__all(rc_cannot_hit(tile_sph[c * RC_CHUNK_TILES + tt], q, tmin, hi))) { nskip += 1; continue; }   // wave-uniform
+            }
+            // the counting form is a reduction, which the loop vectoriser would interleave 32 deep (256 registers and scratch)
+#pragma clang loop unroll_count(2) vectorize(disable) interleave(disable)
+            for (int u = u0; u < u1; ++u) {
+                float t = 0.f;
+                double V, W, det;
+                const bool hit = rc_pair(r, lds[u * RC_REC4], lds[u * RC_REC4 + 1], lds[u * RC_REC4 + 2], tmin, tmax, t, V, W, det) && live;
+                if constexpr (COUNT) {
+                    hits += hit ? 1 : 0;
+                } else {
+                    const unsigned long long k = ((unsigned long long)rc_float_bits(t) << 32) | (unsigned)(f0 + u);
+                    key = hit && k < key ? k : key;
+                }
+            }
+            if constexpr (CULL && !COUNT) hi = key == RC_MISS ? tmax : rc_bits_float((unsigned)(key >> 32));
+        }
+    }
+    if (n < R) {
+        if constexpr (COUNT) pc[(long)blockIdx.y * R + n] = hits;
+        else pk[(long)blockIdx.y * R + n] = key;
+    }
+    if constexpr (CULL) {
+        if (skipped && lane == 0 && n < R && nskip) atomicAdd(skipped, (unsigned long long)nskip);
+    }
+}
+
+// the minimum key of ray n over the S splits, then the pair test once more on the winner
+__global__ __launch_bounds__(256) void rc_finish_cast_kernel(const float4 *__restrict__ rec, int F, const float *__restrict__ rays, int R,
+                                                             const unsigned long long *__restrict__ pk, int S, float tmin, float tmax,
+                                                             float *__restrict__ t_out, int *__restrict__ tri, float *__restrict__ uv,
+                                                             float *__restrict__ normal) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= R) return;
+    unsigned long long key = RC_MISS;
+    for (int s = 0; s < S; ++s) key = min(key, pk[(long)s * R + n]);
+    const unsigned f = (unsigned)(key & 0xFFFFFFFFull);
+    const bool got = key != RC_MISS && f < (unsigned)F;
+    float u = 0.f, v = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
+    if (got && (uv || normal)) {
+        const float4 a = rec[(long)f * RC_REC4], b = rec[(long)f * RC_REC4 + 1], c = rec[(long)f * RC_REC4 + 2];
+        const RcRay r = rc_ray(rays[(long)n * 6], rays[(long)n * 6 + 1], rays[(long)n * 6 + 2], rays[(long)n * 6 + 3],
+                               rays[(long)n * 6 + 4], rays[(long)n * 6 + 5]);
+        float t;
+        double V, W, det;
+        (void)rc_pair(r, a, b, c, tmin, tmax, t, V, W, det);
+        u = (float)(V / det);
+        v = (float)(W / det);
+        const double e1x = (double)b.x - (double)a.x, e1y = (double)b.y - (double)a.y, e1z = (double)b.z - (double)a.z;
+        const double e2x = (double)c.x - (double)a.x, e2y = (double)c.y - (double)a.y, e2z = (double)c.z - (double)a.z;
+        const double mx = e1y * e2z - e1z * e2y, my = e1z * e2x - e1x * e2z, mz = e1x * e2y - e1y * e2x;
+        const double nn = (mx * mx + my * my) + mz * mz;
+        if (nn > 0.0 && nn - nn == 0.0) {
+            const double len = __builtin_sqrt(nn);
+            nx = (float)(mx / len); ny = (float)(my / len); nz = (float)(mz / len);
+        }
+    }
+    if (t_out) t_out[n] = got ? rc_bits_float((unsigned)(key >> 32)) : INFINITY;
+    if (tri) tri[n] = got ? (int)f : -1;
+    if (uv) { uv[(long)n * 2] = u; uv[(long)n * 2 + 1] = v; }
+    if (normal) { normal[(long)n * 3] = nx; normal[(long)n * 3 + 1] = ny; normal[(long)n * 3 + 2] = nz; }
+}
+
+__global__ __launch_bounds__(256) void rc_finish_count_kernel(const int *__restrict__ pc, int S, int R, int *__restrict__ count) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= R) return;
+    int total = 0;
+    for (int s = 0; s < S; ++s) total += pc[(long)s * R + n];
+    count[n] = total;
+}
+
+}  // namespace surfd
+
+#ifndef SURFD_RAYCAST_HOST_TEST
+using namespace surfd;
+
+struct surfd_rayscene {
+    int F = 0, ntile = 0, nchunk = 0;
+    float4 *rec = nullptr;            // [F] triangles of 3 float4
+    float4 *tile_sph = nullptr;       // [ntile]
+    float4 *chunk_sph = nullptr;      // [nchunk]
+    unsigned long long *skipped = nullptr;   // (wave, tile) visits the last call with SURFD_RAY_COUNT_SKIPPED skipped
+    long long last_total = 0;         // and how many visits that call had in all
+    mutable void *ws = nullptr;       // partial results (grows)
+    mutable size_t ws_bytes = 0;
+};
+
+static int rc_ws(const surfd_rayscene *m, size_t bytes, hipStream_t st) {
+    if (bytes <= m->ws_bytes) return SURFD_OK;
+    HIP_TRY(hipStreamSynchronize(st));                // the previous call's kernels may still read the old arena
+    (void)hipFree(m->ws); m->ws = nullptr; m->ws_bytes = 0;
+    HIP_TRY(hipMalloc(&m->ws, bytes));
+    m->ws_bytes = bytes;
+    return SURFD_OK;
+}
+
+// splits of the chunk range per block of rays: about 2048 workgroups over the chip (8 per CU), whole chunks per split
+static void rc_splits(int R, int nchunk, int *S, int *span) {
+    const long rb = ceil_div<long>(R, RC_CHUNK);
+    long s = std::max<long>(1, ceil_div<long>(2048, rb));
+    s = std::min<long>({s, (long)RC_MAX_SPLITS, (long)nchunk});
+    *span = (int)ceil_div<long>(nchunk, s);
+    *S = ceil_div(nchunk, *span);
+}
+
+static int rc_check(const char *who, const surfd_rayscene *m, const float *rays, int R, float tmin, float tmax, int flags) {
+    if (R < 0) SURFD_FAIL(SURFD_ERR_ARG, "%s: R = %d is negative", who, R);
+    if (flags & ~(SURFD_RAY_BRUTE_FORCE | SURFD_RAY_COUNT_SKIPPED)) SURFD_FAIL(SURFD_ERR_ARG, "%s: unknown flags 0x%x", who, flags);
+    if (!(tmin >= 0.f) || !(tmin < INFINITY)) SURFD_FAIL(SURFD_ERR_ARG, "%s: tmin = %g must be finite and not negative", who, (double)tmin);
+    if (tmax != tmax) SURFD_FAIL(SURFD_ERR_ARG, "%s: tmax is a NaN", who);
+    if (!m) SURFD_FAIL(SURFD_ERR_ARG, "%s: null handle", who);
+    if (R > 0 && !rays) SURFD_FAIL(SURFD_ERR_ARG, "%s: null rays", who);
+    if (R > (1 << 28)) SURFD_FAIL(SURFD_ERR_UNSUPPORTED, "%s: R = %d is beyond the supported size", who, R);
+    return SURFD_OK;
+}
+
+template <bool COUNT>
+static int rc_trace(surfd_rayscene *m, const float *rays, int R, float tmin, float tmax, int flags, unsigned long long **pk, int **pc,
+                    int *S_out, hipStream_t st) {
+    int S, span, rc;
+    rc_splits(R, m->nchunk, &S, &span);
+    const size_t np = (size_t)S * R;
+    if ((rc = rc_ws(m, np * sizeof(unsigned long long), st))) return rc;
+    *pk = (unsigned long long *)m->ws;
+    *pc = (int *)m->ws;
+    *S_out = S;
+    const bool brute = flags & SURFD_RAY_BRUTE_FORCE;
+    unsigned long long *skipped = nullptr;
+    if (flags & SURFD_RAY_COUNT_SKIPPED) {
+        HIP_TRY(hipMemsetAsync(m->skipped, 0, sizeof(unsigned long long), st));
+        m->last_total = (long long)ceil_div(R, 64) * m->ntile;
+        skipped = brute ? nullptr : m->skipped;
+    }
+    const dim3 grid((unsigned)ceil_div(R, RC_CHUNK), (unsigned)S);
+    if (brute)
+        hipLaunchKernelGGL((rc_trace_kernel<false, COUNT>), grid, dim3(256), 0, st, (const float4 *)m->rec, m->F, (const float4 *)m->tile_sph,
+                           (const float4 *)m->chunk_sph, m->nchunk, span, rays, R, tmin, tmax, *pk, *pc, skipped);
+    else
+        hipLaunchKernelGGL((rc_trace_kernel<true, COUNT>), grid, dim3(256), 0, st, (const float4 *)m->rec, m->F, (const float4 *)m->tile_sph,
+                           (const float4 *)m->chunk_sph, m->nchunk, span, rays, R, tmin, tmax, *pk, *pc, skipped);
+    LAUNCH_CHECK();
+    return SURFD_OK;
+}
+
+extern "C" {
+
+int surfd_rayscene_create(const float *vertices, int V, const int32_t *triangles, int F, surfd_stream s, surfd_rayscene **out) {
+    if (!out) SURFD_FAIL(SURFD_ERR_ARG, "surfd_rayscene_create: null out");
+    *out = nullptr;
+    if (!vertices || !triangles) SURFD_FAIL(SURFD_ERR_ARG, "surfd_rayscene_create: null vertices or triangles");
+    if (V < 1 || F < 1) SURFD_FAIL(SURFD_ERR_ARG, "surfd_rayscene_create: V = %d, F = %d must be positive", V, F);
+    if (F > (1 << 28)) SURFD_FAIL(SURFD_ERR_UNSUPPORTED, "surfd_rayscene_create: F = %d is beyond the supported size", F);
+    hipStream_t st = as_stream(s);
+    surfd_rayscene *m = new surfd_rayscene();
+    m->F = F;
+    m->ntile = ceil_div(F, RC_TILE);
+    m->nchunk = ceil_div(F, RC_CHUNK);
+    int *bad = nullptr;
+    int rc = SURFD_OK, flag = 0;
+    auto run = [&]() -> int {
+        HIP_TRY(hipMalloc(&m->rec, (size_t)F * RC_REC4 * sizeof(float4)));
+        HIP_TRY(hipMalloc(&m->tile_sph, (size_t)m->ntile * sizeof(float4)));
+        HIP_TRY(hipMalloc(&m->chunk_sph, (size_t)m->nchunk * sizeof(float4)));
+        HIP_TRY(hipMalloc(&m->skipped, sizeof(unsigned long long)));
+        HIP_TRY(hipMalloc(&bad, sizeof(int)));
+        HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int), st));
+        HIP_TRY(hipMemsetAsync(m->skipped, 0, sizeof(unsigned long long), st));
+        hipLaunchKernelGGL(rc_gather_kernel, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, st, vertices, V, triangles, F, m->rec, bad);
+        LAUNCH_CHECK();
+        hipLaunchKernelGGL(rc_bounds_kernel, dim3((unsigned)ceil_div(m->ntile, 64)), dim3(64), 0, st, (const float4 *)m->rec, F, RC_TILE,
+                           m->ntile, m->tile_sph);
+        LAUNCH_CHECK();
+        hipLaunchKernelGGL(rc_bounds_kernel, dim3((unsigned)ceil_div(m->nchunk, 64)), dim3(64), 0, st, (const float4 *)m->rec, F, RC_CHUNK,
+                           m->nchunk, m->chunk_sph);
+        LAUNCH_CHECK();
+        HIP_TRY(hipMemcpyAsync(&flag, bad, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return SURFD_OK;
+    };
+    rc = run();
+    (void)hipFree(bad);
+    if (rc == SURFD_OK && flag) {
+        set_error("surfd_rayscene_create: a triangle names a vertex outside [0, %d)", V);
+        rc = SURFD_ERR_ARG;
+    }
+    if (rc != SURFD_OK) { surfd_rayscene_destroy(m); return rc; }
+    *out = m;
+    return SURFD_OK;
+}
+
+void surfd_rayscene_destroy(surfd_rayscene *m) {
+    if (!m) return;
+    (void)hipFree(m->rec); (void)hipFree(m->tile_sph); (void)hipFree(m->chunk_sph); (void)hipFree(m->skipped); (void)hipFree(m->ws);
+    delete m;
+}
+
+int surfd_rayscene_num_triangles(const surfd_rayscene *m) { return m ? m->F : 0; }
+
+int surfd_rayscene_cast(surfd_rayscene *m, const float *rays, int R, float tmin, float tmax, int flags, float *t, int32_t *tri, float *uv,
+                        float *normal, surfd_stream s) {
+    int rc = rc_check("surfd_rayscene_cast", m, rays, R, tmin, tmax, flags);
+    if (rc != SURFD_OK || R == 0) return rc;
+    hipStream_t st = as_stream(s);
+    unsigned long long *pk;
+    int *pc, S;
+    if ((rc = rc_trace<false>(m, rays, R, tmin, tmax, flags, &pk, &pc, &S, st))) return rc;
+    if (t || tri || uv || normal) {
+        hipLaunchKernelGGL(rc_finish_cast_kernel, dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, st, (const float4 *)m->rec, m->F, rays, R,
+                           (const unsigned long long *)pk, S, tmin, tmax, t, tri, uv, normal);
+        LAUNCH_CHECK();
+    }
+    return SURFD_OK;
+}
+
+int surfd_rayscene_count(surfd_rayscene *m, const float *rays, int R, float tmin, float tmax, int flags, int32_t *count, surfd_stream s) {
+    int rc = rc_check("surfd_rayscene_count", m, rays, R, tmin, tmax, flags);
+    if (rc != SURFD_OK || R == 0) return rc;
+    if (!count) SURFD_FAIL(SURFD_ERR_ARG, "surfd_rayscene_count: null count");
+    hipStream_t st = as_stream(s);
+    unsigned long long *pk;
+    int *pc, S;
+    if ((rc = rc_trace<true>(m, rays, R, tmin, tmax, flags, &pk, &pc, &S, st))) return rc;
+    hipLaunchKernelGGL(rc_finish_count_kernel, dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, st, (const int *)pc, S, R, count);
+    LAUNCH_CHECK();
+    return SURFD_OK;
+}
+
+int surfd_rayscene_skipped(surfd_rayscene *m, int64_t *skipped, int64_t *total, surfd_stream s) {
+    if (!m || !skipped || !total) SURFD_FAIL(SURFD_ERR_ARG, "surfd_rayscene_skipped: null argument");
+    hipStream_t st = as_stream(s);
+    unsigned long long v = 0;
+    HIP_TRY(hipMemcpyAsync(&v, m->skipped, sizeof(v), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *skipped = (int64_t)v;
+    *total = (int64_t)m->last_total;
+    return SURFD_OK;
+}
+
+}  // extern "C"
+#endif  // SURFD_RAYCAST_HOST_TEST

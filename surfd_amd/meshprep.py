@@ -9,6 +9,9 @@ points or meshes to a mesh.  The counterparts of the reference's open3d-based da
   closest_points, MeshDistance <- open3d RaycastingScene.compute_closest_points (utils.py:228-234)
   compute_udf_and_gradients  <- AutoEncoder/utils.py:223-240
   compute_udf_from_mesh      <- AutoEncoder/utils.py:268-314
+  compute_sdf_and_gradients  <- AutoEncoder/utils.py:242-264             (the sign comes from surfd_amd/raycast.py)
+  compute_sdf_from_mesh      <- AutoEncoder/utils.py:317-363
+  is_inside                  no counterpart: open3d's RaycastingScene.compute_occupancy as a bool
   point_to_mesh_distance, mesh_distance   no counterpart: how far a reconstruction is from the mesh it came from
 
 Where the reference takes an open3d mesh (``mesh_o3d``) these take ``(vertices [V, 3] float32, triangles [F, 3] integer)``.
@@ -303,6 +306,62 @@ def compute_udf_from_mesh(vertices: Tensor, triangles: Tensor, num_surface_point
         queries = sample_points_around_pcd(cloud, queries_stds, num_queries_per_std, coords_range, vertices.device)
     udf, gradients = compute_udf_and_gradients(vertices, triangles, queries)
     return queries, udf.clamp(0, max_dist), gradients
+
+
+# ---- SDF labels ---------------------------------------------------------------------------------------------------------------
+def _as_scene(vertices, triangles):
+    from .raycast import RaycastingScene
+    return vertices if isinstance(vertices, RaycastingScene) and triangles is None else RaycastingScene(vertices, triangles)
+
+
+def is_inside(vertices: Tensor, triangles: Tensor, points: Tensor, nsamples: int = 1) -> Tensor:
+    """[N] bool: is the point inside the closed mesh.  The parity of the number of crossings of the ray from the point along
+    +z (csrc/raycast.hip); ``nsamples=3`` also asks +x and +y and takes the majority.  On an open mesh the answer means nothing
+    (surfd_amd/raycast.py, ``compute_occupancy(..., return_votes=True)`` tells).  ``vertices`` may be a RaycastingScene
+    (triangles None)."""
+    from .raycast import RaycastingScene, _check_nsamples
+    if not (isinstance(vertices, RaycastingScene) and triangles is None):
+        _check_mesh(vertices, triangles, need_cuda=False)      # shapes and dtypes first, the CPU-tensor refusal last
+    _check_points("points", points, need_cuda=False)
+    _check_nsamples(nsamples)
+    return _as_scene(vertices, triangles).compute_occupancy(points, nsamples) > 0
+
+
+def compute_sdf_and_gradients(vertices: Tensor, triangles: Tensor, queries: Tensor) -> Tuple[Tensor, Tensor]:
+    """AutoEncoder/utils.py:242-264: sdf = the distance to the mesh, negative inside (open3d's compute_signed_distance: the
+    parity of the crossings along +z), and gradients = sign(sdf) * F.normalize(q - c) for the closest point c of the mesh.  A
+    query on the surface has sdf 0 and a zero gradient.  ``vertices`` may be a RaycastingScene (triangles None)."""
+    scene = _as_scene(vertices, triangles)
+    sdf = scene.compute_signed_distance(queries)
+    offset = queries - scene.mesh_distance().closest(queries)[1]
+    return sdf, torch.sign(sdf)[:, None] * F.normalize(offset, dim=-1)
+
+
+def compute_sdf_from_mesh(vertices: Tensor, triangles: Tensor, num_surface_points: int = 100_000, num_queries_on_surface: int = 10_000,
+                          queries_stds: List[float] = [0.003, 0.01, 0.1], num_queries_per_std: List[int] = [5_000, 4_000, 500, 500],
+                          coords_range: Tuple[float, float] = (-1.0, 1.0), max_dist: float = 0.1, convert_to_bce_labels: bool = False,
+                          use_cuda: bool = True, input_queries: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """AutoEncoder/utils.py:317-363 -> (queries, values, gradients): a surface cloud, queries around it (or ``input_queries``),
+    their SDF clipped to [-max_dist, max_dist] and its gradients; in front of them ``num_queries_on_surface`` points drawn on the
+    surface with value 0 and gradient 0.  ``convert_to_bce_labels`` turns the values into 1 - values / max_dist, as the
+    reference does.  Everything stays on the mesh's device and the random numbers come from that device's global RNG, as in
+    compute_udf_from_mesh."""
+    _check_mesh(vertices, triangles)
+    if not use_cuda:
+        raise RuntimeError("compute_sdf_from_mesh runs only on the GPU through libsurfd_hip.so (no CPU fallback)")
+    queries = input_queries
+    if queries is None:
+        cloud = sample_points_uniformly(vertices, triangles, num_surface_points)
+        queries = sample_points_around_pcd(cloud, queries_stds, num_queries_per_std, coords_range, vertices.device)
+    sdf, gradients = compute_sdf_and_gradients(vertices, triangles, queries)
+    values = sdf.clamp(-max_dist, max_dist)
+    on_surface = sample_points_uniformly(vertices, triangles, num_queries_on_surface)
+    queries = torch.cat([on_surface, queries], dim=0)
+    values = torch.cat([torch.zeros(num_queries_on_surface, device=values.device, dtype=values.dtype), values], dim=0)
+    gradients = torch.cat([torch.zeros(num_queries_on_surface, 3, device=gradients.device, dtype=gradients.dtype), gradients], dim=0)
+    if convert_to_bce_labels:
+        values = 1 - values / max_dist
+    return queries, values, gradients
 
 
 # ---- measurement --------------------------------------------------------------------------------------------------------------
