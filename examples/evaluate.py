@@ -32,6 +32,14 @@ sampling and normalisation, so ``.obj`` and ``.npz`` items are treated alike, as
 nearest neighbours (surfd_amd/cloudnormals.py), and every point's normal is compared with that of its nearest neighbour in the
 other cloud: the mean of |<n, n'>| in both directions, averaged (cloudmetrics.normal_consistency; 1 = the same orientation
 everywhere).  The JSON then records ``normal_consistency`` and ``normals_k`` among its options.
+
+``--paired --self_intersections`` adds, for the GENERATED item of every pair, ``self_intersecting_faces`` (the share of its faces
+with area that pass through another face of the same mesh), ``self_intersecting_pairs`` (how many pairs of faces do) and
+``degenerate_faces`` (faces without area), plus their means (surfd_amd/meshintersect.py: exact integer predicates on the raw
+file's vertices snapped to the finest lattice that holds them; touching and T-junctions count).  ``--paired --collisions`` adds
+``colliding_faces``: the share of the generated item's faces that pass through or touch a face of the reference item, both in
+the frame of the raw files, no normalisation.  Both need meshes: a pair with an ``.npz`` item where a mesh is needed is listed
+under ``skipped``.
 """
 from __future__ import annotations
 
@@ -66,6 +74,8 @@ def parse(argv=None):
     ap.add_argument("--voxel_mode", choices=("surface", "solid", "points"), default="surface")
     ap.add_argument("--normal_consistency", action="store_true", help="--paired: also score the normal consistency of every pair")
     ap.add_argument("--normals_k", type=int, default=16, metavar="K", help="--normal_consistency: neighbours per estimated normal (3 .. 64)")
+    ap.add_argument("--self_intersections", action="store_true", help="--paired: also report the self-intersections of every generated mesh")
+    ap.add_argument("--collisions", action="store_true", help="--paired: also report the faces of every generated mesh that meet its reference mesh")
     ap.add_argument("--output", default="metrics.json")
     return ap.parse_args(argv)
 
@@ -169,7 +179,38 @@ def voxel_scores(gen_items, ref_items, a):
     return items, skipped
 
 
+def _mesh_on_device(path):
+    v, f = load_geometry(path)
+    if f is None or not len(f):
+        return None
+    return v.contiguous().cuda(), f.contiguous().cuda()
+
+
+def intersection_scores(gen_items, ref_items, a):
+    """-> (per-item dict, skipped ids) of --self_intersections and --collisions"""
+    from surfd_amd import meshintersect
+    items, skipped = {}, []
+    for name in gen_items:
+        gen = _mesh_on_device(gen_items[name])
+        ref = _mesh_on_device(ref_items[name]) if a.collisions else None
+        if gen is None or (a.collisions and ref is None):
+            skipped.append(name)
+            continue
+        entry = {}
+        if a.self_intersections:
+            r = meshintersect.self_intersections(*gen, return_pairs=False)
+            entry.update(self_intersecting_faces=r["fraction"], self_intersecting_pairs=r["count"], degenerate_faces=int(r["degenerate"].sum()))
+        if a.collisions:
+            entry["colliding_faces"] = meshintersect.mesh_intersections(*gen, *ref, return_pairs=False)["fraction"]
+        items[name] = entry
+    return items, skipped
+
+
 def run(a):
+    if a.self_intersections and not a.paired:
+        raise SystemExit("--self_intersections scores the generated item of every pair: it needs --paired")
+    if a.collisions and not a.paired:
+        raise SystemExit("--collisions scores pairs: it needs --paired")
     if a.voxel_iou and not a.paired:
         raise SystemExit("--voxel_iou scores pairs: it needs --paired")
     if a.normal_consistency and not a.paired:
@@ -212,6 +253,15 @@ def run(a):
             for i, name in enumerate(gen_items):
                 out["items"][name]["normal_consistency"] = nc[i]
             out["mean"]["normal_consistency"] = float(np.mean(nc, dtype=np.float64))
+        if a.self_intersections or a.collisions:
+            out["options"].update({k: True for k in ("self_intersections", "collisions") if getattr(a, k)})
+            scores, skipped = intersection_scores(gen_items, ref_items, a)
+            for name, s in scores.items():
+                out["items"][name].update(s)
+            for k in ("self_intersecting_faces", "self_intersecting_pairs", "degenerate_faces", "colliding_faces"):
+                if scores and k in next(iter(scores.values())):
+                    out["mean"][k] = float(np.mean([s[k] for s in scores.values()], dtype=np.float64))
+            out["skipped"] = sorted(set(out.get("skipped", [])) | set(skipped))
     else:
         m = cloudmetrics.compute_all_metrics(gen, ref, chunk=a.chunk)
         out["metrics"] = {"mmd_cd": m["mmd_cd"], "cov_cd": m["cov_cd"], "1nna_cd": m["1nna_cd"]}

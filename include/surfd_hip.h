@@ -475,6 +475,51 @@ int surfd_rayscene_count(surfd_rayscene *m, const float *rays, int R, float tmin
 int surfd_rayscene_skipped(surfd_rayscene *m, int64_t *skipped, int64_t *total, surfd_stream s);
 
 /* ------------------------------------------------------------------------------------ */
+/* Intersection tests between triangles: the self-intersections of one mesh and the       */
+/* collisions of two.  No reference counterpart (the reference ships no evaluation code): */
+/* the share of self-intersecting faces is the number that work on meshing unsigned       */
+/* distance fields reports next to the Chamfer distance.  One fp32 snap per vertex, then  */
+/* int64 on int32 differences: exact, no epsilon; results do not depend on any order.     */
+/* ------------------------------------------------------------------------------------ */
+typedef struct surfd_isect surfd_isect;
+#define SURFD_ISECT_BRUTE_FORCE 1     /* flags bit 0: evaluate every pair, no culling */
+#define SURFD_ISECT_COUNT_SKIPPED 2   /* flags bit 1: count the (wave, tile) visits that culling skips (surfd_isect_skipped) */
+/* no reference counterpart; the snapped triangles of one mesh and their exact integer boxes:
+ * vertices[V,3] fp32 and triangles[F,3] int32 on the device (not referenced after the call).  Every coordinate is snapped to
+ * q = rint(x * 2^lattice_log2) in fp32; meshes that are to be compared need the same lattice_log2.  F >= 1, V >= 1,
+ * |lattice_log2| <= 100.  A vertex with a NaN or with |q| > 2^19 is SURFD_ERR_ARG with the number of such vertices in the text;
+ * so is an index outside [0, V), checked on the device and never reported as a fault.  Two vertices with equal snapped
+ * coordinates are the same point whatever their indices, so an unwelded mesh behaves as the welded one.  A triangle whose
+ * normal is (0, 0, 0) after the snap is degenerate: it is flagged and intersects nothing.  host-sync. */
+int surfd_isect_create(const float *vertices, int V, const int32_t *triangles, int F, int lattice_log2, surfd_stream s, surfd_isect **out);
+void surfd_isect_destroy(surfd_isect *m);
+int surfd_isect_num_triangles(const surfd_isect *m);
+/* no reference counterpart; the triangles without area after the snap:
+ * flags[F] (uint8, 1 = degenerate) and count (one int64), both on the device, either may be NULL. */
+int surfd_isect_degenerate(surfd_isect *m, uint8_t *flags, int64_t *count, surfd_stream s);
+/* no reference counterpart; the pairs of triangles of one mesh that have a common point beyond what neighbours share:
+ * the pair test is stated in the header of csrc/meshintersect.hip and restated in tests/meshintersect_ref.py.  Closed triangles:
+ * touching counts.  Two triangles that share one point intersect when they have another common point (a T-junction counts),
+ * two that share an edge only when they are folded flat onto each other, two that share all three points always (duplicates).
+ * hits[F] (int32, zeroed by the call): the number of found pairs each triangle belongs to.  count (one int64): the pairs found.
+ * pairs[capacity] (int64): the keys i << 32 | j, i < j, of the first pairs to claim a slot, in no specified order; count keeps
+ * counting beyond capacity.  All three are device pointers and may be NULL; capacity 0 with pairs NULL is the counting form,
+ * capacity > 0 with pairs NULL is SURFD_ERR_ARG.  Indices are those of the triangles given to create.  hits, count and the set of
+ * pairs do not depend on the order of the triangles (after mapping back), on the launch geometry or on culling: the culled
+ * path equals SURFD_ISECT_BRUTE_FORCE.  Culling works on tiles of 32 and chunks of 256 consecutive triangles; it pays when
+ * these are spatially compact (the Python wrapper sorts by Morton code).  No host sync. */
+int surfd_isect_self(surfd_isect *m, int flags, int32_t *hits, int64_t *pairs, int64_t capacity, int64_t *count, surfd_stream s);
+/* no reference counterpart; the pairs (triangle of a, triangle of b) that have a common point:
+ * the closed test on every pair, no sharing rule (a vertex of a lying exactly on b counts).  hits_a[Fa], hits_b[Fb], pairs (keys
+ * i_a << 32 | j_b), capacity and count as above.  Handles with different lattice_log2, and a == b, are SURFD_ERR_ARG. */
+int surfd_isect_between(surfd_isect *a, surfd_isect *b, int flags, int32_t *hits_a, int32_t *hits_b, int64_t *pairs, int64_t capacity,
+                        int64_t *count, surfd_stream s);
+/* no reference counterpart; a measurement of the culling:
+ * the number of (wave, tile) visits the last call on m (the first handle of a _between) with SURFD_ISECT_COUNT_SKIPPED skipped,
+ * and how many the brute-force path has (waves of 64 consecutive triangles, tiles of 32 partners), to host memory.  host-sync. */
+int surfd_isect_skipped(surfd_isect *m, int64_t *skipped, int64_t *total, surfd_stream s);
+
+/* ------------------------------------------------------------------------------------ */
 /* Point-cloud metrics: nearest neighbours between clouds and the matrix of directed      */
 /* Chamfer means between two sets of clouds.  No reference counterpart (the reference     */
 /* ships no evaluation code): stands for pytorch3d's knn_points(p1, p2, K=1) /            */

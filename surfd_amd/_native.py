@@ -139,6 +139,13 @@ _SIGS = {
     "surfd_rayscene_cast": (C.c_int, [_P, _P, C.c_int, C.c_float, C.c_float, C.c_int, _P, _P, _P, _P, _P]),
     "surfd_rayscene_count": (C.c_int, [_P, _P, C.c_int, C.c_float, C.c_float, C.c_int, _P, _P]),
     "surfd_rayscene_skipped": (C.c_int, [_P, c_i64p, c_i64p, _P]),
+    "surfd_isect_create": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, C.POINTER(_P)]),
+    "surfd_isect_destroy": (None, [_P]),
+    "surfd_isect_num_triangles": (C.c_int, [_P]),
+    "surfd_isect_degenerate": (C.c_int, [_P, _P, _P, _P]),
+    "surfd_isect_self": (C.c_int, [_P, C.c_int, _P, _P, C.c_int64, _P, _P]),
+    "surfd_isect_between": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int64, _P, _P]),
+    "surfd_isect_skipped": (C.c_int, [_P, c_i64p, c_i64p, _P]),
     "surfd_cloud_nn": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "surfd_cloud_nn_matrix": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_float, _P, _P, _P]),
     "surfd_cloud_fps_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
