@@ -22,8 +22,10 @@ the default, ``uniform``, is the behaviour described above and leaves the JSON a
 
 ``--paired --voxel_iou R`` adds the volumetric IoU of every pair on an R^3 grid over ``--voxel_bounds`` (surfd_amd/voxelize.py):
 ``--voxel_mode surface`` (voxels the triangles touch), ``solid`` (parity fill | surface; each item's ``odd_columns`` is recorded,
-0 for a closed mesh) or ``points`` (voxels that hold a vertex of the mesh or a point of the .npz cloud, all of them, no
-subsampling).  Both items of a pair are voxelised in ONE frame: with ``--normalize bbox`` / ``unit_sphere`` the transform of the
+0 for a closed mesh), ``winding`` (voxels whose centre has |generalized winding number| >= 1/2, surfd_amd/winding.py: the fill
+for meshes with small holes, where ``solid`` leaks along every column through a hole; it needs consistently oriented faces) or
+``points`` (voxels that hold a vertex of the mesh or a point of the .npz cloud, all of them, no subsampling).  Both items of a
+pair are voxelised in ONE frame: with ``--normalize bbox`` / ``unit_sphere`` the transform of the
 REFERENCE item (from its vertices or points) is applied to both.  ``.npz`` clouds are scored in ``points`` mode only; elsewhere
 the pair is listed under ``skipped``.
 
@@ -71,7 +73,7 @@ def parse(argv=None):
     ap.add_argument("--init_factor", type=int, default=5, help="--sampling even: uniform candidates per kept point of an .obj item")
     ap.add_argument("--voxel_iou", type=int, default=0, metavar="R", help="--paired: also score volumetric IoU on an R^3 grid (0 = off)")
     ap.add_argument("--voxel_bounds", type=float, nargs=2, default=(-1.0, 1.0), metavar=("LO", "HI"))
-    ap.add_argument("--voxel_mode", choices=("surface", "solid", "points"), default="surface")
+    ap.add_argument("--voxel_mode", choices=("surface", "solid", "winding", "points"), default="surface")
     ap.add_argument("--normal_consistency", action="store_true", help="--paired: also score the normal consistency of every pair")
     ap.add_argument("--normals_k", type=int, default=16, metavar="K", help="--normal_consistency: neighbours per estimated normal (3 .. 64)")
     ap.add_argument("--self_intersections", action="store_true", help="--paired: also report the self-intersections of every generated mesh")
@@ -170,6 +172,8 @@ def voxel_scores(gen_items, ref_items, a):
                 grids.append(voxelize.voxelize_points(v, R, bounds))
             elif a.voxel_mode == "surface":
                 grids.append(voxelize.voxelize_surface(v, f.cuda(), R, bounds))
+            elif a.voxel_mode == "winding":
+                grids.append(voxelize.voxelize_winding(v, f.cuda(), R, bounds))
             else:
                 grid, odd = voxelize.voxelize_solid(v, f.cuda(), R, bounds)
                 grids.append(grid)

@@ -18,7 +18,9 @@ with ``--seed`` before every mesh.
 ``--signed`` writes the signed items of the reference's compute_sdf_from_mesh (AutoEncoder/utils.py:317-363) instead: ``labels``
 is the signed distance clipped to +-0.1, negative inside, ``gradients`` carries its sign, and ``--num_queries_on_surface``
 (10 000) points of the surface with label 0 and gradient 0 come first in ``coords``.  The sign is the parity of the mesh's
-crossings along +z from the query and means something for a closed mesh only.  Without the flag nothing changes.
+crossings along +z from the query and means something for a closed mesh only; ``--signed --sign winding`` takes it from the
+generalized winding number instead (surfd_amd/winding.py: |w| >= 1/2 is inside), which survives small holes and needs
+consistently oriented faces.  The same random numbers are drawn either way.  Without the flags nothing changes.
 """
 from __future__ import annotations
 
@@ -44,6 +46,8 @@ def parse(argv=None):
     ap.add_argument("--max_dist", type=float, default=0.1)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--signed", action="store_true", help="signed distances (negative inside) instead of unsigned ones; closed meshes only")
+    ap.add_argument("--sign", choices=("parity", "winding"), default="parity",
+                    help="with --signed: inside / outside by crossing parity (closed meshes) or by winding number (meshes with holes)")
     ap.add_argument("--num_queries_on_surface", type=int, default=10_000, help="with --signed: on-surface queries put in front")
     return ap.parse_args(argv)
 
@@ -70,7 +74,8 @@ def prepare_one(path, a):
     if a.signed:
         coords, labels, gradients = meshprep.compute_sdf_from_mesh(vd, td, num_surface_points=a.num_surface_points,
                                                                    num_queries_on_surface=a.num_queries_on_surface,
-                                                                   num_queries_per_std=list(a.num_queries_per_std), max_dist=a.max_dist)
+                                                                   num_queries_per_std=list(a.num_queries_per_std), max_dist=a.max_dist,
+                                                                   sign=a.sign)
     else:
         coords, labels, gradients = meshprep.compute_udf_from_mesh(vd, td, num_surface_points=a.num_surface_points,
                                                                    num_queries_per_std=list(a.num_queries_per_std), max_dist=a.max_dist)
@@ -85,6 +90,8 @@ def run(a):
     names = [os.path.splitext(os.path.basename(f))[0] for f in files]
     if len(set(names)) != len(names):
         raise SystemExit(f"item ids must be unique: {names}")
+    if a.sign != "parity" and not a.signed:
+        raise SystemExit("--sign chooses the sign of --signed items: it needs --signed")
     if not torch.cuda.is_available():
         raise SystemExit("preprocess_udfs.py runs on the GPU (no CPU fallback)")
     os.makedirs(a.output_dir, exist_ok=True)

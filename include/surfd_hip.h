@@ -520,6 +520,36 @@ int surfd_isect_between(surfd_isect *a, surfd_isect *b, int flags, int32_t *hits
 int surfd_isect_skipped(surfd_isect *m, int64_t *skipped, int64_t *total, surfd_stream s);
 
 /* ------------------------------------------------------------------------------------ */
+/* Generalized winding numbers of a mesh (Jacobson et al. 2013; libigl's winding_number): */
+/* the signed solid angle of the mesh seen from a point, over 4 pi.  1 inside and 0       */
+/* outside a closed, consistently oriented mesh, and a hole costs only its own solid      */
+/* angle, where the crossing parity above flips a whole cone.  No reference counterpart   */
+/* (the reference takes its signs from open3d's parity).  fp32 in, fp64 arithmetic; the   */
+/* bits of a query's value are a function of the query and the triangle list alone.       */
+/* ------------------------------------------------------------------------------------ */
+typedef struct surfd_winding surfd_winding;
+#define SURFD_WINDING_ONE_SPLIT 1   /* flags bit 0: one workgroup walks the whole triangle range (a test switch; the same bits) */
+/* no reference counterpart; the corners of a mesh's triangles, kept for repeated winding-number calls:
+ * vertices[V,3] fp32 and triangles[F,3] int32 on the device (not referenced after the call); nine fp32 per triangle are kept
+ * in the order given, nothing is sorted.  F >= 1, V >= 1, 3 F < 2^31.  A vertex that holds a NaN or an Inf is SURFD_ERR_ARG with
+ * the number of such vertices in the text; so is an index outside [0, V), checked on the device and never reported as a fault.
+ * Triangles without area are legal and contribute 0.  host-sync. */
+int surfd_winding_create(const float *vertices, int V, const int32_t *triangles, int F, surfd_stream s, surfd_winding **out);
+void surfd_winding_destroy(surfd_winding *m);
+int surfd_winding_num_triangles(const surfd_winding *m);
+/* no reference counterpart; libigl's winding_number(V, F, O):
+ * points[Q,3] fp32 -> w[Q] fp64, both on the device.  Per triangle theta = atan2(det, den) by van Oosterom and Strackee's formula
+ * in fp64, 0 where det == 0 (a point in the triangle's plane or on a vertex, a triangle without area); w = (sum of theta) / (2 pi).
+ * Every operation and the association of the sum (chunks of 256 triangles, groups of 16 chunks, then the groups, each left to
+ * right in the caller's order) are fixed in the header of csrc/winding.hip and restated in tests/winding_ref.py: the bits of
+ * w[n] do not depend on Q, on the other points of the call, on n or on the launch geometry, and differ from the restatement only
+ * through atan2 (|w - w_ref| <= F 2^-50).  w depends on the orientation: a wholly inverted mesh gives -w, one whose faces are not
+ * consistently oriented gives values that mean nothing.  A point that holds a NaN or an Inf gets w = NaN.  0 <= Q < 2^31; Q = 0 is
+ * a no-op.  The handle keeps the call's partial sums in a workspace of its own (at most 256 MiB; the points are walked in slabs):
+ * a handle serves one stream and one host thread at a time. */
+int surfd_winding_eval(surfd_winding *m, const float *points, int64_t Q, int flags, double *w, surfd_stream s);
+
+/* ------------------------------------------------------------------------------------ */
 /* Point-cloud metrics: nearest neighbours between clouds and the matrix of directed      */
 /* Chamfer means between two sets of clouds.  No reference counterpart (the reference     */
 /* ships no evaluation code): stands for pytorch3d's knn_points(p1, p2, K=1) /            */

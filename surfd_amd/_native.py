@@ -146,6 +146,10 @@ _SIGS = {
     "surfd_isect_self": (C.c_int, [_P, C.c_int, _P, _P, C.c_int64, _P, _P]),
     "surfd_isect_between": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int64, _P, _P]),
     "surfd_isect_skipped": (C.c_int, [_P, c_i64p, c_i64p, _P]),
+    "surfd_winding_create": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.POINTER(_P)]),
+    "surfd_winding_destroy": (None, [_P]),
+    "surfd_winding_num_triangles": (C.c_int, [_P]),
+    "surfd_winding_eval": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P]),
     "surfd_cloud_nn": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "surfd_cloud_nn_matrix": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_float, _P, _P, _P]),
     "surfd_cloud_fps_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),

@@ -9,7 +9,8 @@ points or meshes to a mesh.  The counterparts of the reference's open3d-based da
   closest_points, MeshDistance <- open3d RaycastingScene.compute_closest_points (utils.py:228-234)
   compute_udf_and_gradients  <- AutoEncoder/utils.py:223-240
   compute_udf_from_mesh      <- AutoEncoder/utils.py:268-314
-  compute_sdf_and_gradients  <- AutoEncoder/utils.py:242-264             (the sign comes from surfd_amd/raycast.py)
+  compute_sdf_and_gradients  <- AutoEncoder/utils.py:242-264             (the sign comes from surfd_amd/raycast.py, or with
+                                                                          sign="winding" from surfd_amd/winding.py)
   compute_sdf_from_mesh      <- AutoEncoder/utils.py:317-363
   is_inside                  no counterpart: open3d's RaycastingScene.compute_occupancy as a bool
   point_to_mesh_distance, mesh_distance   no counterpart: how far a reconstruction is from the mesh it came from
@@ -309,29 +310,52 @@ def compute_udf_from_mesh(vertices: Tensor, triangles: Tensor, num_surface_point
 
 
 # ---- SDF labels ---------------------------------------------------------------------------------------------------------------
-def _as_scene(vertices, triangles):
+SIGN_METHODS = ("parity", "winding")
+
+
+def _check_method(name: str, method: str) -> None:
+    if method not in SIGN_METHODS:
+        raise ValueError(f"{name} must be 'parity' or 'winding', got {method!r}")
+
+
+def _as_scene(vertices, triangles, method: str = "parity"):
+    """the scene that answers inside / outside by ``method``: a given one of that kind (triangles None), or a new one"""
     from .raycast import RaycastingScene
-    return vertices if isinstance(vertices, RaycastingScene) and triangles is None else RaycastingScene(vertices, triangles)
+    from .winding import WindingScene
+    kind, other = (RaycastingScene, WindingScene) if method == "parity" else (WindingScene, RaycastingScene)
+    if isinstance(vertices, other) and triangles is None:
+        raise TypeError(f"a {other.__name__} cannot answer by {method!r}: pass a {kind.__name__} or the mesh itself")
+    return vertices if isinstance(vertices, kind) and triangles is None else kind(vertices, triangles)
 
 
-def is_inside(vertices: Tensor, triangles: Tensor, points: Tensor, nsamples: int = 1) -> Tensor:
-    """[N] bool: is the point inside the closed mesh.  The parity of the number of crossings of the ray from the point along
-    +z (csrc/raycast.hip); ``nsamples=3`` also asks +x and +y and takes the majority.  On an open mesh the answer means nothing
-    (surfd_amd/raycast.py, ``compute_occupancy(..., return_votes=True)`` tells).  ``vertices`` may be a RaycastingScene
-    (triangles None)."""
+def is_inside(vertices: Tensor, triangles: Tensor, points: Tensor, nsamples: int = 1, method: str = "parity") -> Tensor:
+    """[N] bool: is the point inside the mesh.  ``method="parity"``: the parity of the number of crossings of the ray from the
+    point along +z (csrc/raycast.hip); ``nsamples=3`` also asks +x and +y and takes the majority.  The parity means something on a
+    closed mesh only (surfd_amd/raycast.py, ``compute_occupancy(..., return_votes=True)`` tells); on a mesh with holes use
+    ``method="winding"``: |winding number| >= 1/2 (surfd_amd/winding.py), which needs consistently oriented faces instead and
+    takes no ``nsamples``.  ``vertices`` may be a RaycastingScene, or a WindingScene for "winding" (triangles None)."""
     from .raycast import RaycastingScene, _check_nsamples
-    if not (isinstance(vertices, RaycastingScene) and triangles is None):
+    from .winding import WindingScene
+    _check_method("method", method)
+    if not (isinstance(vertices, (RaycastingScene, WindingScene)) and triangles is None):
         _check_mesh(vertices, triangles, need_cuda=False)      # shapes and dtypes first, the CPU-tensor refusal last
     _check_points("points", points, need_cuda=False)
     _check_nsamples(nsamples)
+    if method == "winding":
+        if nsamples != 1:
+            raise ValueError("nsamples belongs to method='parity': the winding number casts no rays")
+        return _as_scene(vertices, triangles, method).compute_occupancy(points) > 0
     return _as_scene(vertices, triangles).compute_occupancy(points, nsamples) > 0
 
 
-def compute_sdf_and_gradients(vertices: Tensor, triangles: Tensor, queries: Tensor) -> Tuple[Tensor, Tensor]:
+def compute_sdf_and_gradients(vertices: Tensor, triangles: Tensor, queries: Tensor, sign: str = "parity") -> Tuple[Tensor, Tensor]:
     """AutoEncoder/utils.py:242-264: sdf = the distance to the mesh, negative inside (open3d's compute_signed_distance: the
     parity of the crossings along +z), and gradients = sign(sdf) * F.normalize(q - c) for the closest point c of the mesh.  A
-    query on the surface has sdf 0 and a zero gradient.  ``vertices`` may be a RaycastingScene (triangles None)."""
-    scene = _as_scene(vertices, triangles)
+    query on the surface has sdf 0 and a zero gradient.  ``sign="winding"`` takes inside / outside from the winding number
+    instead (surfd_amd/winding.py: for meshes with holes).  ``vertices`` may be a RaycastingScene, or a WindingScene for
+    "winding" (triangles None)."""
+    _check_method("sign", sign)
+    scene = _as_scene(vertices, triangles, sign)
     sdf = scene.compute_signed_distance(queries)
     offset = queries - scene.mesh_distance().closest(queries)[1]
     return sdf, torch.sign(sdf)[:, None] * F.normalize(offset, dim=-1)
@@ -340,12 +364,15 @@ def compute_sdf_and_gradients(vertices: Tensor, triangles: Tensor, queries: Tens
 def compute_sdf_from_mesh(vertices: Tensor, triangles: Tensor, num_surface_points: int = 100_000, num_queries_on_surface: int = 10_000,
                           queries_stds: List[float] = [0.003, 0.01, 0.1], num_queries_per_std: List[int] = [5_000, 4_000, 500, 500],
                           coords_range: Tuple[float, float] = (-1.0, 1.0), max_dist: float = 0.1, convert_to_bce_labels: bool = False,
-                          use_cuda: bool = True, input_queries: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+                          use_cuda: bool = True, input_queries: Optional[Tensor] = None,
+                          sign: str = "parity") -> Tuple[Tensor, Tensor, Tensor]:
     """AutoEncoder/utils.py:317-363 -> (queries, values, gradients): a surface cloud, queries around it (or ``input_queries``),
     their SDF clipped to [-max_dist, max_dist] and its gradients; in front of them ``num_queries_on_surface`` points drawn on the
     surface with value 0 and gradient 0.  ``convert_to_bce_labels`` turns the values into 1 - values / max_dist, as the
     reference does.  Everything stays on the mesh's device and the random numbers come from that device's global RNG, as in
-    compute_udf_from_mesh."""
+    compute_udf_from_mesh.  ``sign``: "parity" (the reference's) or "winding", as in compute_sdf_and_gradients; the same
+    random numbers are drawn either way."""
+    _check_method("sign", sign)
     _check_mesh(vertices, triangles)
     if not use_cuda:
         raise RuntimeError("compute_sdf_from_mesh runs only on the GPU through libsurfd_hip.so (no CPU fallback)")
@@ -353,7 +380,7 @@ def compute_sdf_from_mesh(vertices: Tensor, triangles: Tensor, num_surface_point
     if queries is None:
         cloud = sample_points_uniformly(vertices, triangles, num_surface_points)
         queries = sample_points_around_pcd(cloud, queries_stds, num_queries_per_std, coords_range, vertices.device)
-    sdf, gradients = compute_sdf_and_gradients(vertices, triangles, queries)
+    sdf, gradients = compute_sdf_and_gradients(vertices, triangles, queries, sign)
     values = sdf.clamp(-max_dist, max_dist)
     on_surface = sample_points_uniformly(vertices, triangles, num_queries_on_surface)
     queries = torch.cat([on_surface, queries], dim=0)

@@ -13,7 +13,8 @@ The ray-triangle test runs in csrc/raycast.hip and nowhere else: device tensors 
 (no CPU fallback).  The unsigned part of the signed distance is meshprep.MeshDistance (csrc/meshdist.hip) on the same mesh.
 A ray is ``(ox, oy, oz, dx, dy, dz)``; the direction need not have unit length and ``t`` counts in units of it.  A ray that
 holds a NaN or an Inf, or whose direction is zero, hits nothing.  Inside / outside is the parity of the number of crossings
-and means something on a closed mesh only; on an open one the three axes of ``nsamples=3`` can disagree, which ``votes`` shows.
+and means something on a closed mesh only; on an open one the three axes of ``nsamples=3`` can disagree, which ``votes`` shows,
+and surfd_amd/winding.py (WindingScene: |winding number| >= 1/2) is the answer that survives holes.
 """
 from __future__ import annotations
 

@@ -2,6 +2,7 @@
 
   voxelize_surface   mesh -> the voxels its triangles touch (conservative: the separating-axis test on closed voxels)
   voxelize_solid     mesh -> parity fill along +z (| surface), and the number of columns with an odd crossing total
+  voxelize_winding   mesh -> the voxels whose centre has |winding number| >= threshold (surfd_amd/winding.py): for meshes with holes
   voxelize_points    cloud -> the voxels that hold a point
   VoxelGrid          the bit-packed grid [R, R, W] uint32 (stored as int32), W = ceil(R / 32); .dense() gives bool [R, R, R]
   voxel_iou          paired IoU of grids or packed batches;  voxel_iou_matrix  every a against every b
@@ -9,7 +10,8 @@
 
 No reference counterpart (the reference ships no evaluation code).  The grid is the cube [lo, hi]^3 in R^3 closed voxels, axes
 (x, y, z) = (i, j, k), 1 <= R <= 512.  One fp32 step (the snap to 1/256 voxel), then integers: a grid has the same bits for any
-face order, winding, batch and path.  It runs in the library and nowhere else; CPU tensors are refused (no CPU fallback).
+face order, winding, batch and path (voxelize_winding is the exception: fp64 sums at the voxel centres, and the orientation of
+the faces matters).  It runs in the library and nowhere else; CPU tensors are refused (no CPU fallback).
 """
 from __future__ import annotations
 
@@ -151,7 +153,8 @@ def voxelize_surface(vertices: Tensor, faces: Tensor, resolution: int = 32, boun
 def voxelize_solid(vertices: Tensor, faces: Tensor, resolution: int = 32, bounds=(-1.0, 1.0), out: Optional[VoxelGrid] = None,
                    path: Optional[str] = None, include_surface: bool = True, return_counts: bool = False):
     """Parity fill along +z, OR-ed with the surface voxels when ``include_surface``.  -> (grid, odd_columns): the number of
-    columns whose crossing total is odd, 0 for a closed snapped mesh (the fill of an open mesh leaks along those columns).
+    columns whose crossing total is odd, 0 for a closed snapped mesh (the fill of an open mesh leaks along those columns;
+    voxelize_winding fills such a mesh without the leak).
     With ``return_counts`` the second value is a dict with 'odd_columns' and 'dropped'."""
     R, bounds = _check_grid(resolution, bounds)
     flags = _flags(path)
@@ -165,6 +168,27 @@ def voxelize_solid(vertices: Tensor, faces: Tensor, resolution: int = 32, bounds
                                           N.stream()))
     c = counts.tolist()
     return grid, ({"odd_columns": c[0], "dropped": c[1]} if return_counts else c[0])
+
+
+def voxelize_winding(vertices: Tensor, faces: Tensor, resolution: int = 32, bounds=(-1.0, 1.0), threshold: float = 0.5) -> VoxelGrid:
+    """The voxels whose centre lies inside the mesh by its generalized winding number: |w| >= ``threshold`` (csrc/winding.hip
+    through surfd_amd/winding.py).  A hole costs only its own solid angle, so a mesh with small holes fills as the closed one
+    does, where voxelize_solid leaks along every column through a hole.  The centres are
+    lo + (arange(R, dtype=float32) + 0.5) * ((hi - lo) / R), built in torch on the device; R^3 x F terms, nothing is culled.  The
+    faces must be consistently oriented (all outwards or all inwards); surface voxels are not OR-ed in.  Indices outside
+    [0, V) and vertices that are not finite are refused, not dropped."""
+    from .winding import WindingScene, _check_threshold
+    R, bounds = _check_grid(resolution, bounds)
+    threshold = _check_threshold(threshold)
+    if not isinstance(vertices, Tensor) or not isinstance(faces, Tensor):
+        raise TypeError("vertices and faces must be tensors")
+    scene = WindingScene(vertices, faces)
+    lo, hi = bounds
+    with torch.cuda.device(scene.device):
+        c = lo + (torch.arange(R, dtype=torch.float32, device=scene.device) + 0.5) * ((hi - lo) / R)
+        centres = torch.stack(torch.meshgrid(c, c, c, indexing="ij"), dim=-1).reshape(-1, 3)
+        occ = scene.compute_occupancy(centres, threshold)
+    return VoxelGrid.from_dense(occ.reshape(R, R, R) > 0, bounds)
 
 
 def voxelize_points(points: Tensor, resolution: int = 32, bounds=(-1.0, 1.0), out: Optional[VoxelGrid] = None, return_counts: bool = False):

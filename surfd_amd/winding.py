@@ -1,0 +1,119 @@
+"""Generalized winding numbers of a triangle mesh on the MI355X path: inside / outside that survives holes.
+
+  WindingScene.winding_number          <- libigl's winding_number(V, F, O) (Jacobson et al. 2013)
+  WindingScene.compute_occupancy       the role of open3d's RaycastingScene.compute_occupancy, decided by |w| >= threshold
+  WindingScene.compute_signed_distance the role of RaycastingScene.compute_signed_distance, signed by the same rule
+  winding_number                       the one-shot form
+
+w(p) is the signed solid angle of the mesh seen from p over 4 pi: 1 inside and 0 outside a closed mesh whose faces are oriented
+outwards, and a hole costs only its own solid angle, where the parity of ray crossings (surfd_amd/raycast.py, voxelize_solid)
+flips a whole cone or column behind every missing face.  The sum runs in csrc/winding.hip and nowhere else: device tensors in,
+device tensors out, CPU tensors are refused (no CPU fallback).  Every triangle contributes to every query, so nothing is sorted
+or culled: Q x F terms.
+
+w depends on the ORIENTATION of the faces.  A wholly inverted mesh gives -w, which ``|w| >= threshold`` forgives; a mesh whose
+faces are not consistently oriented (tests/raycast_ref.cube_flipped) gives values between about -0.67 and 0.66 that mean nothing,
+while its crossing parity is fine: use RaycastingScene there.  Re-orienting such a mesh is not done here.
+The fp64 bits of a query's w do not depend on the other queries of the call, on its position, or on the launch geometry.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Tuple, Union
+
+import torch
+from torch import Tensor
+
+from . import _native as N
+from .meshprep import MeshDistance, _check_mesh, _check_points
+
+ONE_SPLIT = 1                   # SURFD_WINDING_ONE_SPLIT
+
+
+def _check_threshold(threshold: float) -> float:
+    threshold = float(threshold)
+    if not 0.0 < threshold < 1.0:
+        raise ValueError(f"threshold must lie in (0, 1), got {threshold}")
+    return threshold
+
+
+class WindingScene:
+    """One mesh, kept for repeated calls.  The triangles reach the library in the caller's order.  Host syncs: the constructor
+    checks the vertices and the index range and the library's create reads its flags; the calls themselves do not sync.  One
+    stream at a time per object: the library keeps its partial sums in a workspace of the handle."""
+
+    def __init__(self, vertices: Tensor, triangles: Tensor):
+        _check_mesh(vertices, triangles, need_cuda=False)          # shapes and dtypes first, the CPU-tensor refusal last
+        _check_mesh(vertices, triangles)
+        if not bool(torch.isfinite(vertices).all()):
+            raise ValueError("vertices contain NaN or Inf")
+        self._handle = None
+        self._distance: Optional[MeshDistance] = None
+        v = vertices.contiguous()
+        t = triangles.long()
+        if int(t.min()) < 0 or int(t.max()) >= v.shape[0]:
+            raise ValueError(f"triangles name vertices outside [0, {v.shape[0]})")
+        self.device = v.device
+        self.vertices, self.triangles = v, t
+        ts = t.to(torch.int32).contiguous()
+        self.num_triangles = int(t.shape[0])
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            N.check(N.lib().surfd_winding_create(N.ptr(v), v.shape[0], N.ptr(ts), ts.shape[0], N.stream(), C.byref(h)))
+        self._handle = h
+        assert N.lib().surfd_winding_num_triangles(h) == self.num_triangles
+
+    def _points(self, points: Tensor) -> Tensor:
+        _check_points("points", points, need_cuda=False)
+        _check_points("points", points)
+        if points.device != self.device:
+            raise RuntimeError(f"points are on {points.device}, the mesh is on {self.device}")
+        return points.contiguous()
+
+    def winding_number(self, points: Tensor, one_split: bool = False) -> Tensor:
+        """points [N, 3] float32 -> [N] float64.  A point that holds a NaN or an Inf gets NaN.  ``one_split`` is a test switch:
+        one workgroup walks all triangles for its queries (the same bits, slower when N is small)."""
+        p = self._points(points)
+        w = torch.empty(p.shape[0], device=self.device, dtype=torch.float64)
+        if p.shape[0] == 0:
+            return w
+        with torch.cuda.device(self.device):
+            N.check(N.lib().surfd_winding_eval(self._handle, N.ptr(p), p.shape[0], ONE_SPLIT if one_split else 0, N.ptr(w), N.stream()))
+        return w
+
+    def compute_occupancy(self, points: Tensor, threshold: float = 0.5,
+                          return_winding: bool = False) -> Union[Tensor, Tuple[Tensor, Tensor]]:
+        """points [N, 3] -> [N] float32, 1 where |w| >= threshold and 0 elsewhere (a NaN point is outside).  The absolute value
+        makes a wholly inverted mesh work; inconsistently oriented faces do not (see the module's text).  ``return_winding``
+        adds w [N] float64."""
+        threshold = _check_threshold(threshold)
+        w = self.winding_number(points)
+        occ = (w.abs() >= threshold).float()
+        return (occ, w) if return_winding else occ
+
+    def mesh_distance(self) -> MeshDistance:
+        """the closest-point structure of the same mesh (made on first use)"""
+        if self._distance is None:
+            self._distance = MeshDistance(self.vertices, self.triangles)
+        return self._distance
+
+    def compute_signed_distance(self, points: Tensor, threshold: float = 0.5) -> Tensor:
+        """points [N, 3] -> [N] float32: the distance to the mesh (meshprep.MeshDistance), negative where compute_occupancy
+        says occupied"""
+        occ = self.compute_occupancy(points, threshold)
+        dist = self.mesh_distance().closest(points)[0]
+        return torch.where(occ > 0, -dist, dist)
+
+    def __del__(self):
+        try:
+            if self._handle is not None:
+                N.lib().surfd_winding_destroy(self._handle)
+        except Exception:                                       # interpreter shutdown
+            pass
+
+
+def winding_number(vertices: Tensor, triangles: Tensor, points: Tensor) -> Tensor:
+    """[N] float64: the winding number of the mesh at every point (one WindingScene, one call)"""
+    _check_mesh(vertices, triangles, need_cuda=False)
+    _check_points("points", points, need_cuda=False)
+    return WindingScene(vertices, triangles).winding_number(points)
