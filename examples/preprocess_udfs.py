@@ -21,6 +21,10 @@ is the signed distance clipped to +-0.1, negative inside, ``gradients`` carries 
 crossings along +z from the query and means something for a closed mesh only; ``--signed --sign winding`` takes it from the
 generalized winding number instead (surfd_amd/winding.py: |w| >= 1/2 is inside), which survives small holes and needs
 consistently oriented faces.  The same random numbers are drawn either way.  Without the flags nothing changes.
+
+``--accel bvh`` searches the mesh through the box hierarchy of csrc/meshbvh.hip instead of its tiles: the files are the same
+bytes.  The rays behind the sign of ``--signed`` go 4 to 24 times faster; the closest-point search does not yet (DESIGN.md
+section 8.11 has the measurements).
 """
 from __future__ import annotations
 
@@ -49,6 +53,8 @@ def parse(argv=None):
     ap.add_argument("--sign", choices=("parity", "winding"), default="parity",
                     help="with --signed: inside / outside by crossing parity (closed meshes) or by winding number (meshes with holes)")
     ap.add_argument("--num_queries_on_surface", type=int, default=10_000, help="with --signed: on-surface queries put in front")
+    ap.add_argument("--accel", choices=("tiles", "bvh"), default="tiles",
+                    help="how the mesh is searched: its tiles, or the box hierarchy (the same bytes; faster for the rays of --signed)")
     return ap.parse_args(argv)
 
 
@@ -75,10 +81,11 @@ def prepare_one(path, a):
         coords, labels, gradients = meshprep.compute_sdf_from_mesh(vd, td, num_surface_points=a.num_surface_points,
                                                                    num_queries_on_surface=a.num_queries_on_surface,
                                                                    num_queries_per_std=list(a.num_queries_per_std), max_dist=a.max_dist,
-                                                                   sign=a.sign)
+                                                                   sign=a.sign, **({"accel": a.accel} if a.accel != "tiles" else {}))
     else:
         coords, labels, gradients = meshprep.compute_udf_from_mesh(vd, td, num_surface_points=a.num_surface_points,
-                                                                   num_queries_per_std=list(a.num_queries_per_std), max_dist=a.max_dist)
+                                                                   num_queries_per_std=list(a.num_queries_per_std), max_dist=a.max_dist,
+                                                                   **({"accel": a.accel} if a.accel != "tiles" else {}))
     return dict(vertices=v.numpy(), triangles=t.numpy(), pcd=pcd.cpu().numpy(), coords=coords.cpu().numpy(),
                 labels=labels.cpu().numpy(), gradients=gradients.cpu().numpy())
 

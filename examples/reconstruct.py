@@ -50,6 +50,9 @@ def parse(argv=None):
     ap.add_argument("--size_latent", type=int, default=32, help="latent size of the --synthetic checkpoint")
     ap.add_argument("--metrics", action="store_true",
                     help="for inputs that carry 'vertices' / 'triangles' (examples/preprocess_udfs.py): write metrics.json")
+    ap.add_argument("--accel", choices=("tiles", "bvh"), default="tiles",
+                    help="--metrics: how mesh_distance searches the meshes: their tiles, or the box hierarchy of csrc/meshbvh.hip "
+                         "(the same numbers; not faster yet for closest points: DESIGN.md section 8.11)")
     ap.add_argument("--mesh_quality", action="store_true",
                     help="--metrics: also record self_intersecting_faces, the share of the reconstruction's faces that pass through another")
     ap.add_argument("--preview", type=int, default=0, metavar="N",
@@ -121,13 +124,14 @@ def load_models(ae_dir):
     return encoder, decoder.cuda().eval(), size_latent
 
 
-def item_metrics(path, verts, faces, field, seed, mesh_quality=False):
+def item_metrics(path, verts, faces, field, seed, mesh_quality=False, accel="tiles"):
     """what --metrics records for one item, or None where the input carries no mesh: mesh_distance between the reconstruction
     and the original; the IoU of their surface voxels on a 64^3 grid over [-1, 1]^3 (voxel_iou_surface_64); the normal
     consistency of 16 Ki = 16 384 surface points per mesh with their face normals, unsigned (normal_consistency_16: the number
     counts samples, no neighbourhood size enters); and, where the file has 'coords' / 'labels', the mean absolute error of the
     decoder's UDF at those queries.  ``mesh_quality`` adds self_intersecting_faces: the share of the reconstruction's faces with
-    area that pass through or touch another of its faces beyond what neighbours share (surfd_amd.meshintersect)"""
+    area that pass through or touch another of its faces beyond what neighbours share (surfd_amd.meshintersect).  ``accel``:
+    how mesh_distance searches the two meshes ("tiles" or "bvh": the same numbers)"""
     from surfd_amd import meshprep
     if not path.endswith(".npz"):
         return None
@@ -141,7 +145,7 @@ def item_metrics(path, verts, faces, field, seed, mesh_quality=False):
     if len(faces):
         g = torch.Generator(device="cuda").manual_seed(seed)
         rv, rt = torch.from_numpy(np.ascontiguousarray(verts, dtype=np.float32)).cuda(), torch.from_numpy(np.ascontiguousarray(faces).astype(np.int64)).cuda()
-        d = meshprep.mesh_distance(rv, rt, ov, ot, generator=g)
+        d = meshprep.mesh_distance(rv, rt, ov, ot, generator=g, **({"accel": accel} if accel != "tiles" else {}))
         out.update(reconstruction_to_original=d["d12"], original_to_reconstruction=d["d21"], mesh_distance=d["sum"])
         from surfd_amd import voxelize
         out["voxel_iou_surface_64"] = float(voxelize.voxel_iou(voxelize.voxelize_surface(rv, rt, 64), voxelize.voxelize_surface(ov, ot, 64)))
@@ -163,6 +167,8 @@ def main(argv=None):
 
 
 def run(a):
+    if a.accel != "tiles" and not a.metrics:
+        raise SystemExit("--accel chooses how --metrics measures: it needs --metrics")
     if a.mesh_quality and not a.metrics:
         raise SystemExit("--mesh_quality adds to metrics.json: it needs --metrics")
     os.makedirs(a.output_dir, exist_ok=True)
@@ -218,7 +224,7 @@ def run(a):
                                        torch.as_tensor(np.ascontiguousarray(faces, dtype=np.int64)).reshape(-1, 3).cuda(), n_views=a.preview, size=512)
             written += render.save_views(a.output_dir, os.path.splitext(os.path.basename(path))[0], views)
         if a.metrics:
-            m = item_metrics(files[k], verts, faces, field, a.seed, a.mesh_quality)
+            m = item_metrics(files[k], verts, faces, field, a.seed, a.mesh_quality, a.accel)
             if m is not None:
                 metrics[item] = m
     if a.metrics:

@@ -431,6 +431,32 @@ int surfd_mesh_num_triangles(const surfd_mesh *m);
 int surfd_mesh_closest(const surfd_mesh *m, const float *queries, int Q, int flags, float *dist, float *closest, int32_t *tri,
                        int64_t *skipped_tiles, surfd_stream s);
 
+/* no reference counterpart; an opt-in hierarchy of boxes over the handle's triangles:
+ * csrc/meshbvh.hip (63-bit Morton codes of the centroids, a stable radix sort, leaves of 4 triangles, an implicit 4-ary tree
+ * without pointers), built on the device from the records the handle holds.  Idempotent.  host-sync. */
+int surfd_mesh_build_bvh(surfd_mesh *m, surfd_stream s);
+#define SURFD_MESH_COUNT_VISITS 2  /* flags bit 1 of surfd_mesh_closest_bvh: count box tests and pair tests (surfd_mesh_visits) */
+/* RaycastingScene.compute_closest_points (utils.py:228-234) through the hierarchy:
+ * surfd_mesh_closest with every query walking the tree on its own instead of the tiles; the same arguments, the same outputs bit
+ * for bit (the hierarchy decides which pairs are tested, never a pair's result or the order that picks the winner).  flags:
+ * SURFD_MESH_BRUTE_FORCE wins and is surfd_mesh_closest's brute-force path; SURFD_MESH_COUNT_VISITS.  Without
+ * surfd_mesh_build_bvh: SURFD_ERR_STATE, never a fallback.  skipped_tiles (nullable) is set to 0: there are no tiles. */
+int surfd_mesh_closest_bvh(const surfd_mesh *m, const float *queries, int Q, int flags, float *dist, float *closest, int32_t *tri,
+                           int64_t *skipped_tiles, surfd_stream s);
+/* no reference counterpart; a measurement of the hierarchy:
+ * the box tests and pair tests, summed over the lanes, of the last call with SURFD_MESH_COUNT_VISITS, to host memory.
+ * host-sync.  Measurement only. */
+int surfd_mesh_visits(const surfd_mesh *m, int64_t *box_tests, int64_t *pair_tests, surfd_stream s);
+/* no reference counterpart; the hierarchy's shape, for tests:
+ * the number of levels, leaves and nodes, and the first min(capacity, levels) level sizes, level 0 (the nodes above the leaves)
+ * first; any pointer may be NULL.  SURFD_ERR_STATE without a build. */
+int surfd_mesh_bvh_info(const surfd_mesh *m, int *levels, int *leaves, int *nodes, int32_t *level_sizes, int capacity);
+/* no reference counterpart; the hierarchy's content, for tests:
+ * boxes[nodes,6,4] fp32 (lo.x, lo.y, lo.z, hi.x, hi.y, hi.z of a node's 4 children; an absent child is lo = +inf, hi = -inf;
+ * level k starts at the sum of the sizes below it) and leaf_triangles[leaves,4] int32 (indices into the triangles given to
+ * create, -1 past the end) are copied to the caller's buffers (device or host; either may be NULL).  host-sync. */
+int surfd_mesh_bvh_read(const surfd_mesh *m, float *boxes, int32_t *leaf_triangles, surfd_stream s);
+
 /* ------------------------------------------------------------------------------------ */
 /* Ray casting on a mesh: first hit per ray and the number of triangles a ray meets.      */
 /* Stands for the ray half of open3d's RaycastingScene (cast_rays, count_intersections)   */
@@ -441,6 +467,8 @@ int surfd_mesh_closest(const surfd_mesh *m, const float *queries, int Q, int fla
 typedef struct surfd_rayscene surfd_rayscene;
 #define SURFD_RAY_BRUTE_FORCE 1     /* flags bit 0: test every (ray, triangle) pair, no culling */
 #define SURFD_RAY_COUNT_SKIPPED 2   /* flags bit 1: count the (wave, tile) visits that culling skips (surfd_rayscene_skipped) */
+#define SURFD_RAY_BVH 4             /* flags bit 2: walk the hierarchy of surfd_rayscene_build_bvh instead of the tiles */
+#define SURFD_RAY_COUNT_VISITS 8    /* flags bit 3: with SURFD_RAY_BVH, count box tests and pair tests (surfd_rayscene_visits) */
 /* vertices[V,3] fp32 and triangles[F,3] int32 on the device -> the triangles' corners and per-tile bounding spheres (the
  * inputs are not referenced after the call).  F >= 1; every index must lie in [0, V): checked on the device and reported as
  * SURFD_ERR_ARG, never as a fault.  Degenerate triangles are legal and are never hit.  host-sync. */
@@ -473,6 +501,22 @@ int surfd_rayscene_count(surfd_rayscene *m, const float *rays, int R, float tmin
  * the number of (wave, tile) visits the last call with SURFD_RAY_COUNT_SKIPPED skipped, and how many it had in all (waves of 64
  * consecutive rays, tiles of 32 consecutive triangles), to host memory.  host-sync.  Measurement only. */
 int surfd_rayscene_skipped(surfd_rayscene *m, int64_t *skipped, int64_t *total, surfd_stream s);
+
+/* no reference counterpart; an opt-in hierarchy of boxes over the handle's triangles:
+ * the same as surfd_mesh_build_bvh's.  Idempotent.  host-sync.  Afterwards SURFD_RAY_BVH on surfd_rayscene_cast / _count makes every ray walk the tree on its own instead of the
+ * tiles: the same outputs bit for bit.  SURFD_RAY_BVH without a build is SURFD_ERR_STATE, never a fallback;
+ * SURFD_RAY_BRUTE_FORCE wins over it. */
+int surfd_rayscene_build_bvh(surfd_rayscene *m, surfd_stream s);
+/* no reference counterpart; a measurement of the hierarchy:
+ * the box tests and pair tests, summed over the lanes, of the last call with SURFD_RAY_COUNT_VISITS, to host memory.
+ * host-sync.  Measurement only. */
+int surfd_rayscene_visits(surfd_rayscene *m, int64_t *box_tests, int64_t *pair_tests, surfd_stream s);
+/* no reference counterpart; the hierarchy's shape, for tests:
+ * as surfd_mesh_bvh_info */
+int surfd_rayscene_bvh_info(const surfd_rayscene *m, int *levels, int *leaves, int *nodes, int32_t *level_sizes, int capacity);
+/* no reference counterpart; the hierarchy's content, for tests:
+ * as surfd_mesh_bvh_read */
+int surfd_rayscene_bvh_read(const surfd_rayscene *m, float *boxes, int32_t *leaf_triangles, surfd_stream s);
 
 /* ------------------------------------------------------------------------------------ */
 /* Intersection tests between triangles: the self-intersections of one mesh and the       */

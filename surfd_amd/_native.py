@@ -133,12 +133,21 @@ _SIGS = {
     "surfd_mesh_destroy": (None, [_P]),
     "surfd_mesh_num_triangles": (C.c_int, [_P]),
     "surfd_mesh_closest": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "surfd_mesh_build_bvh": (C.c_int, [_P, _P]),
+    "surfd_mesh_closest_bvh": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "surfd_mesh_visits": (C.c_int, [_P, c_i64p, c_i64p, _P]),
+    "surfd_mesh_bvh_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int32), C.c_int]),
+    "surfd_mesh_bvh_read": (C.c_int, [_P, _P, _P, _P]),
     "surfd_rayscene_create": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.POINTER(_P)]),
     "surfd_rayscene_destroy": (None, [_P]),
     "surfd_rayscene_num_triangles": (C.c_int, [_P]),
     "surfd_rayscene_cast": (C.c_int, [_P, _P, C.c_int, C.c_float, C.c_float, C.c_int, _P, _P, _P, _P, _P]),
     "surfd_rayscene_count": (C.c_int, [_P, _P, C.c_int, C.c_float, C.c_float, C.c_int, _P, _P]),
     "surfd_rayscene_skipped": (C.c_int, [_P, c_i64p, c_i64p, _P]),
+    "surfd_rayscene_build_bvh": (C.c_int, [_P, _P]),
+    "surfd_rayscene_visits": (C.c_int, [_P, c_i64p, c_i64p, _P]),
+    "surfd_rayscene_bvh_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int32), C.c_int]),
+    "surfd_rayscene_bvh_read": (C.c_int, [_P, _P, _P, _P]),
     "surfd_isect_create": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, C.POINTER(_P)]),
     "surfd_isect_destroy": (None, [_P]),
     "surfd_isect_num_triangles": (C.c_int, [_P]),

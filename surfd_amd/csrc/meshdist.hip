@@ -51,11 +51,32 @@
 // The first bound of a wave comes from the tile whose sphere centre is nearest to the wave's first query, visited before the
 // ascending pass (a tile visited twice changes nothing: the order above is a total order on pairs).
 //
+// Hierarchy (surfd_mesh_closest_bvh, the bvm_ kernel; built by meshbvh.hip, whose header describes the tree and how a leaf's box
+// is widened so that it holds the triangle md_pair() sees: a, a + ab, a + ac in real numbers).  bvm_closest_kernel: one query
+// per lane, every lane walks the implicit tree on its own (meshbvh_layout.h; no stack, no private array), one split, then
+// md_finish_kernel with S = 1.  A leaf's triangles go through md_pair() with the handle's own index: keys and ties as above.
+// First bound: the lane descends from the root to one leaf, at every node into the child whose box is nearest (the lowest on
+// a tie), and takes that leaf's triangles; then it walks the whole tree with the children in ascending order.  The result
+// cannot depend on either choice: the winner is the minimum of a total order over the pairs tested, a pair tested twice
+// changes nothing, and the bound below never skips a pair that could be that minimum.
+// Box bound (bvm_cannot_improve), from md_cannot_improve's analysis, u = 2^-24.  Dn = the distance from q to the box, Df = the
+// distance to its farthest corner, d = sqrt(best2) of the lane.  Every point of a triangle in the box is at least Dn away, its
+// vertices at most Df, its edges no longer than 2 Df.  md_pair's roundings as listed above (r_b and a segment's difference
+// vector 2u (|r| + |e|) per component, the squared length 3u, the plane accepted 5u |r| outside with h off by 4u |r|), with
+// |r| <= Df and |e| <= 2 Df, put the computed distance of a pair at or above Dn - 62u Df (the 10u (D + 5r) of the sphere bound
+// with D + r <= Df, r <= Df, and 2u Df for a box edge that the widening moved).  A box can be skipped when Dn > d + 62u Df;
+// squared, with d Df <= max(d^2, Df^2), that follows from Dn^2 > d^2 + 125u max(d^2, Df^2).  In fp32 D2 = Dn^2 and F2 = Df^2
+// (three subtractions, a max, one product, two fmaf each) are within 6u relative, the right-hand side within 3u:
+// the test D2 > fl(best2 + 2^-16 fl(best2 + F2)) has 256u (best2 + F2) where 125u + 6u + 3u of it are needed: a factor 1.9 in
+// hand, and strict, so a pair that ties the best distance is never skipped.  best2 = +inf (nothing found yet), a box of
+// (-inf, +inf)^3 (D2 = 0) and a NaN anywhere make the compare false: no skip.
+//
 // Hazards: the only LDS reuse is the record chunk of md_closest_kernel, bracketed by a barrier on both sides (__syncthreads_or
 // in front of the staging stores, __syncthreads() behind them); cross-lane values move with __shfl_xor / __all only.  The only
 // atomics are integer ones (the skipped-tile count, one per wave that holds a query, and the bad-index flag).  A handle's
 // partial-result workspace is shared by its calls: one stream at a time per handle.
 #include "common.h"
+#include "meshbvh.h"
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -304,6 +325,107 @@ __global__ __launch_bounds__(256) void md_closest_kernel(const float4 *__restric
     }
 }
 
+// squared distances from q to the nearest point (D2) and to the farthest corner (F2) of a box
+__device__ __forceinline__ void bvm_box(float lox, float loy, float loz, float hix, float hiy, float hiz, float qx, float qy, float qz,
+                                        float &D2, float &F2) {
+    const float ax = lox - qx, ay = loy - qy, az = loz - qz, bx = qx - hix, by = qy - hiy, bz = qz - hiz;
+    const float nx = fmaxf(fmaxf(ax, bx), 0.f), ny = fmaxf(fmaxf(ay, by), 0.f), nz = fmaxf(fmaxf(az, bz), 0.f);
+    const float fx = fmaxf(fabsf(ax), fabsf(bx)), fy = fmaxf(fabsf(ay), fabsf(by)), fz = fmaxf(fabsf(az), fabsf(bz));
+    D2 = md_dot(nx, ny, nz, nx, ny, nz);
+    F2 = md_dot(fx, fy, fz, fx, fy, fz);
+}
+
+// true where no triangle inside the box can beat or tie the lane's best squared distance (header: box bound)
+__device__ __forceinline__ bool bvm_cannot_improve(float D2, float F2, float best2) {
+    return D2 > fmaf(best2 + F2, MD_CULL_MARGIN, best2);
+}
+
+// the children of a node that the lane has to enter: bit c for child c
+__device__ __forceinline__ unsigned bvm_children(const BvhNode &n, float qx, float qy, float qz, float best2, unsigned &nbox) {
+    unsigned m = 0;
+#pragma unroll
+    for (int c = 0; c < BVH_W; ++c) {
+        const float lox = bvh_comp(n.lox, c), hix = bvh_comp(n.hix, c);
+        const bool there = bvh_child_exists(lox, hix);
+        float D2, F2;
+        bvm_box(lox, bvh_comp(n.loy, c), bvh_comp(n.loz, c), hix, bvh_comp(n.hiy, c), bvh_comp(n.hiz, c), qx, qy, qz, D2, F2);
+        nbox += there ? 1u : 0u;
+        m |= (there && !bvm_cannot_improve(D2, F2, best2)) ? (1u << c) : 0u;
+    }
+    return m;
+}
+
+// the existing child whose box is nearest to q (the lowest on a tie; child 0 of a node always exists)
+__device__ __forceinline__ unsigned bvm_nearest(const BvhNode &n, float qx, float qy, float qz, unsigned &nbox) {
+    unsigned best = 0;
+    float bd = INFINITY;
+#pragma unroll
+    for (int c = 0; c < BVH_W; ++c) {
+        const float lox = bvh_comp(n.lox, c), hix = bvh_comp(n.hix, c);
+        const bool there = bvh_child_exists(lox, hix);
+        float D2, F2;
+        bvm_box(lox, bvh_comp(n.loy, c), bvh_comp(n.loz, c), hix, bvh_comp(n.hiy, c), bvh_comp(n.hiz, c), qx, qy, qz, D2, F2);
+        nbox += there ? 1u : 0u;
+        const bool take = there && D2 < bd;
+        bd = take ? D2 : bd;
+        best = take ? (unsigned)c : best;
+    }
+    return best;
+}
+
+__device__ __forceinline__ void bvm_leaf(const float4 *__restrict__ rec, int F, int4 ids, float qx, float qy, float qz, float &best, int &idx,
+                                         unsigned &npair) {
+    float dx, dy, dz;
+#pragma unroll
+    for (int i = 0; i < BVH_L; ++i) {
+        const int f = bvh_comp(ids, i);
+        if ((unsigned)f >= (unsigned)F) continue;                  // -1: the last leaf has fewer than L triangles
+        md_take(md_pair(md_load(rec + (long)f * MD_REC4), qx, qy, qz, dx, dy, dz), f, best, idx);
+        npair += 1;
+    }
+}
+
+// queries [Q, 3]; results pd / pi [Q] (one split).  visits: null, or two counters (box tests, pair tests)
+__global__ __launch_bounds__(256) void bvm_closest_kernel(const float4 *__restrict__ rec, int F, const float4 *__restrict__ boxes,
+                                                          const int4 *__restrict__ leaf_tri, const int *__restrict__ level_off, int top,
+                                                          int nleaf, const float *__restrict__ queries, int Q, float *__restrict__ pd,
+                                                          int *__restrict__ pi, unsigned long long *__restrict__ visits) {
+    __shared__ int off[BVH_MAX_LEVELS];
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (tid < BVH_MAX_LEVELS) off[tid] = level_off[tid];
+    __syncthreads();
+    const int n = blockIdx.x * MD_CHUNK + tid;
+    const int nq = n < Q ? n : Q - 1;
+    const float qx = queries[(long)nq * 3], qy = queries[(long)nq * 3 + 1], qz = queries[(long)nq * 3 + 2];
+    float best = INFINITY;
+    int idx = INT_MAX;
+    unsigned nbox = 0, npair = 0;
+    // the first bound: down to one leaf through the nearest boxes
+    unsigned node = 0;
+#pragma unroll 1
+    for (int level = top; level >= 0; --level) node = node * BVH_W + bvm_nearest(bvh_load(boxes, off[level], node), qx, qy, qz, nbox);
+    if (node < (unsigned)nleaf) bvm_leaf(rec, F, leaf_tri[node], qx, qy, qz, best, idx, npair);
+    // the whole tree, children in ascending order
+    int level = top;
+    unsigned child = 0;
+    node = 0;
+    unsigned long long mask = bvh_mask_bits(top, bvm_children(bvh_load(boxes, off[top], 0), qx, qy, qz, best, nbox));
+#pragma unroll 1
+    while (bvh_next(top, level, node, mask, child)) {
+        if (level > 0) {
+            bvh_enter(level, node, child);
+            mask |= bvh_mask_bits(level, bvm_children(bvh_load(boxes, off[level], node), qx, qy, qz, best, nbox));
+        } else {
+            bvm_leaf(rec, F, leaf_tri[child], qx, qy, qz, best, idx, npair);
+        }
+    }
+    if (n < Q) {
+        pd[n] = best;
+        pi[n] = idx;
+    }
+    if (visits && n - lane < Q) bvh_count_visits(visits, n < Q ? nbox : 0u, n < Q ? npair : 0u, lane);
+}
+
 // the minimum of the S partial results of query n under (squared distance, index), then the pair test on the winner
 __global__ __launch_bounds__(256) void md_finish_kernel(const float4 *__restrict__ rec, int F, const float *__restrict__ queries, int Q,
                                                         const float *__restrict__ pd, const int *__restrict__ pi, int S,
@@ -337,6 +459,7 @@ struct surfd_mesh {
     float4 *chunk_sph = nullptr;      // [nchunk]
     mutable void *ws = nullptr;       // partial results of surfd_mesh_closest (grows)
     mutable size_t ws_bytes = 0;
+    MeshBvh bvh;                      // the hierarchy of surfd_mesh_build_bvh (meshbvh.hip)
 };
 
 static int md_ws(const surfd_mesh *m, size_t bytes, hipStream_t st) {
@@ -404,6 +527,7 @@ int surfd_mesh_create(const float *vertices, int V, const int32_t *triangles, in
 void surfd_mesh_destroy(surfd_mesh *m) {
     if (!m) return;
     (void)hipFree(m->rec); (void)hipFree(m->tile_sph); (void)hipFree(m->chunk_sph); (void)hipFree(m->ws);
+    bvh_free(&m->bvh);
     delete m;
 }
 
@@ -439,6 +563,55 @@ int surfd_mesh_closest(const surfd_mesh *m, const float *queries, int Q, int fla
         LAUNCH_CHECK();
     }
     return SURFD_OK;
+}
+
+int surfd_mesh_build_bvh(surfd_mesh *m, surfd_stream s) {
+    if (!m) SURFD_FAIL(SURFD_ERR_ARG, "surfd_mesh_build_bvh: null handle");
+    return bvh_build(&m->bvh, (const float4 *)m->rec, MD_REC4, true, m->F, as_stream(s));
+}
+
+int surfd_mesh_closest_bvh(const surfd_mesh *m, const float *queries, int Q, int flags, float *dist, float *closest, int32_t *tri,
+                           int64_t *skipped_tiles, surfd_stream s) {
+    if (Q < 0) SURFD_FAIL(SURFD_ERR_ARG, "surfd_mesh_closest_bvh: Q = %d is negative", Q);
+    if (flags & ~(SURFD_MESH_BRUTE_FORCE | SURFD_MESH_COUNT_VISITS)) SURFD_FAIL(SURFD_ERR_ARG, "surfd_mesh_closest_bvh: unknown flags 0x%x", flags);
+    if (!m) SURFD_FAIL(SURFD_ERR_ARG, "surfd_mesh_closest_bvh: null handle");
+    if (flags & SURFD_MESH_BRUTE_FORCE) return surfd_mesh_closest(m, queries, Q, SURFD_MESH_BRUTE_FORCE, dist, closest, tri, skipped_tiles, s);
+    if (!m->bvh.built) SURFD_FAIL(SURFD_ERR_STATE, "surfd_mesh_closest_bvh: the hierarchy was not built (surfd_mesh_build_bvh)");
+    if (Q == 0) return SURFD_OK;
+    if (!queries) SURFD_FAIL(SURFD_ERR_ARG, "surfd_mesh_closest_bvh: null queries");
+    if (Q > (1 << 28)) SURFD_FAIL(SURFD_ERR_UNSUPPORTED, "surfd_mesh_closest_bvh: Q = %d is beyond the supported size", Q);
+    hipStream_t st = as_stream(s);
+    int rc;
+    if ((rc = md_ws(m, 2 * (size_t)Q * sizeof(float), st))) return rc;
+    float *pd = (float *)m->ws;
+    int *pi = (int *)(pd + Q);
+    if (skipped_tiles) HIP_TRY(hipMemsetAsync(skipped_tiles, 0, sizeof(int64_t), st));      // no tiles on this path
+    if ((flags & SURFD_MESH_COUNT_VISITS) && (rc = bvh_visits_reset(&m->bvh, st))) return rc;
+    hipLaunchKernelGGL(bvm_closest_kernel, dim3((unsigned)ceil_div(Q, MD_CHUNK)), dim3(256), 0, st, (const float4 *)m->rec, m->F,
+                       (const float4 *)m->bvh.boxes, (const int4 *)m->bvh.leaf_tri, (const int *)m->bvh.level_off, m->bvh.lay.levels - 1,
+                       m->bvh.lay.nleaf, queries, Q, pd, pi, (flags & SURFD_MESH_COUNT_VISITS) ? m->bvh.visits : nullptr);
+    LAUNCH_CHECK();
+    if (dist || closest || tri) {
+        hipLaunchKernelGGL(md_finish_kernel, dim3((unsigned)ceil_div(Q, 256)), dim3(256), 0, st, (const float4 *)m->rec, m->F, queries, Q,
+                           (const float *)pd, (const int *)pi, 1, dist, closest, tri);
+        LAUNCH_CHECK();
+    }
+    return SURFD_OK;
+}
+
+int surfd_mesh_visits(const surfd_mesh *m, int64_t *box_tests, int64_t *pair_tests, surfd_stream s) {
+    if (!m) SURFD_FAIL(SURFD_ERR_ARG, "surfd_mesh_visits: null handle");
+    return bvh_visits_read("surfd_mesh_visits", &m->bvh, box_tests, pair_tests, as_stream(s));
+}
+
+int surfd_mesh_bvh_info(const surfd_mesh *m, int *levels, int *leaves, int *nodes, int32_t *level_sizes, int capacity) {
+    if (!m) SURFD_FAIL(SURFD_ERR_ARG, "surfd_mesh_bvh_info: null handle");
+    return bvh_info("surfd_mesh_bvh_info", &m->bvh, levels, leaves, nodes, level_sizes, capacity);
+}
+
+int surfd_mesh_bvh_read(const surfd_mesh *m, float *boxes, int32_t *leaf_triangles, surfd_stream s) {
+    if (!m) SURFD_FAIL(SURFD_ERR_ARG, "surfd_mesh_bvh_read: null handle");
+    return bvh_read("surfd_mesh_bvh_read", &m->bvh, boxes, leaf_triangles, as_stream(s));
 }
 
 }  // extern "C"

@@ -64,10 +64,47 @@
 //   that, a needle seen edge-on, can be reported hit by a ray that passes its supporting line outside the triangle; the culled
 //   and the brute-force path can differ for such a pair only.  The restatement and SURFD_RAY_BRUTE_FORCE always agree.
 //
+// Hierarchy (SURFD_RAY_BVH, the bvr_ kernels; built by meshbvh.hip, whose header describes the tree).  bvr_trace_kernel: one ray
+// per lane, 256 rays per workgroup, every lane walks the whole implicit tree on its own (meshbvh_layout.h: level, node and one
+// 64-bit word of waiting children; no stack, no private array), so the triangle range is not split and the existing finish
+// kernels run with S = 1.  A leaf's triangles go through rc_pair() with the handle's own index, so keys and ties are those of
+// the other two paths; every triangle is in exactly one leaf, so a crossing is counted once.  The children of a node are taken
+// in ascending order, whatever the ray: the result cannot depend on the order (the minimum of a total order, a sum of integers).
+//
+// Box bound (bvr_cannot_hit), derived like rc_cannot_hit's, u = 2^-24.  A lane may skip only when its ray is TAME as above and
+// the box is finite (a box of meshbvh.hip has |coordinates| <= 2^20 or is (-inf, +inf)^3, which fails M < inf below).
+//   What an accepted pair guarantees.  With the computed weights (U, V, W) / det >= 0 (sum 1 to 2^-52) the fp64 value
+//   t* = (Sz T) / det is the same combination of the vertices' own parameters along kz, and o + t* d is the same combination p
+//   of the vertices, minus (in the two sheared axes) the residual rho = (U Ax + V Bx + W Cx) / det, which is zero in exact
+//   arithmetic.  p lies in every box that holds the vertices.  |rho| is the rounding of the edge functions over det: below
+//   2^-50 |P - o| except for the needle of the caveat above, exactly the "true line within the pair test's own rounding of a point
+//   of the triangle" that bound 1 of rc_cannot_hit relies on.  So for every axis j: o_j + t* d_j in [lo_j - |rho|, hi_j + |rho|].
+//   1  positions: a_j = fl(lo_j - o_j), b_j = fl(hi_j - o_j), M = the largest of the six sizes, s = fl(2^-16 M + 2^-60),
+//      a'_j = fl(a_j - s), b'_j = fl(b_j + s).  The four roundings are below 4u M = 2^-22 M, so [a'_j, b'_j] holds
+//      [lo_j - o_j - 2^-17 M, hi_j - o_j + 2^-17 M]: a factor 2 on s in hand, and 2^-17 M against |rho| <= 2^-50 |P - o| <= 2^-49 M
+//      leaves what the needle caveat is about the same room rc_cannot_hit gives it or more: that test passes a line up to
+//      sqrt(rs^2 (1 + 2^-10) + 2^-27 |w|^2) - rs from its sphere, at its least (rs = 2^-8.5 |w|) 2^-18.5 |w| <= 2^-17.7 M.
+//   2  an axis with |d_j| < 2^-40 max |d| is PARALLEL: over every t with |t d_kz| <= M + s the ray moves along j by less than
+//      2^-39 M, inside the room of 1.  Such an axis skips when a'_j > 0 or b'_j < 0 and constrains t in no other way.  d_j = 0 is
+//      the plain case of it; no division by a small d_j occurs.
+//   3  every other axis (kz always is one): i_j = fl(1 / d_j), 2^-20 <= |i_j| <= 2^60, t1 = fl(a'_j i_j), t2 = fl(b'_j i_j), each
+//      within 2u of the exact quotient and never a NaN or an Inf (|a'_j| < 2^22); t* lies between the exact quotients and the
+//      fp32 t of the pair within u |t*| of t*.  With e_j = fl(2^-20 max(|t1|, |t2|) + 2^-100) (needed: 3.1u max, so a factor 5 in
+//      hand for e_j's own rounding and that of the two operations below) the pair's t lies in [min(t1, t2) - e_j, max(t1, t2) + e_j].
+//      near = the largest lower end, far = the smallest upper end over these axes.  The box is skipped when near > far, when
+//      far < tmin, or when near > hi; hi = tmax, or in a cast the lane's best t so far: STRICT, so a pair that ties the best t
+//      and might win on the index is never skipped.
+//   A NaN anywhere makes the compares false: no skip.  A ray that is not ok walks nothing; a ray that is ok but not tame skips
+//   nothing and meets every triangle.  The needle caveat carries over as it stands; nothing else is excused.
+//
 // Bounds: ray n >= R reads ray R - 1 and writes nothing.  Staging reads records below F only; LDS is indexed with u < cnt <= 256.
 // The sphere arrays are indexed with c < nchunk and c * 8 + tt < ntile.  Partial results [S, R] live in the handle's workspace:
-// one stream at a time per handle.  Hazards: the LDS chunk is bracketed by a barrier on both sides.
+// one stream at a time per handle.  Hazards: the LDS chunk is bracketed by a barrier on both sides.  bvr_trace_kernel reads
+// node off[level] + node with node < size[level] and leaf_tri[child] with child < nleaf: only children whose box exists are ever
+// entered (meshbvh_layout.h); a triangle index outside [0, F) is not read.  Its LDS holds the level offsets, written once
+// before one barrier.
 #include "common.h"
+#include "meshbvh.h"
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -89,6 +126,10 @@ constexpr float RC_R2_MARGIN = 9.765625e-04f;     // 2^-10
 constexpr float RC_W2_MARGIN = 7.450580596923828125e-09f;   // 2^-27
 constexpr float RC_T_REL = 9.5367431640625e-07f;  // 2^-20
 constexpr float RC_T_ABS = 7.88860905221011805e-31f;        // 2^-100
+
+constexpr float BVR_PARALLEL = 9.094947017729282379e-13f;      // 2^-40
+constexpr float BVR_POS_REL = 1.52587890625e-05f;              // 2^-16
+constexpr float BVR_POS_ABS = 8.67361737988403547e-19f;        // 2^-60
 
 struct RcRay {
     double ox, oy, oz;       // the origin, permuted to (kx, ky, kz)
@@ -326,6 +367,125 @@ __global__ __launch_bounds__(256) void rc_trace_kernel(const float4 *__restrict_
     }
 }
 
+// what a lane needs of its ray to test a box (fp32): the origin, 1 / d_j of the axes that are not parallel, and which are
+struct BvrRay {
+    float ox, oy, oz, ix, iy, iz;
+    bool px, py, pz;     // parallel axes (header, 2)
+    bool tame;
+};
+
+__device__ __forceinline__ BvrRay bvr_setup(float ox, float oy, float oz, float dx, float dy, float dz) {
+    BvrRay q;
+    q.ox = ox; q.oy = oy; q.oz = oz;
+    const float ax = fabsf(dx), ay = fabsf(dy), az = fabsf(dz);
+    const float m = fmaxf(ax, fmaxf(ay, az));
+    const float lim = m * BVR_PARALLEL;
+    q.px = !(ax >= lim) || ax == 0.f; q.py = !(ay >= lim) || ay == 0.f; q.pz = !(az >= lim) || az == 0.f;
+    q.ix = q.px ? 0.f : __fdiv_rn(1.f, dx);
+    q.iy = q.py ? 0.f : __fdiv_rn(1.f, dy);
+    q.iz = q.pz ? 0.f : __fdiv_rn(1.f, dz);
+    q.tame = fabsf(ox) <= RC_TAME_HI && fabsf(oy) <= RC_TAME_HI && fabsf(oz) <= RC_TAME_HI && m >= RC_TAME_LO && m <= RC_TAME_HI;
+    return q;
+}
+
+// one axis of the box test: a, b = the widened box relative to the origin.  Returns true where the axis alone rules the box out
+__device__ __forceinline__ bool bvr_axis(float a, float b, float inv, bool parallel, float &near, float &far) {
+    const float t1 = a * inv, t2 = b * inv;
+    const float e = fmaf(fmaxf(fabsf(t1), fabsf(t2)), RC_T_REL, RC_T_ABS);
+    const float n = fminf(t1, t2) - e, f = fmaxf(t1, t2) + e;
+    near = parallel ? near : fmaxf(near, n);
+    far = parallel ? far : fminf(far, f);
+    return parallel && (a > 0.f || b < 0.f);
+}
+
+// true where no triangle with all its vertices inside the box can be a hit of this lane's ray with tmin <= t < (or, in a cast,
+// <=) hi: the bound of the header
+__device__ __forceinline__ bool bvr_cannot_hit(float lox, float loy, float loz, float hix, float hiy, float hiz, const BvrRay &q,
+                                               float tmin, float hi) {
+    float ax = lox - q.ox, ay = loy - q.oy, az = loz - q.oz, bx = hix - q.ox, by = hiy - q.oy, bz = hiz - q.oz;
+    const float M = fmaxf(fmaxf(fmaxf(fabsf(ax), fabsf(bx)), fmaxf(fabsf(ay), fabsf(by))), fmaxf(fabsf(az), fabsf(bz)));
+    const float s = fmaf(M, BVR_POS_REL, BVR_POS_ABS);
+    ax -= s; ay -= s; az -= s; bx += s; by += s; bz += s;
+    float near = -INFINITY, far = INFINITY;
+    bool out = bvr_axis(ax, bx, q.ix, q.px, near, far);
+    out = bvr_axis(ay, by, q.iy, q.py, near, far) || out;
+    out = bvr_axis(az, bz, q.iz, q.pz, near, far) || out;
+    out = out || near > far || far < tmin || near > hi;
+    return q.tame && M < INFINITY && out;
+}
+
+// the children of a node that the lane has to enter: bit c for child c; nbox counts the box tests made
+__device__ __forceinline__ unsigned bvr_children(const BvhNode &n, const BvrRay &q, float tmin, float hi, unsigned &nbox) {
+    unsigned m = 0;
+#pragma unroll
+    for (int c = 0; c < BVH_W; ++c) {
+        const float lox = bvh_comp(n.lox, c), hix = bvh_comp(n.hix, c);
+        const bool there = bvh_child_exists(lox, hix);
+        const bool skip = bvr_cannot_hit(lox, bvh_comp(n.loy, c), bvh_comp(n.loz, c), hix, bvh_comp(n.hiy, c), bvh_comp(n.hiz, c), q, tmin, hi);
+        nbox += there ? 1u : 0u;
+        m |= (there && !skip) ? (1u << c) : 0u;
+    }
+    return m;
+}
+
+// rays [R, 6]; results pk / pc [R] (one split).  visits: null, or two counters (box tests, pair tests)
+template <bool COUNT>
+__global__ __launch_bounds__(256) void bvr_trace_kernel(const float4 *__restrict__ rec, int F, const float4 *__restrict__ boxes,
+                                                        const int4 *__restrict__ leaf_tri, const int *__restrict__ level_off, int top,
+                                                        const float *__restrict__ rays, int R, float tmin, float tmax,
+                                                        unsigned long long *__restrict__ pk, int *__restrict__ pc,
+                                                        unsigned long long *__restrict__ visits) {
+    __shared__ int off[BVH_MAX_LEVELS];
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (tid < BVH_MAX_LEVELS) off[tid] = level_off[tid];
+    __syncthreads();
+    const int n = blockIdx.x * RC_CHUNK + tid;
+    const long nr = n < R ? n : R - 1;
+    const float ox = rays[nr * 6], oy = rays[nr * 6 + 1], oz = rays[nr * 6 + 2];
+    const float dx = rays[nr * 6 + 3], dy = rays[nr * 6 + 4], dz = rays[nr * 6 + 5];
+    const RcRay r = rc_ray(ox, oy, oz, dx, dy, dz);
+    const bool live = n < R && r.ok;
+    const BvrRay q = bvr_setup(ox, oy, oz, dx, dy, dz);
+    unsigned long long key = RC_MISS;
+    int hits = 0;
+    float hi = tmax;
+    unsigned nbox = 0, npair = 0;
+    int level = top;
+    unsigned node = 0, child = 0;
+    unsigned long long mask = 0;
+    if (live) mask = bvh_mask_bits(top, bvr_children(bvh_load(boxes, off[top], 0), q, tmin, hi, nbox));
+#pragma unroll 1
+    while (bvh_next(top, level, node, mask, child)) {
+        if (level > 0) {
+            bvh_enter(level, node, child);
+            mask |= bvh_mask_bits(level, bvr_children(bvh_load(boxes, off[level], node), q, tmin, hi, nbox));
+            continue;
+        }
+        const int4 ids = leaf_tri[child];
+#pragma unroll
+        for (int i = 0; i < BVH_L; ++i) {
+            const int f = bvh_comp(ids, i);
+            if ((unsigned)f >= (unsigned)F) continue;              // -1: the last leaf has fewer than L triangles
+            float t = 0.f;
+            double V, W, det;
+            const bool hit = rc_pair(r, rec[(long)f * RC_REC4], rec[(long)f * RC_REC4 + 1], rec[(long)f * RC_REC4 + 2], tmin, tmax, t, V, W, det);
+            npair += 1;
+            if constexpr (COUNT) {
+                hits += hit ? 1 : 0;
+            } else {
+                const unsigned long long k = ((unsigned long long)rc_float_bits(t) << 32) | (unsigned)f;
+                key = hit && k < key ? k : key;
+            }
+        }
+        if constexpr (!COUNT) hi = key == RC_MISS ? tmax : rc_bits_float((unsigned)(key >> 32));
+    }
+    if (n < R) {
+        if constexpr (COUNT) pc[n] = hits;
+        else pk[n] = key;
+    }
+    if (visits) bvh_count_visits(visits, nbox, npair, lane);
+}
+
 // the minimum key of ray n over the S splits, then the pair test once more on the winner
 __global__ __launch_bounds__(256) void rc_finish_cast_kernel(const float4 *__restrict__ rec, int F, const float *__restrict__ rays, int R,
                                                              const unsigned long long *__restrict__ pk, int S, float tmin, float tmax,
@@ -384,6 +544,7 @@ struct surfd_rayscene {
     long long last_total = 0;         // and how many visits that call had in all
     mutable void *ws = nullptr;       // partial results (grows)
     mutable size_t ws_bytes = 0;
+    MeshBvh bvh;                      // the hierarchy of surfd_rayscene_build_bvh (meshbvh.hip)
 };
 
 static int rc_ws(const surfd_rayscene *m, size_t bytes, hipStream_t st) {
@@ -406,7 +567,11 @@ static void rc_splits(int R, int nchunk, int *S, int *span) {
 
 static int rc_check(const char *who, const surfd_rayscene *m, const float *rays, int R, float tmin, float tmax, int flags) {
     if (R < 0) SURFD_FAIL(SURFD_ERR_ARG, "%s: R = %d is negative", who, R);
-    if (flags & ~(SURFD_RAY_BRUTE_FORCE | SURFD_RAY_COUNT_SKIPPED)) SURFD_FAIL(SURFD_ERR_ARG, "%s: unknown flags 0x%x", who, flags);
+    if (flags & ~(SURFD_RAY_BRUTE_FORCE | SURFD_RAY_COUNT_SKIPPED | SURFD_RAY_BVH | SURFD_RAY_COUNT_VISITS))
+        SURFD_FAIL(SURFD_ERR_ARG, "%s: unknown flags 0x%x", who, flags);
+    if ((flags & SURFD_RAY_BVH) && !(flags & SURFD_RAY_BRUTE_FORCE) && !(m && m->bvh.built))
+        SURFD_FAIL(m ? SURFD_ERR_STATE : SURFD_ERR_ARG, "%s: flags 0x%x ask for the hierarchy, which was not built (surfd_rayscene_build_bvh)",
+                   who, flags);
     if (!(tmin >= 0.f) || !(tmin < INFINITY)) SURFD_FAIL(SURFD_ERR_ARG, "%s: tmin = %g must be finite and not negative", who, (double)tmin);
     if (tmax != tmax) SURFD_FAIL(SURFD_ERR_ARG, "%s: tmax is a NaN", who);
     if (!m) SURFD_FAIL(SURFD_ERR_ARG, "%s: null handle", who);
@@ -419,13 +584,27 @@ template <bool COUNT>
 static int rc_trace(surfd_rayscene *m, const float *rays, int R, float tmin, float tmax, int flags, unsigned long long **pk, int **pc,
                     int *S_out, hipStream_t st) {
     int S, span, rc;
+    const bool brute = flags & SURFD_RAY_BRUTE_FORCE;
+    const bool tree = (flags & SURFD_RAY_BVH) && !brute;      // the brute-force flag wins
     rc_splits(R, m->nchunk, &S, &span);
+    if (tree) S = 1;
     const size_t np = (size_t)S * R;
     if ((rc = rc_ws(m, np * sizeof(unsigned long long), st))) return rc;
     *pk = (unsigned long long *)m->ws;
     *pc = (int *)m->ws;
     *S_out = S;
-    const bool brute = flags & SURFD_RAY_BRUTE_FORCE;
+    if (m->bvh.built && (flags & SURFD_RAY_COUNT_VISITS) && (rc = bvh_visits_reset(&m->bvh, st))) return rc;
+    if (tree) {
+        if (flags & SURFD_RAY_COUNT_SKIPPED) {
+            HIP_TRY(hipMemsetAsync(m->skipped, 0, sizeof(unsigned long long), st));
+            m->last_total = 0;                                // no tiles on this path
+        }
+        hipLaunchKernelGGL((bvr_trace_kernel<COUNT>), dim3((unsigned)ceil_div(R, RC_CHUNK)), dim3(256), 0, st, (const float4 *)m->rec, m->F,
+                           (const float4 *)m->bvh.boxes, (const int4 *)m->bvh.leaf_tri, (const int *)m->bvh.level_off, m->bvh.lay.levels - 1,
+                           rays, R, tmin, tmax, *pk, *pc, (flags & SURFD_RAY_COUNT_VISITS) ? m->bvh.visits : nullptr);
+        LAUNCH_CHECK();
+        return SURFD_OK;
+    }
     unsigned long long *skipped = nullptr;
     if (flags & SURFD_RAY_COUNT_SKIPPED) {
         HIP_TRY(hipMemsetAsync(m->skipped, 0, sizeof(unsigned long long), st));
@@ -492,6 +671,7 @@ int surfd_rayscene_create(const float *vertices, int V, const int32_t *triangles
 void surfd_rayscene_destroy(surfd_rayscene *m) {
     if (!m) return;
     (void)hipFree(m->rec); (void)hipFree(m->tile_sph); (void)hipFree(m->chunk_sph); (void)hipFree(m->skipped); (void)hipFree(m->ws);
+    bvh_free(&m->bvh);
     delete m;
 }
 
@@ -535,6 +715,26 @@ int surfd_rayscene_skipped(surfd_rayscene *m, int64_t *skipped, int64_t *total, 
     *skipped = (int64_t)v;
     *total = (int64_t)m->last_total;
     return SURFD_OK;
+}
+
+int surfd_rayscene_build_bvh(surfd_rayscene *m, surfd_stream s) {
+    if (!m) SURFD_FAIL(SURFD_ERR_ARG, "surfd_rayscene_build_bvh: null handle");
+    return bvh_build(&m->bvh, (const float4 *)m->rec, RC_REC4, false, m->F, as_stream(s));
+}
+
+int surfd_rayscene_visits(surfd_rayscene *m, int64_t *box_tests, int64_t *pair_tests, surfd_stream s) {
+    if (!m) SURFD_FAIL(SURFD_ERR_ARG, "surfd_rayscene_visits: null handle");
+    return bvh_visits_read("surfd_rayscene_visits", &m->bvh, box_tests, pair_tests, as_stream(s));
+}
+
+int surfd_rayscene_bvh_info(const surfd_rayscene *m, int *levels, int *leaves, int *nodes, int32_t *level_sizes, int capacity) {
+    if (!m) SURFD_FAIL(SURFD_ERR_ARG, "surfd_rayscene_bvh_info: null handle");
+    return bvh_info("surfd_rayscene_bvh_info", &m->bvh, levels, leaves, nodes, level_sizes, capacity);
+}
+
+int surfd_rayscene_bvh_read(const surfd_rayscene *m, float *boxes, int32_t *leaf_triangles, surfd_stream s) {
+    if (!m) SURFD_FAIL(SURFD_ERR_ARG, "surfd_rayscene_bvh_read: null handle");
+    return bvh_read("surfd_rayscene_bvh_read", &m->bvh, boxes, leaf_triangles, as_stream(s));
 }
 
 }  // extern "C"

@@ -113,6 +113,30 @@ def morton_order(p: Tensor) -> Tensor:
 
 
 # ---- closest point ------------------------------------------------------------------------------------------------------------
+ACCELS = ("tiles", "bvh")
+MESH_BRUTE_FORCE = 1
+MESH_COUNT_VISITS = 2
+
+
+def _check_accel(accel: str) -> None:
+    if accel not in ACCELS:
+        raise ValueError(f"accel must be 'tiles' or 'bvh', got {accel!r}")
+
+
+def _read_bvh(handle, info_fn, read_fn, device) -> dict:
+    """the hierarchy of a handle as the library holds it: {"level_sizes": [levels] ints (level 0 = the nodes above the leaves),
+    "boxes": [nodes, 6, 4] float32 (lo.xyz, hi.xyz of a node's 4 children), "leaves": [leaves, 4] int32 (the HANDLE's triangle
+    indices, -1 past the end)}, on the device"""
+    levels, leaves, nodes = C.c_int(), C.c_int(), C.c_int()
+    sizes = (C.c_int32 * 16)()
+    N.check(info_fn(handle, C.byref(levels), C.byref(leaves), C.byref(nodes), sizes, 16))
+    boxes = torch.empty(nodes.value, 6, 4, device=device, dtype=torch.float32)
+    tri = torch.empty(leaves.value, 4, device=device, dtype=torch.int32)
+    with torch.cuda.device(device):
+        N.check(read_fn(handle, N.ptr(boxes), N.ptr(tri), N.stream()))
+    return {"level_sizes": [int(sizes[k]) for k in range(levels.value)], "boxes": boxes, "leaves": tri}
+
+
 class MeshDistance:
     """The closest-point structure of one mesh, kept for repeated calls (the role of open3d's RaycastingScene).
 
@@ -121,9 +145,13 @@ class MeshDistance:
     come back in the caller's order with the caller's triangle indices.  Ties in distance go to the triangle that comes first
     in the Morton order.  Host syncs: the constructor checks the vertices and the index range (three) and the library's create
     reads its bad-index flag (one); every ``closest`` call checks that the queries are finite (one).  One stream at a time per
-    object: the library keeps its partial results in a workspace of the handle."""
+    object: the library keeps its partial results in a workspace of the handle.
 
-    def __init__(self, vertices: Tensor, triangles: Tensor):
+    ``accel="bvh"`` also builds the box hierarchy of csrc/meshbvh.hip (one more host sync); ``closest`` then walks it instead of
+    the tiles unless ``brute_force=True``.  The results are the same bits either way."""
+
+    def __init__(self, vertices: Tensor, triangles: Tensor, accel: str = "tiles"):
+        _check_accel(accel)
         _check_mesh(vertices, triangles)
         if not bool(torch.isfinite(vertices).all()):
             raise ValueError("vertices contain NaN or Inf")
@@ -141,13 +169,31 @@ class MeshDistance:
             N.check(N.lib().surfd_mesh_create(N.ptr(v), v.shape[0], N.ptr(ts), ts.shape[0], N.stream(), C.byref(h)))
         self._handle = h
         assert N.lib().surfd_mesh_num_triangles(h) == self.num_triangles
+        self.accel = accel
+        if accel == "bvh":
+            with torch.cuda.device(self.device):
+                N.check(N.lib().surfd_mesh_build_bvh(h, N.stream()))
         self.last_skipped_tiles: Optional[int] = None
         self.last_total_tiles: Optional[int] = None
+        self.last_box_tests: Optional[int] = None
+        self.last_pair_tests: Optional[int] = None
 
-    def closest(self, queries: Tensor, brute_force: bool = False, count_skipped: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
+    def read_bvh(self) -> dict:
+        """the hierarchy (``accel="bvh"`` only), for tests: see ``_read_bvh``; ``perm`` maps a handle index to the caller's"""
+        out = _read_bvh(self._handle, N.lib().surfd_mesh_bvh_info, N.lib().surfd_mesh_bvh_read, self.device)
+        out["perm"] = self._perm
+        return out
+
+    def closest(self, queries: Tensor, brute_force: bool = False, count_skipped: bool = False,
+                count_visits: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
         """queries [Q, 3] -> (dist [Q] float32, points [Q, 3] float32, tri [Q] int64).  ``brute_force`` tests every pair (the
         correctness baseline; the same bits).  With ``count_skipped`` the number of (wave, tile) visits that culling skipped is
-        left in ``last_skipped_tiles`` and their total in ``last_total_tiles`` (one host sync)."""
+        left in ``last_skipped_tiles`` and their total in ``last_total_tiles`` (one host sync).  With ``count_visits``
+        (``accel="bvh"``) the box tests and pair tests of the call, summed over the queries, are left in ``last_box_tests`` and
+        ``last_pair_tests`` (one host sync)."""
+        use_bvh = self.accel == "bvh" and not brute_force
+        if count_visits and not use_bvh:
+            raise ValueError("count_visits counts the hierarchy's tests: it needs accel='bvh' and not brute_force")
         _check_points("queries", queries)
         if queries.device != self.device:
             raise RuntimeError(f"queries are on {queries.device}, the mesh is on {self.device}")
@@ -163,8 +209,16 @@ class MeshDistance:
         qs = queries[order].contiguous()
         skipped = torch.zeros(1, device=self.device, dtype=torch.int64) if count_skipped else None
         with torch.cuda.device(self.device):
-            N.check(N.lib().surfd_mesh_closest(self._handle, N.ptr(qs), Q, 1 if brute_force else 0, N.ptr(dist), N.ptr(pts), N.ptr(tri),
-                                               N.ptr(skipped), N.stream()))
+            if use_bvh:
+                N.check(N.lib().surfd_mesh_closest_bvh(self._handle, N.ptr(qs), Q, MESH_COUNT_VISITS if count_visits else 0, N.ptr(dist),
+                                                       N.ptr(pts), N.ptr(tri), N.ptr(skipped), N.stream()))
+                if count_visits:
+                    b, p = C.c_int64(), C.c_int64()
+                    N.check(N.lib().surfd_mesh_visits(self._handle, C.byref(b), C.byref(p), N.stream()))
+                    self.last_box_tests, self.last_pair_tests = int(b.value), int(p.value)
+            else:
+                N.check(N.lib().surfd_mesh_closest(self._handle, N.ptr(qs), Q, MESH_BRUTE_FORCE if brute_force else 0, N.ptr(dist),
+                                                   N.ptr(pts), N.ptr(tri), N.ptr(skipped), N.stream()))
         if count_skipped:
             self.last_skipped_tiles = int(skipped.item())
             self.last_total_tiles = ((Q + 63) // 64) * ((self.num_triangles + 31) // 32)
@@ -180,13 +234,16 @@ class MeshDistance:
             pass
 
 
-def closest_points(vertices: Tensor, triangles: Tensor, queries: Tensor, brute_force: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
-    """(dist [Q], points [Q, 3], tri [Q]): for every query the exact closest point of the mesh, its distance and its triangle"""
+def closest_points(vertices: Tensor, triangles: Tensor, queries: Tensor, brute_force: bool = False,
+                   accel: str = "tiles") -> Tuple[Tensor, Tensor, Tensor]:
+    """(dist [Q], points [Q, 3], tri [Q]): for every query the exact closest point of the mesh, its distance and its triangle.
+    ``accel``: "tiles" or "bvh" (MeshDistance); the same bits."""
+    _check_accel(accel)
     _check_mesh(vertices, triangles, need_cuda=False)          # shapes and dtypes first, the CPU-tensor refusal last
     _check_points("queries", queries, need_cuda=False)
     _check_mesh(vertices, triangles)
     _check_points("queries", queries)
-    return MeshDistance(vertices, triangles).closest(queries, brute_force=brute_force)
+    return MeshDistance(vertices, triangles, accel=accel).closest(queries, brute_force=brute_force)
 
 
 # ---- samplers (torch plumbing) ------------------------------------------------------------------------------------------------
@@ -280,24 +337,30 @@ def sample_points_around_pcd(pcd: Tensor, stds: List[float], num_points_per_std:
 
 
 # ---- UDF labels ---------------------------------------------------------------------------------------------------------------
-def _as_mesh_distance(vertices, triangles) -> MeshDistance:
-    return vertices if isinstance(vertices, MeshDistance) and triangles is None else MeshDistance(vertices, triangles)
+def _as_mesh_distance(vertices, triangles, accel: str = "tiles") -> MeshDistance:
+    """a given MeshDistance (triangles None; it keeps its own ``accel``), or a new one"""
+    _check_accel(accel)
+    return vertices if isinstance(vertices, MeshDistance) and triangles is None else MeshDistance(vertices, triangles, accel=accel)
 
 
-def compute_udf_and_gradients(vertices: Tensor, triangles: Tensor, queries: Tensor) -> Tuple[Tensor, Tensor]:
+def compute_udf_and_gradients(vertices: Tensor, triangles: Tensor, queries: Tensor, accel: str = "tiles") -> Tuple[Tensor, Tensor]:
     """AutoEncoder/utils.py:223-240: udf = |q - c| and gradients = F.normalize(q - c) for the closest point c of the mesh (a
-    query on the surface gets a zero gradient through F.normalize's eps).  ``vertices`` may be a MeshDistance (triangles None)."""
-    offset = queries - _as_mesh_distance(vertices, triangles).closest(queries)[1]
+    query on the surface gets a zero gradient through F.normalize's eps).  ``vertices`` may be a MeshDistance (triangles None).
+    ``accel``: how a new MeshDistance searches ("tiles" or "bvh"; the same bits)."""
+    offset = queries - _as_mesh_distance(vertices, triangles, accel).closest(queries)[1]
     return offset.norm(dim=-1), F.normalize(offset, dim=-1)
 
 
 def compute_udf_from_mesh(vertices: Tensor, triangles: Tensor, num_surface_points: int = 100_000, num_queries_on_surface: int = 10_000,
                           queries_stds: List[float] = [0.003, 0.01, 0.1], num_queries_per_std: List[int] = [5_000, 4_000, 500, 500],
                           coords_range: Tuple[float, float] = (-1.0, 1.0), max_dist: float = 0.1, convert_to_bce_labels: bool = False,
-                          use_cuda: bool = True, input_queries: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+                          use_cuda: bool = True, input_queries: Optional[Tensor] = None,
+                          accel: str = "tiles") -> Tuple[Tensor, Tensor, Tensor]:
     """AutoEncoder/utils.py:268-314 -> (queries, values, gradients): a surface cloud, queries around it (or ``input_queries``),
     their UDF clipped to [0, max_dist] and its gradients.  Everything stays on the mesh's device (the reference moves the queries
-    to the CPU for open3d); ``num_queries_on_surface`` and ``convert_to_bce_labels`` are unused, as in the reference."""
+    to the CPU for open3d); ``num_queries_on_surface`` and ``convert_to_bce_labels`` are unused, as in the reference.
+    ``accel``: "tiles" or "bvh" (MeshDistance); the same random numbers and the same bits."""
+    _check_accel(accel)
     _check_mesh(vertices, triangles)
     if not use_cuda:
         raise RuntimeError("compute_udf_from_mesh runs only on the GPU through libsurfd_hip.so (no CPU fallback)")
@@ -305,7 +368,7 @@ def compute_udf_from_mesh(vertices: Tensor, triangles: Tensor, num_surface_point
     if queries is None:
         cloud = sample_points_uniformly(vertices, triangles, num_surface_points)
         queries = sample_points_around_pcd(cloud, queries_stds, num_queries_per_std, coords_range, vertices.device)
-    udf, gradients = compute_udf_and_gradients(vertices, triangles, queries)
+    udf, gradients = compute_udf_and_gradients(vertices, triangles, queries, accel=accel)
     return queries, udf.clamp(0, max_dist), gradients
 
 
@@ -318,25 +381,32 @@ def _check_method(name: str, method: str) -> None:
         raise ValueError(f"{name} must be 'parity' or 'winding', got {method!r}")
 
 
-def _as_scene(vertices, triangles, method: str = "parity"):
-    """the scene that answers inside / outside by ``method``: a given one of that kind (triangles None), or a new one"""
+def _as_scene(vertices, triangles, method: str = "parity", accel: str = "tiles"):
+    """the scene that answers inside / outside by ``method``: a given one of that kind (triangles None), or a new one.  ``accel``
+    goes to a new RaycastingScene and its mesh_distance(); a WindingScene has no hierarchy and ignores it."""
     from .raycast import RaycastingScene
     from .winding import WindingScene
+    _check_accel(accel)
     kind, other = (RaycastingScene, WindingScene) if method == "parity" else (WindingScene, RaycastingScene)
     if isinstance(vertices, other) and triangles is None:
         raise TypeError(f"a {other.__name__} cannot answer by {method!r}: pass a {kind.__name__} or the mesh itself")
-    return vertices if isinstance(vertices, kind) and triangles is None else kind(vertices, triangles)
+    if isinstance(vertices, kind) and triangles is None:
+        return vertices
+    return RaycastingScene(vertices, triangles, accel=accel) if kind is RaycastingScene else kind(vertices, triangles)
 
 
-def is_inside(vertices: Tensor, triangles: Tensor, points: Tensor, nsamples: int = 1, method: str = "parity") -> Tensor:
+def is_inside(vertices: Tensor, triangles: Tensor, points: Tensor, nsamples: int = 1, method: str = "parity",
+              accel: str = "tiles") -> Tensor:
     """[N] bool: is the point inside the mesh.  ``method="parity"``: the parity of the number of crossings of the ray from the
     point along +z (csrc/raycast.hip); ``nsamples=3`` also asks +x and +y and takes the majority.  The parity means something on a
     closed mesh only (surfd_amd/raycast.py, ``compute_occupancy(..., return_votes=True)`` tells); on a mesh with holes use
     ``method="winding"``: |winding number| >= 1/2 (surfd_amd/winding.py), which needs consistently oriented faces instead and
-    takes no ``nsamples``.  ``vertices`` may be a RaycastingScene, or a WindingScene for "winding" (triangles None)."""
+    takes no ``nsamples``.  ``vertices`` may be a RaycastingScene, or a WindingScene for "winding" (triangles None).
+    ``accel``: how a new RaycastingScene casts ("tiles" or "bvh"; the same answers)."""
     from .raycast import RaycastingScene, _check_nsamples
     from .winding import WindingScene
     _check_method("method", method)
+    _check_accel(accel)
     if not (isinstance(vertices, (RaycastingScene, WindingScene)) and triangles is None):
         _check_mesh(vertices, triangles, need_cuda=False)      # shapes and dtypes first, the CPU-tensor refusal last
     _check_points("points", points, need_cuda=False)
@@ -345,17 +415,19 @@ def is_inside(vertices: Tensor, triangles: Tensor, points: Tensor, nsamples: int
         if nsamples != 1:
             raise ValueError("nsamples belongs to method='parity': the winding number casts no rays")
         return _as_scene(vertices, triangles, method).compute_occupancy(points) > 0
-    return _as_scene(vertices, triangles).compute_occupancy(points, nsamples) > 0
+    return _as_scene(vertices, triangles, accel=accel).compute_occupancy(points, nsamples) > 0
 
 
-def compute_sdf_and_gradients(vertices: Tensor, triangles: Tensor, queries: Tensor, sign: str = "parity") -> Tuple[Tensor, Tensor]:
+def compute_sdf_and_gradients(vertices: Tensor, triangles: Tensor, queries: Tensor, sign: str = "parity",
+                              accel: str = "tiles") -> Tuple[Tensor, Tensor]:
     """AutoEncoder/utils.py:242-264: sdf = the distance to the mesh, negative inside (open3d's compute_signed_distance: the
     parity of the crossings along +z), and gradients = sign(sdf) * F.normalize(q - c) for the closest point c of the mesh.  A
     query on the surface has sdf 0 and a zero gradient.  ``sign="winding"`` takes inside / outside from the winding number
     instead (surfd_amd/winding.py: for meshes with holes).  ``vertices`` may be a RaycastingScene, or a WindingScene for
-    "winding" (triangles None)."""
+    "winding" (triangles None).  ``accel``: how a new RaycastingScene casts and measures ("tiles" or "bvh"; the same bits);
+    with ``sign="winding"`` it is ignored, a WindingScene has no hierarchy."""
     _check_method("sign", sign)
-    scene = _as_scene(vertices, triangles, sign)
+    scene = _as_scene(vertices, triangles, sign, accel)
     sdf = scene.compute_signed_distance(queries)
     offset = queries - scene.mesh_distance().closest(queries)[1]
     return sdf, torch.sign(sdf)[:, None] * F.normalize(offset, dim=-1)
@@ -365,14 +437,15 @@ def compute_sdf_from_mesh(vertices: Tensor, triangles: Tensor, num_surface_point
                           queries_stds: List[float] = [0.003, 0.01, 0.1], num_queries_per_std: List[int] = [5_000, 4_000, 500, 500],
                           coords_range: Tuple[float, float] = (-1.0, 1.0), max_dist: float = 0.1, convert_to_bce_labels: bool = False,
                           use_cuda: bool = True, input_queries: Optional[Tensor] = None,
-                          sign: str = "parity") -> Tuple[Tensor, Tensor, Tensor]:
+                          sign: str = "parity", accel: str = "tiles") -> Tuple[Tensor, Tensor, Tensor]:
     """AutoEncoder/utils.py:317-363 -> (queries, values, gradients): a surface cloud, queries around it (or ``input_queries``),
     their SDF clipped to [-max_dist, max_dist] and its gradients; in front of them ``num_queries_on_surface`` points drawn on the
     surface with value 0 and gradient 0.  ``convert_to_bce_labels`` turns the values into 1 - values / max_dist, as the
     reference does.  Everything stays on the mesh's device and the random numbers come from that device's global RNG, as in
     compute_udf_from_mesh.  ``sign``: "parity" (the reference's) or "winding", as in compute_sdf_and_gradients; the same
-    random numbers are drawn either way."""
+    random numbers are drawn either way.  ``accel``: as in compute_sdf_and_gradients."""
     _check_method("sign", sign)
+    _check_accel(accel)
     _check_mesh(vertices, triangles)
     if not use_cuda:
         raise RuntimeError("compute_sdf_from_mesh runs only on the GPU through libsurfd_hip.so (no CPU fallback)")
@@ -380,7 +453,7 @@ def compute_sdf_from_mesh(vertices: Tensor, triangles: Tensor, num_surface_point
     if queries is None:
         cloud = sample_points_uniformly(vertices, triangles, num_surface_points)
         queries = sample_points_around_pcd(cloud, queries_stds, num_queries_per_std, coords_range, vertices.device)
-    sdf, gradients = compute_sdf_and_gradients(vertices, triangles, queries, sign)
+    sdf, gradients = compute_sdf_and_gradients(vertices, triangles, queries, sign, accel=accel)
     values = sdf.clamp(-max_dist, max_dist)
     on_surface = sample_points_uniformly(vertices, triangles, num_queries_on_surface)
     queries = torch.cat([on_surface, queries], dim=0)
@@ -392,18 +465,22 @@ def compute_sdf_from_mesh(vertices: Tensor, triangles: Tensor, num_surface_point
 
 
 # ---- measurement --------------------------------------------------------------------------------------------------------------
-def point_to_mesh_distance(points: Tensor, vertices: Tensor, triangles: Tensor) -> Tensor:
-    """[N] exact distances of the points to the mesh (``vertices`` may be a MeshDistance, triangles None)"""
-    return _as_mesh_distance(vertices, triangles).closest(points)[0]
+def point_to_mesh_distance(points: Tensor, vertices: Tensor, triangles: Tensor, accel: str = "tiles") -> Tensor:
+    """[N] exact distances of the points to the mesh (``vertices`` may be a MeshDistance, triangles None).  ``accel``: how a new
+    MeshDistance searches ("tiles" or "bvh"; the same bits)."""
+    return _as_mesh_distance(vertices, triangles, accel).closest(points)[0]
 
 
-def mesh_distance(v1: Tensor, t1: Tensor, v2: Tensor, t2: Tensor, n: int = 100_000, generator: Optional[torch.Generator] = None) -> dict:
+def mesh_distance(v1: Tensor, t1: Tensor, v2: Tensor, t2: Tensor, n: int = 100_000, generator: Optional[torch.Generator] = None,
+                  accel: str = "tiles") -> dict:
     """The two directed mean distances between two meshes and their sum: ``n`` points sampled on the surface of one mesh,
-    exact distance to the other.  {"d12": mesh 1 -> mesh 2, "d21": mesh 2 -> mesh 1, "sum": d12 + d21}"""
+    exact distance to the other.  {"d12": mesh 1 -> mesh 2, "d21": mesh 2 -> mesh 1, "sum": d12 + d21}.  ``accel``: "tiles" or
+    "bvh" (MeshDistance); the same numbers."""
+    _check_accel(accel)
     _check_mesh(v1, t1)
     _check_mesh(v2, t2)
     p1 = sample_points_uniformly(v1, t1, n, generator=generator)
     p2 = sample_points_uniformly(v2, t2, n, generator=generator)
-    d12 = float(point_to_mesh_distance(p1, v2, t2).double().mean())
-    d21 = float(point_to_mesh_distance(p2, v1, t1).double().mean())
+    d12 = float(point_to_mesh_distance(p1, v2, t2, accel=accel).double().mean())
+    d21 = float(point_to_mesh_distance(p2, v1, t1, accel=accel).double().mean())
     return {"d12": d12, "d21": d21, "sum": d12 + d21}

@@ -26,10 +26,12 @@ import torch
 from torch import Tensor
 
 from . import _native as N
-from .meshprep import MeshDistance, _check_mesh, _check_points, morton_order
+from .meshprep import MeshDistance, _check_accel, _check_mesh, _check_points, _read_bvh, morton_order
 
 BRUTE_FORCE = 1
 COUNT_SKIPPED = 2
+BVH = 4
+COUNT_VISITS = 8
 
 
 def _check_rays(rays: Tensor, device=None) -> None:
@@ -65,9 +67,13 @@ class RaycastingScene:
     the caller's order with the caller's triangle indices.  Two triangles met at the same ``t`` (bit for bit): the one that
     comes first in the Morton order wins.  Host syncs: the constructor checks the vertices and the index range and the
     library's create reads its bad-index flag; the calls themselves do not sync.  One stream at a time per object: the library
-    keeps its partial results in a workspace of the handle."""
+    keeps its partial results in a workspace of the handle.
 
-    def __init__(self, vertices: Tensor, triangles: Tensor):
+    ``accel="bvh"`` also builds the box hierarchy of csrc/meshbvh.hip (one more host sync); every method then walks it instead
+    of the tiles unless ``brute_force=True``, and ``mesh_distance()`` is built with it too.  The results are the same bits."""
+
+    def __init__(self, vertices: Tensor, triangles: Tensor, accel: str = "tiles"):
+        _check_accel(accel)
         _check_mesh(vertices, triangles, need_cuda=False)          # shapes and dtypes first, the CPU-tensor refusal last
         _check_mesh(vertices, triangles)
         if not bool(torch.isfinite(vertices).all()):
@@ -88,8 +94,20 @@ class RaycastingScene:
             N.check(N.lib().surfd_rayscene_create(N.ptr(v), v.shape[0], N.ptr(ts), ts.shape[0], N.stream(), C.byref(h)))
         self._handle = h
         assert N.lib().surfd_rayscene_num_triangles(h) == self.num_triangles
+        self.accel = accel
+        if accel == "bvh":
+            with torch.cuda.device(self.device):
+                N.check(N.lib().surfd_rayscene_build_bvh(h, N.stream()))
         self.last_skipped_tiles: Optional[int] = None
         self.last_total_tiles: Optional[int] = None
+        self.last_box_tests: Optional[int] = None
+        self.last_pair_tests: Optional[int] = None
+
+    def read_bvh(self) -> dict:
+        """the hierarchy (``accel="bvh"`` only), for tests: see ``meshprep._read_bvh``; ``perm`` maps a handle index to the caller's"""
+        out = _read_bvh(self._handle, N.lib().surfd_rayscene_bvh_info, N.lib().surfd_rayscene_bvh_read, self.device)
+        out["perm"] = self._perm
+        return out
 
     # ---- the two kernels ------------------------------------------------------------------------------------------------------
     def _sorted(self, rays: Tensor):
@@ -103,8 +121,17 @@ class RaycastingScene:
         inv[order] = torch.arange(R, device=self.device)
         return rays[order].contiguous(), order, inv
 
-    def _flags(self, brute_force: bool, count_skipped: bool) -> int:
-        return (BRUTE_FORCE if brute_force else 0) | (COUNT_SKIPPED if count_skipped else 0)
+    def _flags(self, brute_force: bool, count_skipped: bool, count_visits: bool = False) -> int:
+        use_bvh = self.accel == "bvh" and not brute_force
+        if count_visits and not use_bvh:
+            raise ValueError("count_visits counts the hierarchy's tests: it needs accel='bvh' and not brute_force")
+        return (BRUTE_FORCE if brute_force else 0) | (COUNT_SKIPPED if count_skipped else 0) | (BVH if use_bvh else 0) | \
+            (COUNT_VISITS if count_visits else 0)
+
+    def _read_visits(self) -> None:
+        b, p = C.c_int64(), C.c_int64()
+        N.check(N.lib().surfd_rayscene_visits(self._handle, C.byref(b), C.byref(p), N.stream()))
+        self.last_box_tests, self.last_pair_tests = int(b.value), int(p.value)
 
     def _read_skipped(self) -> None:
         s, t = C.c_int64(), C.c_int64()
@@ -112,12 +139,15 @@ class RaycastingScene:
         self.last_skipped_tiles, self.last_total_tiles = int(s.value), int(t.value)
 
     def cast_rays(self, rays: Tensor, tmin: float = 0.0, tmax: float = math.inf, brute_force: bool = False,
-                  count_skipped: bool = False) -> Dict[str, Tensor]:
+                  count_skipped: bool = False, count_visits: bool = False) -> Dict[str, Tensor]:
         """rays [R, 6] -> {"t_hit" [R] float32 (+inf on a miss), "primitive_ids" [R] int64 (-1 on a miss), "primitive_uvs"
         [R, 2] float32, "primitive_normals" [R, 3] float32}: the first triangle met with tmin <= t < tmax.  ``brute_force``
         tests every pair (the correctness baseline; the same bits).  With ``count_skipped`` the number of (wave, tile) visits
-        that culling skipped is left in ``last_skipped_tiles`` and their total in ``last_total_tiles`` (one host sync)."""
+        that culling skipped is left in ``last_skipped_tiles`` and their total in ``last_total_tiles`` (one host sync).  With
+        ``count_visits`` (``accel="bvh"``) the box tests and pair tests of the call, summed over the rays, are left in
+        ``last_box_tests`` and ``last_pair_tests`` (one host sync)."""
         tmin, tmax = _check_range(tmin, tmax)
+        flags = self._flags(brute_force, count_skipped, count_visits)
         rs, order, inv = self._sorted(rays)
         R = rays.shape[0]
         t = torch.empty(R, device=self.device, dtype=torch.float32)
@@ -127,28 +157,33 @@ class RaycastingScene:
         if R == 0:
             return {"t_hit": t, "primitive_ids": tri.long(), "primitive_uvs": uv, "primitive_normals": nrm}
         with torch.cuda.device(self.device):
-            N.check(N.lib().surfd_rayscene_cast(self._handle, N.ptr(rs), R, tmin, tmax, self._flags(brute_force, count_skipped),
+            N.check(N.lib().surfd_rayscene_cast(self._handle, N.ptr(rs), R, tmin, tmax, flags,
                                                 N.ptr(t), N.ptr(tri), N.ptr(uv), N.ptr(nrm), N.stream()))
             if count_skipped:
                 self._read_skipped()
+            if count_visits:
+                self._read_visits()
         tri = tri.long()
         ids = torch.where(tri >= 0, self._perm[tri.clamp_min(0)], tri)
         return {"t_hit": t[inv], "primitive_ids": ids[inv], "primitive_uvs": uv[inv], "primitive_normals": nrm[inv]}
 
     def count_intersections(self, rays: Tensor, tmin: float = 0.0, tmax: float = math.inf, brute_force: bool = False,
-                            count_skipped: bool = False) -> Tensor:
-        """rays [R, 6] -> [R] int32: the number of triangles met with tmin <= t < tmax"""
+                            count_skipped: bool = False, count_visits: bool = False) -> Tensor:
+        """rays [R, 6] -> [R] int32: the number of triangles met with tmin <= t < tmax (``count_visits``: as in cast_rays)"""
         tmin, tmax = _check_range(tmin, tmax)
+        flags = self._flags(brute_force, count_skipped, count_visits)
         rs, order, inv = self._sorted(rays)
         R = rays.shape[0]
         cnt = torch.empty(R, device=self.device, dtype=torch.int32)
         if R == 0:
             return cnt
         with torch.cuda.device(self.device):
-            N.check(N.lib().surfd_rayscene_count(self._handle, N.ptr(rs), R, tmin, tmax, self._flags(brute_force, count_skipped),
+            N.check(N.lib().surfd_rayscene_count(self._handle, N.ptr(rs), R, tmin, tmax, flags,
                                                  N.ptr(cnt), N.stream()))
             if count_skipped:
                 self._read_skipped()
+            if count_visits:
+                self._read_visits()
         return cnt[inv]
 
     # ---- what follows from them -----------------------------------------------------------------------------------------------
@@ -179,7 +214,7 @@ class RaycastingScene:
     def mesh_distance(self) -> MeshDistance:
         """the closest-point structure of the same mesh (made on first use)"""
         if self._distance is None:
-            self._distance = MeshDistance(self.vertices, self.triangles)
+            self._distance = MeshDistance(self.vertices, self.triangles, accel=self.accel)
         return self._distance
 
     def compute_signed_distance(self, points: Tensor, nsamples: int = 1, brute_force: bool = False) -> Tensor:
