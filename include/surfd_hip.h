@@ -372,7 +372,8 @@ int surfd_xattn_set_param(surfd_xattn *a, const char *name, const float *src, co
 /* CrossAttention.forward(x, context=None, mask=None) (:171-193): x [B, N, query_dim]; context [B, M, context_dim] or
  * NULL (self-attention, M ignored); mask [B, M] bytes, non-zero = attend, or NULL (masked scores are set to
  * -FLT_MAX exactly as masked_fill_ does, so a fully masked row attends uniformly); out [B, N, query_dim].
- * Dropout (p = 0 in every constructor call of the reference) is the identity. */
+ * Dropout (p = 0 in every constructor call of the reference) is the identity.
+ * Limits (SURFD_ERR_UNSUPPORTED beyond them): B * heads <= 65535; B * N and B * M <= (2^24 - 1) * 64 = 1 073 741 760 rows. */
 int surfd_xattn_forward(surfd_xattn *a, const float *x, const float *context, const unsigned char *mask, float *out,
                         int B, int N, int M, surfd_stream s);
 

@@ -11,6 +11,10 @@
 //                      softmax runs in registers (+ one cross-half shuffle) and the probabilities are already the B
 //                      operand of the value product (same idiom as attn_kernel in unet.hip); running max / sum
 //                      ("online" softmax) across key blocks, so any context length works with O(1) LDS.
+//
+// Limits of surfd_xattn_forward (refused with SURFD_ERR_UNSUPPORTED beyond them): dim_head <= 128, batch x heads <= 65 535
+// (grid.y of xa_core_kernel), b * n and b * m <= (2^24 - 1) * 64 = 1 073 741 760 token rows (grid.x of xa_linear_kernel,
+// one 64-row tile per workgroup of 256 threads, under 2^32 threads per launch), feature counts <= 65 535 * 64.
 #include "common.h"
 #include <cfloat>
 #include <cmath>
@@ -26,8 +30,8 @@ __global__ __launch_bounds__(256) void xa_linear_kernel(const float *X, long ldx
     const int tid = threadIdx.x, lane = tid & 63, col = lane & 31, half = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 1, wc = wave & 1;
-    const long r0 = (long)blockIdx.y * 64;
-    const int o0 = blockIdx.x * 64;
+    const long r0 = (long)blockIdx.x * 64;                         // row tiles on grid.x: rows = b * n has no 65 535-block limit
+    const int o0 = blockIdx.y * 64;
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -163,9 +167,15 @@ struct surfd_xattn {
     size_t ws_floats = 0;
 };
 
+// Row tiles ride on grid.x (hipDeviceProp_t::maxGridSize = {2^31 - 1, 65 536, 65 536} on gfx950), and a launch may not
+// span 2^32 threads or more in one dimension: (2^24 - 1) tiles of 256 threads, 64 rows each.  Output tiles ride on grid.y.
+// Both limits are checked by the callers (surfd_xattn_create: features, surfd_xattn_forward: rows).
+static const long XA_MAX_ROWS = ((1L << 24) - 1) * 64;
+static const long XA_MAX_FEATURES = 65535L * 64;
+
 static int xa_linear(const float *X, long ldx, const float *W, const float *bias, float *Y, long ldy, long R, int K, int O, hipStream_t st) {
     if (R <= 0) return SURFD_OK;
-    dim3 grid((unsigned)ceil_div(O, 64), (unsigned)ceil_div<long>(R, 64));
+    dim3 grid((unsigned)ceil_div<long>(R, 64), (unsigned)ceil_div(O, 64));
     hipLaunchKernelGGL(xa_linear_kernel, grid, dim3(256), 0, st, X, ldx, W, bias, Y, ldy, (int)R, K, O);
     LAUNCH_CHECK();
     return SURFD_OK;
@@ -177,6 +187,8 @@ int surfd_xattn_create(int query_dim, int context_dim, int heads, int dim_head, 
     if (!out) SURFD_FAIL(SURFD_ERR_ARG, "surfd_xattn_create: null out");
     if (query_dim < 1 || heads < 1 || dim_head < 1) SURFD_FAIL(SURFD_ERR_ARG, "surfd_xattn_create: sizes must be positive");
     if (dim_head > 128) SURFD_FAIL(SURFD_ERR_UNSUPPORTED, "surfd_xattn_create: dim_head %d > 128 is not supported", dim_head);
+    if (query_dim > XA_MAX_FEATURES || (long)heads * dim_head > XA_MAX_FEATURES)
+        SURFD_FAIL(SURFD_ERR_UNSUPPORTED, "surfd_xattn_create: more than %ld features (query_dim or heads x dim_head) are not supported", XA_MAX_FEATURES);
     if (context_dim <= 0) context_dim = query_dim;                  // default(context_dim, query_dim), attention.py:156
     surfd_xattn *a = new surfd_xattn();
     a->qdim = query_dim; a->cdim = context_dim; a->heads = heads; a->dh = dim_head; a->inner = heads * dim_head;
@@ -234,6 +246,8 @@ int surfd_xattn_forward(surfd_xattn *a, const float *x, const float *context, co
     }
     if (M < 1) SURFD_FAIL(SURFD_ERR_ARG, "surfd_xattn_forward: empty context (softmax over zero keys)");
     if ((long)B * a->heads > 65535) SURFD_FAIL(SURFD_ERR_UNSUPPORTED, "surfd_xattn_forward: batch x heads > 65535");
+    if ((long)B * N > XA_MAX_ROWS || (long)B * M > XA_MAX_ROWS)     // refused before anything is allocated or launched
+        SURFD_FAIL(SURFD_ERR_UNSUPPORTED, "surfd_xattn_forward: more than %ld token rows (b x n or b x m) are not supported", XA_MAX_ROWS);
     hipStream_t st = as_stream(s);
     const size_t nq = (size_t)B * N * a->inner, nk = (size_t)B * M * a->inner;
     const size_t need = 2 * nq + 2 * nk;
