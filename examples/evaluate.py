@@ -38,7 +38,10 @@ everywhere).  The JSON then records ``normal_consistency`` and ``normals_k`` amo
 ``--paired --self_intersections`` adds, for the GENERATED item of every pair, ``self_intersecting_faces`` (the share of its faces
 with area that pass through another face of the same mesh), ``self_intersecting_pairs`` (how many pairs of faces do) and
 ``degenerate_faces`` (faces without area), plus their means (surfd_amd/meshintersect.py: exact integer predicates on the raw
-file's vertices snapped to the finest lattice that holds them; touching and T-junctions count).  ``--paired --collisions`` adds
+file's vertices snapped to the finest lattice that holds them; touching and T-junctions count).  ``--paired --topology`` adds,
+for the GENERATED item of every pair, ``topology``: the numbers of surfd_amd.meshtopo (edges by class, Euler characteristic,
+components under the three connectivities, border loops and the largest, closed, edge_manifold, orientable,
+consistently_oriented) on the file's own indices, and their means as ``topology_*``.  ``--paired --collisions`` adds
 ``colliding_faces``: the share of the generated item's faces that pass through or touch a face of the reference item, both in
 the frame of the raw files, no normalisation.  Both need meshes: a pair with an ``.npz`` item where a mesh is needed is listed
 under ``skipped``.
@@ -78,6 +81,7 @@ def parse(argv=None):
     ap.add_argument("--normals_k", type=int, default=16, metavar="K", help="--normal_consistency: neighbours per estimated normal (3 .. 64)")
     ap.add_argument("--self_intersections", action="store_true", help="--paired: also report the self-intersections of every generated mesh")
     ap.add_argument("--collisions", action="store_true", help="--paired: also report the faces of every generated mesh that meet its reference mesh")
+    ap.add_argument("--topology", action="store_true", help="--paired: also report the topology of every generated mesh (pieces, holes, manifoldness)")
     ap.add_argument("--output", default="metrics.json")
     return ap.parse_args(argv)
 
@@ -210,7 +214,23 @@ def intersection_scores(gen_items, ref_items, a):
     return items, skipped
 
 
+def topology_scores(gen_items):
+    """-> (per-item dict, skipped ids) of --topology: surfd_amd.meshtopo.MeshTopology.summary() of the generated mesh without its
+    per-patch list, under the key ``topology``"""
+    from surfd_amd import meshtopo
+    items, skipped = {}, []
+    for name in gen_items:
+        gen = _mesh_on_device(gen_items[name])
+        if gen is None:
+            skipped.append(name)
+            continue
+        items[name] = {"topology": {k: v for k, v in meshtopo.MeshTopology(gen[1], gen[0].shape[0]).summary().items() if k != "patches"}}
+    return items, skipped
+
+
 def run(a):
+    if a.topology and not a.paired:
+        raise SystemExit("--topology describes the generated item of every pair: it needs --paired")
     if a.self_intersections and not a.paired:
         raise SystemExit("--self_intersections scores the generated item of every pair: it needs --paired")
     if a.collisions and not a.paired:
@@ -265,6 +285,17 @@ def run(a):
             for k in ("self_intersecting_faces", "self_intersecting_pairs", "degenerate_faces", "colliding_faces"):
                 if scores and k in next(iter(scores.values())):
                     out["mean"][k] = float(np.mean([s[k] for s in scores.values()], dtype=np.float64))
+            out["skipped"] = sorted(set(out.get("skipped", [])) | set(skipped))
+        if a.topology:
+            out["options"]["topology"] = True
+            scores, skipped = topology_scores(gen_items)
+            for name, s in scores.items():
+                out["items"][name].update(s)
+            for k in ("components_vertex", "border_loops", "non_manifold_edges"):
+                if scores:
+                    out["mean"]["topology_" + k] = float(np.mean([s["topology"][k] for s in scores.values()], dtype=np.float64))
+            if scores:
+                out["mean"]["topology_closed"] = float(np.mean([s["topology"]["closed"] for s in scores.values()], dtype=np.float64))
             out["skipped"] = sorted(set(out.get("skipped", [])) | set(skipped))
     else:
         m = cloudmetrics.compute_all_metrics(gen, ref, chunk=a.chunk)

@@ -20,7 +20,10 @@ is the signed distance clipped to +-0.1, negative inside, ``gradients`` carries 
 (10 000) points of the surface with label 0 and gradient 0 come first in ``coords``.  The sign is the parity of the mesh's
 crossings along +z from the query and means something for a closed mesh only; ``--signed --sign winding`` takes it from the
 generalized winding number instead (surfd_amd/winding.py: |w| >= 1/2 is inside), which survives small holes and needs
-consistently oriented faces.  The same random numbers are drawn either way.  Without the flags nothing changes.
+consistently oriented faces.  ``--orient`` gives them that first (surfd_amd/meshtopo.py: every manifold patch consistent, closed
+patches outward; a patch that cannot be oriented stops the run) and ``--orient --weld`` takes the topology from the mesh with
+coincident vertices welded, which is what dataset meshes that arrive as unwelded soups of mixed orientation need.  The written
+``vertices`` / ``triangles`` stay the file's.  The same random numbers are drawn either way.  Without the flags nothing changes.
 
 ``--accel bvh`` searches the mesh through the box hierarchy of csrc/meshbvh.hip instead of its tiles: the files are the same
 bytes.  The rays behind the sign of ``--signed`` go 4 to 24 times faster; the closest-point search does not yet (DESIGN.md
@@ -52,6 +55,10 @@ def parse(argv=None):
     ap.add_argument("--signed", action="store_true", help="signed distances (negative inside) instead of unsigned ones; closed meshes only")
     ap.add_argument("--sign", choices=("parity", "winding"), default="parity",
                     help="with --signed: inside / outside by crossing parity (closed meshes) or by winding number (meshes with holes)")
+    ap.add_argument("--orient", action="store_true",
+                    help="with --signed --sign winding: give the faces a consistent, outward winding first (surfd_amd/meshtopo.py)")
+    ap.add_argument("--weld", action="store_true",
+                    help="with --orient: take the topology from the mesh with coincident vertices welded (for soups whose faces share no indices)")
     ap.add_argument("--num_queries_on_surface", type=int, default=10_000, help="with --signed: on-surface queries put in front")
     ap.add_argument("--accel", choices=("tiles", "bvh"), default="tiles",
                     help="how the mesh is searched: its tiles, or the box hierarchy (the same bytes; faster for the rays of --signed)")
@@ -78,10 +85,17 @@ def prepare_one(path, a):
     vd, td = v.cuda(), t.cuda()
     pcd = meshprep.sample_points_uniformly(vd, td, a.num_surface_points)                       # preprocess_udfs.py:126-127
     if a.signed:
-        coords, labels, gradients = meshprep.compute_sdf_from_mesh(vd, td, num_surface_points=a.num_surface_points,
+        extra = {"accel": a.accel} if a.accel != "tiles" else {}
+        vs, ts = vd, td
+        if a.orient:
+            from surfd_amd import meshtopo
+            if a.weld:                                         # the sign comes from the welded mesh: the same surface, shared indices
+                vs, ts, _ = meshtopo.weld_vertices(vd, td)
+            extra["orient"] = "outward"
+        coords, labels, gradients = meshprep.compute_sdf_from_mesh(vs, ts, num_surface_points=a.num_surface_points,
                                                                    num_queries_on_surface=a.num_queries_on_surface,
                                                                    num_queries_per_std=list(a.num_queries_per_std), max_dist=a.max_dist,
-                                                                   sign=a.sign, **({"accel": a.accel} if a.accel != "tiles" else {}))
+                                                                   sign=a.sign, **extra)
     else:
         coords, labels, gradients = meshprep.compute_udf_from_mesh(vd, td, num_surface_points=a.num_surface_points,
                                                                    num_queries_per_std=list(a.num_queries_per_std), max_dist=a.max_dist,
@@ -99,6 +113,10 @@ def run(a):
         raise SystemExit(f"item ids must be unique: {names}")
     if a.sign != "parity" and not a.signed:
         raise SystemExit("--sign chooses the sign of --signed items: it needs --signed")
+    if a.orient and a.sign != "winding":
+        raise SystemExit("--orient re-orients the faces for the winding number: it needs --signed --sign winding")
+    if a.weld and not a.orient:
+        raise SystemExit("--weld welds the mesh whose topology --orient uses: it needs --orient")
     if not torch.cuda.is_available():
         raise SystemExit("preprocess_udfs.py runs on the GPU (no CPU fallback)")
     os.makedirs(a.output_dir, exist_ok=True)

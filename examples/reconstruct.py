@@ -55,6 +55,8 @@ def parse(argv=None):
                          "(the same numbers; not faster yet for closest points: DESIGN.md section 8.11)")
     ap.add_argument("--mesh_quality", action="store_true",
                     help="--metrics: also record self_intersecting_faces, the share of the reconstruction's faces that pass through another")
+    ap.add_argument("--topology", action="store_true",
+                    help="--metrics: also record the reconstruction's topology (surfd_amd.meshtopo): pieces, holes, manifoldness, orientation")
     ap.add_argument("--preview", type=int, default=0, metavar="N",
                     help="also write N orbit views (shaded / depth / normal PNGs, surfd_amd.render) of every mesh; 0 = none")
     return ap.parse_args(argv)
@@ -124,13 +126,15 @@ def load_models(ae_dir):
     return encoder, decoder.cuda().eval(), size_latent
 
 
-def item_metrics(path, verts, faces, field, seed, mesh_quality=False, accel="tiles"):
+def item_metrics(path, verts, faces, field, seed, mesh_quality=False, accel="tiles", topology=False):
     """what --metrics records for one item, or None where the input carries no mesh: mesh_distance between the reconstruction
     and the original; the IoU of their surface voxels on a 64^3 grid over [-1, 1]^3 (voxel_iou_surface_64); the normal
     consistency of 16 Ki = 16 384 surface points per mesh with their face normals, unsigned (normal_consistency_16: the number
     counts samples, no neighbourhood size enters); and, where the file has 'coords' / 'labels', the mean absolute error of the
     decoder's UDF at those queries.  ``mesh_quality`` adds self_intersecting_faces: the share of the reconstruction's faces with
-    area that pass through or touch another of its faces beyond what neighbours share (surfd_amd.meshintersect).  ``accel``:
+    area that pass through or touch another of its faces beyond what neighbours share (surfd_amd.meshintersect).  ``topology``
+    adds topology: the numbers of surfd_amd.meshtopo.MeshTopology.summary() for the reconstruction without its per-patch list
+    (edges by class, Euler characteristic, components, border loops, closed, edge_manifold, orientable, ...).  ``accel``:
     how mesh_distance searches the two meshes ("tiles" or "bvh": the same numbers)"""
     from surfd_amd import meshprep
     if not path.endswith(".npz"):
@@ -156,6 +160,9 @@ def item_metrics(path, verts, faces, field, seed, mesh_quality=False, accel="til
         if mesh_quality:
             from surfd_amd import meshintersect
             out["self_intersecting_faces"] = meshintersect.self_intersections(rv, rt, return_pairs=False)["fraction"]
+        if topology:
+            from surfd_amd import meshtopo
+            out["topology"] = {k: v for k, v in meshtopo.MeshTopology(rt, len(verts)).summary().items() if k != "patches"}
     if coords is not None:
         pred = torch.cat([field(coords[i:i + 2 ** 16]) for i in range(0, len(coords), 2 ** 16)])
         out["udf_mean_abs_error"] = float((pred.reshape(-1) - labels).abs().double().mean())
@@ -171,6 +178,8 @@ def run(a):
         raise SystemExit("--accel chooses how --metrics measures: it needs --metrics")
     if a.mesh_quality and not a.metrics:
         raise SystemExit("--mesh_quality adds to metrics.json: it needs --metrics")
+    if a.topology and not a.metrics:
+        raise SystemExit("--topology adds to metrics.json: it needs --metrics")
     os.makedirs(a.output_dir, exist_ok=True)
     inputs = list(a.inputs)
     if a.synthetic:
@@ -224,7 +233,7 @@ def run(a):
                                        torch.as_tensor(np.ascontiguousarray(faces, dtype=np.int64)).reshape(-1, 3).cuda(), n_views=a.preview, size=512)
             written += render.save_views(a.output_dir, os.path.splitext(os.path.basename(path))[0], views)
         if a.metrics:
-            m = item_metrics(files[k], verts, faces, field, a.seed, a.mesh_quality, a.accel)
+            m = item_metrics(files[k], verts, faces, field, a.seed, a.mesh_quality, a.accel, a.topology)
             if m is not None:
                 metrics[item] = m
     if a.metrics:

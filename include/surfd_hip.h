@@ -595,6 +595,68 @@ int surfd_winding_num_triangles(const surfd_winding *m);
 int surfd_winding_eval(surfd_winding *m, const float *points, int64_t Q, int flags, double *w, surfd_stream s);
 
 /* ------------------------------------------------------------------------------------ */
+/* Mesh topology: edges and their valences, face neighbours, connected components,        */
+/* border loops, a consistent orientation of every manifold patch, exact welding.  No     */
+/* reference counterpart (the reference leaves these to trimesh / pymeshlab on the host). */
+/* Integer work on the index array; every output is a function of the input alone, not    */
+/* of launch geometry or of the order in which atomics arrive (csrc/meshtopo.hip states   */
+/* the contract and why its lock-free union-find terminates; the tests restate the        */
+/* contract sequentially in numpy).                                                       */
+/* ------------------------------------------------------------------------------------ */
+typedef struct surfd_meshtopo surfd_meshtopo;
+#define SURFD_MESHTOPO_VERTEX 0     /* connectivity: faces that share a vertex */
+#define SURFD_MESHTOPO_EDGE 1       /* connectivity: faces that share an edge of any valence */
+#define SURFD_MESHTOPO_MANIFOLD 2   /* connectivity: faces that share an edge of valence 2 */
+/* no reference counterpart; trimesh's edges_unique / face_adjacency, built once and kept:
+ * triangles[F,3] int32 on the device (copied; not referenced after the call), V the number of vertices they may name.  Half-edge
+ * h = 3 f + c runs from t[f, c] to t[f, (c + 1) % 3]; a face with two equal indices is degenerate and takes part in nothing.
+ * One 64-bit key lo << 32 | hi per half-edge, a stable radix sort, run lengths: the edges in ascending (lo, hi) order.
+ * F >= 0 (F = 0 gives empty outputs), V >= 0, 3 F < 2^31; an index outside [0, V) is SURFD_ERR_ARG with the first such face in
+ * the text, checked on the device and never reported as a fault.  Allocates every workspace the calls below use.  host-sync
+ * (the number of edges is read back). */
+int surfd_meshtopo_create(const int32_t *triangles, int F, int V, surfd_stream s, surfd_meshtopo **out);
+void surfd_meshtopo_destroy(surfd_meshtopo *m);
+/* no reference counterpart; the sizes the arrays of surfd_meshtopo_read have:
+ * faces F, edges E, degenerate faces, and the vertices that a non-degenerate face names; each nullable, host memory. */
+int surfd_meshtopo_counts(const surfd_meshtopo *m, int64_t *faces, int64_t *edges, int64_t *degenerate, int64_t *referenced);
+/* no reference counterpart; trimesh's edges_unique, edges_unique_inverse, face_adjacency:
+ * device arrays, each nullable: edges[E,2] (lo, hi), valence[E], edge_offsets[E+1] and edge_halfedges[3 (F - degenerate)] (the
+ * half-edges of edge e, ascending), face_edges[F,3] (the edge of half-edge 3 f + c; -1 in a degenerate face),
+ * face_neighbors[F,3] (the other face across a valence-2 edge, -1 across a border edge and in a degenerate face, -2 across an
+ * edge of valence >= 3), degenerate[F] (bytes 0 / 1).  Copies on the stream; does not sync. */
+int surfd_meshtopo_read(const surfd_meshtopo *m, int32_t *edges, int32_t *valence, int32_t *edge_offsets, int32_t *edge_halfedges,
+                        int32_t *face_edges, int32_t *face_neighbors, unsigned char *degenerate, surfd_stream s);
+/* no reference counterpart; trimesh's Trimesh.split / graph.connected_components over face adjacency:
+ * labels[F] int32 on the device: the components under the given connectivity, numbered in ascending order of their lowest
+ * face; -1 for a degenerate face.  count (host) = the number of components.  A lock-free union-find over an explicit pair list:
+ * the larger root is hooked under the smaller, so a component's root is its smallest node whatever the schedule.  host-sync
+ * (count is read back).  A handle serves one stream and one host thread at a time (the workspaces are the handle's). */
+int surfd_meshtopo_components(surfd_meshtopo *m, int connectivity, int32_t *labels, int64_t *count, surfd_stream s);
+/* no reference counterpart; trimesh's Trimesh.outline / pymeshlab's border loops:
+ * labels[E] int32 on the device: for every border edge (valence 1) the loop it lies on, loops being the components of the
+ * border edges under "share a vertex", numbered in ascending order of their lowest edge; -1 for every other edge.
+ * irregular[E] (bytes, nullable): 1 for a border edge with an end point that lies on a number of border edges other than two;
+ * a loop is simple when none of its edges is irregular.  count (host) = the number of loops.  host-sync. */
+int surfd_meshtopo_border_loops(surfd_meshtopo *m, int32_t *labels, unsigned char *irregular, int64_t *count, surfd_stream s);
+/* no reference counterpart; trimesh's repair.fix_normals (fix_winding, then fix_inversion per body):
+ * flip[F] (bytes): the one assignment under which the two half-edges of every valence-2 edge run in opposite directions and
+ * the lowest face of every manifold component (patch) keeps its winding; 0 throughout a patch that has no such assignment
+ * and in degenerate faces.  orientable[F] (bytes, nullable): 0 for the faces of a patch without one.  patch_face[F] (int32,
+ * nullable): the lowest face of the face's patch, -1 in a degenerate face.  Components of the double cover (2 F nodes), one run
+ * of the union-find however long the patch's diameter.  vertices[V,3] fp32 on the device or NULL; where given, every orientable
+ * patch all of whose edges have valence 2 is then turned as a whole so that its signed volume is positive: the volume is the
+ * integer sum of llrint(det(v0, v1, v2) 2^30 / M^3), M the power of two >= max |coordinate|, so it has no order of addition; 0
+ * leaves the patch.  Patch by patch, no nesting analysis (the shell of a cavity ends up outward too).  Does not sync. */
+int surfd_meshtopo_orient(surfd_meshtopo *m, const float *vertices, unsigned char *flip, unsigned char *orientable, int32_t *patch_face,
+                          surfd_stream s);
+/* no reference counterpart; trimesh's merge_vertices(merge_tex=True, digits_vertex=None), without its rounding:
+ * vertices[V,3] fp32 on the device -> vertex_map[V] int32 (the index of every vertex's survivor AFTER compaction) and
+ * survivor[V] (bytes: 1 where the vertex stays).  Vertices with equal coordinates become one (-0 == +0; a vertex that holds a NaN
+ * equals nothing, itself included); the survivor is the lowest index of its class, survivors keep their order.  No tolerance.
+ * count (host) = the number of survivors.  3 V < 2^31.  host-sync. */
+int surfd_meshtopo_weld(const float *vertices, int V, int32_t *vertex_map, unsigned char *survivor, int64_t *count, surfd_stream s);
+
+/* ------------------------------------------------------------------------------------ */
 /* Point-cloud metrics: nearest neighbours between clouds and the matrix of directed      */
 /* Chamfer means between two sets of clouds.  No reference counterpart (the reference     */
 /* ships no evaluation code): stands for pytorch3d's knn_points(p1, p2, K=1) /            */

@@ -159,6 +159,14 @@ _SIGS = {
     "surfd_winding_destroy": (None, [_P]),
     "surfd_winding_num_triangles": (C.c_int, [_P]),
     "surfd_winding_eval": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P]),
+    "surfd_meshtopo_create": (C.c_int, [_P, C.c_int, C.c_int, _P, C.POINTER(_P)]),
+    "surfd_meshtopo_destroy": (None, [_P]),
+    "surfd_meshtopo_counts": (C.c_int, [_P, c_i64p, c_i64p, c_i64p, c_i64p]),
+    "surfd_meshtopo_read": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "surfd_meshtopo_components": (C.c_int, [_P, C.c_int, _P, c_i64p, _P]),
+    "surfd_meshtopo_border_loops": (C.c_int, [_P, _P, _P, c_i64p, _P]),
+    "surfd_meshtopo_orient": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "surfd_meshtopo_weld": (C.c_int, [_P, C.c_int, _P, _P, c_i64p, _P]),
     "surfd_cloud_nn": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "surfd_cloud_nn_matrix": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_float, _P, _P, _P]),
     "surfd_cloud_fps_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),

@@ -32,6 +32,7 @@ SOURCES.insert(SOURCES.index("mcubes.cpp"), "raycast.hip")           # ray casti
 SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshintersect.hip")     # self-intersections and collisions of meshes (surfd_amd/meshintersect.py)
 SOURCES.insert(SOURCES.index("mcubes.cpp"), "winding.hip")           # generalized winding numbers of meshes (surfd_amd/winding.py)
 SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshbvh.hip")           # box hierarchy over a mesh for raycast.hip / meshdist.hip (accel="bvh")
+SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshtopo.hip")          # edges, components, border loops, orientation, weld (surfd_amd/meshtopo.py)
 # cloudnn.hip: without SLP vectorisation the pair test stays 8 plain fp32 instructions + half a v_min3; with it the compiler packs
 # half of them into v_pk_*_f32 (issued at half rate, so nothing is gained) and pads the loop with s_nop
 # cloudnormals.hip: the same pair test in its scan; measured 0.5-2.7 % slower with the vectoriser on

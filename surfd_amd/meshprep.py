@@ -381,9 +381,10 @@ def _check_method(name: str, method: str) -> None:
         raise ValueError(f"{name} must be 'parity' or 'winding', got {method!r}")
 
 
-def _as_scene(vertices, triangles, method: str = "parity", accel: str = "tiles"):
+def _as_scene(vertices, triangles, method: str = "parity", accel: str = "tiles", orient=False):
     """the scene that answers inside / outside by ``method``: a given one of that kind (triangles None), or a new one.  ``accel``
-    goes to a new RaycastingScene and its mesh_distance(); a WindingScene has no hierarchy and ignores it."""
+    goes to a new RaycastingScene and its mesh_distance(); a WindingScene has no hierarchy and ignores it.  ``orient`` goes to a new
+    WindingScene (a given scene keeps the orientation it was made with); the parity does not depend on the winding."""
     from .raycast import RaycastingScene
     from .winding import WindingScene
     _check_accel(accel)
@@ -392,17 +393,20 @@ def _as_scene(vertices, triangles, method: str = "parity", accel: str = "tiles")
         raise TypeError(f"a {other.__name__} cannot answer by {method!r}: pass a {kind.__name__} or the mesh itself")
     if isinstance(vertices, kind) and triangles is None:
         return vertices
-    return RaycastingScene(vertices, triangles, accel=accel) if kind is RaycastingScene else kind(vertices, triangles)
+    if orient is not False and method != "winding":
+        raise ValueError("orient belongs to the winding number: the crossing parity does not depend on the faces' winding")
+    return RaycastingScene(vertices, triangles, accel=accel) if kind is RaycastingScene else kind(vertices, triangles, orient=orient)
 
 
 def is_inside(vertices: Tensor, triangles: Tensor, points: Tensor, nsamples: int = 1, method: str = "parity",
-              accel: str = "tiles") -> Tensor:
+              accel: str = "tiles", orient=False) -> Tensor:
     """[N] bool: is the point inside the mesh.  ``method="parity"``: the parity of the number of crossings of the ray from the
     point along +z (csrc/raycast.hip); ``nsamples=3`` also asks +x and +y and takes the majority.  The parity means something on a
     closed mesh only (surfd_amd/raycast.py, ``compute_occupancy(..., return_votes=True)`` tells); on a mesh with holes use
     ``method="winding"``: |winding number| >= 1/2 (surfd_amd/winding.py), which needs consistently oriented faces instead and
     takes no ``nsamples``.  ``vertices`` may be a RaycastingScene, or a WindingScene for "winding" (triangles None).
-    ``accel``: how a new RaycastingScene casts ("tiles" or "bvh"; the same answers)."""
+    ``accel``: how a new RaycastingScene casts ("tiles" or "bvh"; the same answers).  ``orient`` (method="winding" only): True or
+    "outward" re-orients the faces first (surfd_amd/meshtopo.py), for meshes whose faces are not consistently oriented."""
     from .raycast import RaycastingScene, _check_nsamples
     from .winding import WindingScene
     _check_method("method", method)
@@ -414,20 +418,20 @@ def is_inside(vertices: Tensor, triangles: Tensor, points: Tensor, nsamples: int
     if method == "winding":
         if nsamples != 1:
             raise ValueError("nsamples belongs to method='parity': the winding number casts no rays")
-        return _as_scene(vertices, triangles, method).compute_occupancy(points) > 0
-    return _as_scene(vertices, triangles, accel=accel).compute_occupancy(points, nsamples) > 0
+        return _as_scene(vertices, triangles, method, orient=orient).compute_occupancy(points) > 0
+    return _as_scene(vertices, triangles, accel=accel, orient=orient).compute_occupancy(points, nsamples) > 0
 
 
 def compute_sdf_and_gradients(vertices: Tensor, triangles: Tensor, queries: Tensor, sign: str = "parity",
-                              accel: str = "tiles") -> Tuple[Tensor, Tensor]:
+                              accel: str = "tiles", orient=False) -> Tuple[Tensor, Tensor]:
     """AutoEncoder/utils.py:242-264: sdf = the distance to the mesh, negative inside (open3d's compute_signed_distance: the
     parity of the crossings along +z), and gradients = sign(sdf) * F.normalize(q - c) for the closest point c of the mesh.  A
     query on the surface has sdf 0 and a zero gradient.  ``sign="winding"`` takes inside / outside from the winding number
     instead (surfd_amd/winding.py: for meshes with holes).  ``vertices`` may be a RaycastingScene, or a WindingScene for
     "winding" (triangles None).  ``accel``: how a new RaycastingScene casts and measures ("tiles" or "bvh"; the same bits);
-    with ``sign="winding"`` it is ignored, a WindingScene has no hierarchy."""
+    with ``sign="winding"`` it is ignored, a WindingScene has no hierarchy.  ``orient`` (sign="winding" only): as in is_inside."""
     _check_method("sign", sign)
-    scene = _as_scene(vertices, triangles, sign, accel)
+    scene = _as_scene(vertices, triangles, sign, accel, orient=orient)
     sdf = scene.compute_signed_distance(queries)
     offset = queries - scene.mesh_distance().closest(queries)[1]
     return sdf, torch.sign(sdf)[:, None] * F.normalize(offset, dim=-1)
@@ -437,13 +441,13 @@ def compute_sdf_from_mesh(vertices: Tensor, triangles: Tensor, num_surface_point
                           queries_stds: List[float] = [0.003, 0.01, 0.1], num_queries_per_std: List[int] = [5_000, 4_000, 500, 500],
                           coords_range: Tuple[float, float] = (-1.0, 1.0), max_dist: float = 0.1, convert_to_bce_labels: bool = False,
                           use_cuda: bool = True, input_queries: Optional[Tensor] = None,
-                          sign: str = "parity", accel: str = "tiles") -> Tuple[Tensor, Tensor, Tensor]:
+                          sign: str = "parity", accel: str = "tiles", orient=False) -> Tuple[Tensor, Tensor, Tensor]:
     """AutoEncoder/utils.py:317-363 -> (queries, values, gradients): a surface cloud, queries around it (or ``input_queries``),
     their SDF clipped to [-max_dist, max_dist] and its gradients; in front of them ``num_queries_on_surface`` points drawn on the
     surface with value 0 and gradient 0.  ``convert_to_bce_labels`` turns the values into 1 - values / max_dist, as the
     reference does.  Everything stays on the mesh's device and the random numbers come from that device's global RNG, as in
     compute_udf_from_mesh.  ``sign``: "parity" (the reference's) or "winding", as in compute_sdf_and_gradients; the same
-    random numbers are drawn either way.  ``accel``: as in compute_sdf_and_gradients."""
+    random numbers are drawn either way.  ``accel`` and ``orient``: as in compute_sdf_and_gradients."""
     _check_method("sign", sign)
     _check_accel(accel)
     _check_mesh(vertices, triangles)
@@ -453,7 +457,7 @@ def compute_sdf_from_mesh(vertices: Tensor, triangles: Tensor, num_surface_point
     if queries is None:
         cloud = sample_points_uniformly(vertices, triangles, num_surface_points)
         queries = sample_points_around_pcd(cloud, queries_stds, num_queries_per_std, coords_range, vertices.device)
-    sdf, gradients = compute_sdf_and_gradients(vertices, triangles, queries, sign, accel=accel)
+    sdf, gradients = compute_sdf_and_gradients(vertices, triangles, queries, sign, accel=accel, orient=orient)
     values = sdf.clamp(-max_dist, max_dist)
     on_surface = sample_points_uniformly(vertices, triangles, num_queries_on_surface)
     queries = torch.cat([on_surface, queries], dim=0)

@@ -13,7 +13,9 @@ or culled: Q x F terms.
 
 w depends on the ORIENTATION of the faces.  A wholly inverted mesh gives -w, which ``|w| >= threshold`` forgives; a mesh whose
 faces are not consistently oriented (tests/raycast_ref.cube_flipped) gives values between about -0.67 and 0.66 that mean nothing,
-while its crossing parity is fine: use RaycastingScene there.  Re-orienting such a mesh is not done here.
+while its crossing parity is fine.  ``orient=True`` re-orients such a mesh first (surfd_amd/meshtopo.py: every manifold patch gets
+a consistent winding, its lowest face keeps its own); ``orient="outward"`` also turns closed patches so that their volume is
+positive.  A patch that has no consistent winding (a Moebius band) raises.  The default leaves the triangles as they came.
 The fp64 bits of a query's w do not depend on the other queries of the call, on its position, or on the launch geometry.
 """
 from __future__ import annotations
@@ -42,7 +44,7 @@ class WindingScene:
     checks the vertices and the index range and the library's create reads its flags; the calls themselves do not sync.  One
     stream at a time per object: the library keeps its partial sums in a workspace of the handle."""
 
-    def __init__(self, vertices: Tensor, triangles: Tensor):
+    def __init__(self, vertices: Tensor, triangles: Tensor, orient: Union[bool, str] = False):
         _check_mesh(vertices, triangles, need_cuda=False)          # shapes and dtypes first, the CPU-tensor refusal last
         _check_mesh(vertices, triangles)
         if not bool(torch.isfinite(vertices).all()):
@@ -53,6 +55,9 @@ class WindingScene:
         t = triangles.long()
         if int(t.min()) < 0 or int(t.max()) >= v.shape[0]:
             raise ValueError(f"triangles name vertices outside [0, {v.shape[0]})")
+        if orient is not False:
+            from .meshtopo import oriented_for_winding
+            t = oriented_for_winding(v, t, orient)
         self.device = v.device
         self.vertices, self.triangles = v, t
         ts = t.to(torch.int32).contiguous()
@@ -112,8 +117,8 @@ class WindingScene:
             pass
 
 
-def winding_number(vertices: Tensor, triangles: Tensor, points: Tensor) -> Tensor:
-    """[N] float64: the winding number of the mesh at every point (one WindingScene, one call)"""
+def winding_number(vertices: Tensor, triangles: Tensor, points: Tensor, orient: Union[bool, str] = False) -> Tensor:
+    """[N] float64: the winding number of the mesh at every point (one WindingScene, one call).  ``orient``: see WindingScene."""
     _check_mesh(vertices, triangles, need_cuda=False)
     _check_points("points", points, need_cuda=False)
-    return WindingScene(vertices, triangles).winding_number(points)
+    return WindingScene(vertices, triangles, orient=orient).winding_number(points)
