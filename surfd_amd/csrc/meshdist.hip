@@ -73,10 +73,11 @@
 //
 // Hazards: the only LDS reuse is the record chunk of md_closest_kernel, bracketed by a barrier on both sides (__syncthreads_or
 // in front of the staging stores, __syncthreads() behind them); cross-lane values move with __shfl_xor / __all only.  The only
-// atomics are integer ones (the skipped-tile count, one per wave that holds a query, and the bad-index flag).  A handle's
-// partial-result workspace is shared by its calls: one stream at a time per handle.
+// atomics are integer ones (the skipped-tile count, one per wave that holds a query, and the bad-index flag).  A call's partial
+// results live in the handle's arena (meshscene.h).
 #include "common.h"
 #include "meshbvh.h"
+#include "meshscene.h"
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -457,51 +458,28 @@ struct surfd_mesh {
     float4 *rec = nullptr;            // [F] records of 4 float4
     float4 *tile_sph = nullptr;       // [ntile]
     float4 *chunk_sph = nullptr;      // [nchunk]
-    mutable void *ws = nullptr;       // partial results of surfd_mesh_closest (grows)
-    mutable size_t ws_bytes = 0;
+    mutable DeviceArena ws;           // partial results of surfd_mesh_closest: the calls take a const handle
     MeshBvh bvh;                      // the hierarchy of surfd_mesh_build_bvh (meshbvh.hip)
 };
-
-static int md_ws(const surfd_mesh *m, size_t bytes, hipStream_t st) {
-    if (bytes <= m->ws_bytes) return SURFD_OK;
-    HIP_TRY(hipStreamSynchronize(st));                // the previous call's kernels may still read the old arena
-    (void)hipFree(m->ws); m->ws = nullptr; m->ws_bytes = 0;
-    HIP_TRY(hipMalloc(&m->ws, bytes));
-    m->ws_bytes = bytes;
-    return SURFD_OK;
-}
-
-// splits of the chunk range per query block: about 2048 workgroups over the chip (8 per CU), whole chunks per split
-static void md_splits(int Q, int nchunk, int *S, int *span) {
-    const long qb = ceil_div<long>(Q, MD_CHUNK);
-    long s = std::max<long>(1, ceil_div<long>(2048, qb));
-    s = std::min<long>({s, (long)MD_MAX_SPLITS, (long)nchunk});
-    *span = (int)ceil_div<long>(nchunk, s);
-    *S = ceil_div(nchunk, *span);
-}
 
 extern "C" {
 
 int surfd_mesh_create(const float *vertices, int V, const int32_t *triangles, int F, surfd_stream s, surfd_mesh **out) {
-    if (!out) SURFD_FAIL(SURFD_ERR_ARG, "surfd_mesh_create: null out");
-    *out = nullptr;
-    if (!vertices || !triangles) SURFD_FAIL(SURFD_ERR_ARG, "surfd_mesh_create: null vertices or triangles");
-    if (V < 1 || F < 1) SURFD_FAIL(SURFD_ERR_ARG, "surfd_mesh_create: V = %d, F = %d must be positive", V, F);
-    if (F > (1 << 28)) SURFD_FAIL(SURFD_ERR_UNSUPPORTED, "surfd_mesh_create: F = %d is beyond the supported size", F);
+    int rc = mesh_create_args("surfd_mesh_create", vertices, V, triangles, F, out, 1 << 28);
+    if (rc != SURFD_OK) return rc;
     hipStream_t st = as_stream(s);
     surfd_mesh *m = new surfd_mesh();
     m->F = F;
     m->ntile = ceil_div(F, MD_TILE);
     m->nchunk = ceil_div(F, MD_CHUNK);
-    int *bad = nullptr;
-    int rc = SURFD_OK, flag = 0;
+    CreateFlags bad(1);
+    int flag = 0;
     auto run = [&]() -> int {
         HIP_TRY(hipMalloc(&m->rec, (size_t)F * sizeof(MdRec)));
         HIP_TRY(hipMalloc(&m->tile_sph, (size_t)m->ntile * sizeof(float4)));
         HIP_TRY(hipMalloc(&m->chunk_sph, (size_t)m->nchunk * sizeof(float4)));
-        HIP_TRY(hipMalloc(&bad, sizeof(int)));
-        HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int), st));
-        hipLaunchKernelGGL(md_prepare_kernel, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, st, vertices, V, triangles, F, m->rec, bad);
+        if (int e = bad.init(st)) return e;
+        hipLaunchKernelGGL(md_prepare_kernel, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, st, vertices, V, triangles, F, m->rec, bad.dev);
         LAUNCH_CHECK();
         hipLaunchKernelGGL(md_bounds_kernel, dim3((unsigned)ceil_div(m->ntile, 64)), dim3(64), 0, st, (const float4 *)m->rec, F, MD_TILE,
                            m->ntile, m->tile_sph);
@@ -509,16 +487,10 @@ int surfd_mesh_create(const float *vertices, int V, const int32_t *triangles, in
         hipLaunchKernelGGL(md_bounds_kernel, dim3((unsigned)ceil_div(m->nchunk, 64)), dim3(64), 0, st, (const float4 *)m->rec, F, MD_CHUNK,
                            m->nchunk, m->chunk_sph);
         LAUNCH_CHECK();
-        HIP_TRY(hipMemcpyAsync(&flag, bad, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return SURFD_OK;
+        return bad.read(&flag, st);
     };
     rc = run();
-    (void)hipFree(bad);
-    if (rc == SURFD_OK && flag) {
-        set_error("surfd_mesh_create: a triangle names a vertex outside [0, %d)", V);
-        rc = SURFD_ERR_ARG;
-    }
+    if (rc == SURFD_OK && flag) rc = mesh_bad_index("surfd_mesh_create", V);
     if (rc != SURFD_OK) { surfd_mesh_destroy(m); return rc; }
     *out = m;
     return SURFD_OK;
@@ -526,7 +498,8 @@ int surfd_mesh_create(const float *vertices, int V, const int32_t *triangles, in
 
 void surfd_mesh_destroy(surfd_mesh *m) {
     if (!m) return;
-    (void)hipFree(m->rec); (void)hipFree(m->tile_sph); (void)hipFree(m->chunk_sph); (void)hipFree(m->ws);
+    (void)hipFree(m->rec); (void)hipFree(m->tile_sph); (void)hipFree(m->chunk_sph);
+    m->ws.release();
     bvh_free(&m->bvh);
     delete m;
 }
@@ -542,11 +515,11 @@ int surfd_mesh_closest(const surfd_mesh *m, const float *queries, int Q, int fla
     if (!queries) SURFD_FAIL(SURFD_ERR_ARG, "surfd_mesh_closest: null queries");
     if (Q > (1 << 28)) SURFD_FAIL(SURFD_ERR_UNSUPPORTED, "surfd_mesh_closest: Q = %d is beyond the supported size", Q);
     hipStream_t st = as_stream(s);
-    int S, span, rc;
-    md_splits(Q, m->nchunk, &S, &span);
+    const Split sp = split_units(Q, MD_CHUNK, m->nchunk, MD_MAX_SPLITS);      // splits of the chunk range per query block
+    const int S = sp.S, span = sp.span;
     const size_t np = (size_t)S * Q;
-    if ((rc = md_ws(m, 2 * np * sizeof(float), st))) return rc;
-    float *pd = (float *)m->ws;
+    if (int rc = m->ws.reserve(2 * np * sizeof(float), st)) return rc;
+    float *pd = (float *)m->ws.ptr;
     int *pi = (int *)(pd + np);
     if (skipped_tiles) HIP_TRY(hipMemsetAsync(skipped_tiles, 0, sizeof(int64_t), st));
     const dim3 grid((unsigned)ceil_div(Q, MD_CHUNK), (unsigned)S);
@@ -582,8 +555,8 @@ int surfd_mesh_closest_bvh(const surfd_mesh *m, const float *queries, int Q, int
     if (Q > (1 << 28)) SURFD_FAIL(SURFD_ERR_UNSUPPORTED, "surfd_mesh_closest_bvh: Q = %d is beyond the supported size", Q);
     hipStream_t st = as_stream(s);
     int rc;
-    if ((rc = md_ws(m, 2 * (size_t)Q * sizeof(float), st))) return rc;
-    float *pd = (float *)m->ws;
+    if ((rc = m->ws.reserve(2 * (size_t)Q * sizeof(float), st))) return rc;
+    float *pd = (float *)m->ws.ptr;
     int *pi = (int *)(pd + Q);
     if (skipped_tiles) HIP_TRY(hipMemsetAsync(skipped_tiles, 0, sizeof(int64_t), st));      // no tiles on this path
     if ((flags & SURFD_MESH_COUNT_VISITS) && (rc = bvh_visits_reset(&m->bvh, st))) return rc;

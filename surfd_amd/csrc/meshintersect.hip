@@ -53,7 +53,9 @@
 // e < 3 cnt with 256 c + cnt <= FB; LDS is indexed with 3 u + 2 < 3 cnt <= 768; box arrays with 2 c + 1 < 2 nchunkB and
 // 2 (8 c + tt) + 1 < 2 ntileB (tt < ceil(cnt / 32), so 8 c + tt < ntileB); hits with i < FA and j = 256 c + u < FB; pairs with a
 // slot < capacity only.  Hazards: the LDS chunk is bracketed by a barrier on both sides.  No workgroup waits for another.
+// The host side of create, the split count and the skipped read-back are meshscene.h's; this handle keeps no arena.
 #include "common.h"
+#include "meshscene.h"
 #include <climits>
 #include <cmath>
 #include <algorithm>
@@ -313,15 +315,6 @@ struct surfd_isect {
     long long last_total = 0;         // the visits the last call with SURFD_ISECT_COUNT_SKIPPED had in all
 };
 
-// splits of the partner chunk range per block of triangles: about 2048 workgroups over the chip (8 per CU), whole chunks per split
-static void mi_splits(int FA, int nchunkB, int *S, int *span) {
-    const long rb = ceil_div<long>(FA, MI_CHUNK);
-    long s = std::max<long>(1, ceil_div<long>(2048, rb));
-    s = std::min<long>({s, (long)MI_MAX_SPLITS, (long)nchunkB});
-    *span = (int)ceil_div<long>(nchunkB, s);
-    *S = ceil_div(nchunkB, *span);
-}
-
 static int mi_run(const char *who, surfd_isect *a, surfd_isect *b, bool self, int flags, int32_t *hits_a, int32_t *hits_b, int64_t *pairs,
                   int64_t capacity, int64_t *count, hipStream_t st) {
     if (!a || !b) SURFD_FAIL(SURFD_ERR_ARG, "%s: null handle", who);
@@ -346,9 +339,9 @@ static int mi_run(const char *who, surfd_isect *a, surfd_isect *b, bool self, in
         a->last_total = total;
         skipped = brute ? nullptr : a->counters + 1;
     }
-    int S, span;
-    mi_splits(a->F, b->nchunk, &S, &span);
-    const dim3 grid((unsigned)ceil_div(a->F, MI_CHUNK), (unsigned)S);
+    const Split sp = split_units(a->F, MI_CHUNK, b->nchunk, MI_MAX_SPLITS);   // splits of the partner chunk range per block of triangles
+    const int span = sp.span;
+    const dim3 grid((unsigned)ceil_div(a->F, MI_CHUNK), (unsigned)sp.S);
 #define MI_LAUNCH(CULL, SELF)                                                                                                        \
     hipLaunchKernelGGL((mi_pair_kernel<CULL, SELF>), grid, dim3(256), 0, st, (const int4 *)a->rec, a->F, (const int4 *)b->rec, b->F, \
                        (const int4 *)b->tile_box, (const int4 *)b->chunk_box, b->nchunk, span, hits_a, hits_b,                       \
@@ -363,10 +356,8 @@ static int mi_run(const char *who, surfd_isect *a, surfd_isect *b, bool self, in
 extern "C" {
 
 int surfd_isect_create(const float *vertices, int V, const int32_t *triangles, int F, int lattice_log2, surfd_stream s, surfd_isect **out) {
-    if (!out) SURFD_FAIL(SURFD_ERR_ARG, "surfd_isect_create: null out");
-    *out = nullptr;
-    if (!vertices || !triangles) SURFD_FAIL(SURFD_ERR_ARG, "surfd_isect_create: null vertices or triangles");
-    if (V < 1 || F < 1) SURFD_FAIL(SURFD_ERR_ARG, "surfd_isect_create: V = %d, F = %d must be positive", V, F);
+    int rc = mesh_create_args("surfd_isect_create", vertices, V, triangles, F, out, INT_MAX);    // the size test below is this file's
+    if (rc != SURFD_OK) return rc;
     if (lattice_log2 < -MI_MAX_LOG2 || lattice_log2 > MI_MAX_LOG2)
         SURFD_FAIL(SURFD_ERR_ARG, "surfd_isect_create: lattice_log2 = %d outside -%d .. %d", lattice_log2, MI_MAX_LOG2, MI_MAX_LOG2);
     if (F > (1 << 28) || V > (1 << 28)) SURFD_FAIL(SURFD_ERR_UNSUPPORTED, "surfd_isect_create: V = %d, F = %d is beyond the supported size", V, F);
@@ -376,20 +367,20 @@ int surfd_isect_create(const float *vertices, int V, const int32_t *triangles, i
     m->L = lattice_log2;
     m->ntile = ceil_div(F, MI_TILE);
     m->nchunk = ceil_div(F, MI_CHUNK);
-    int *q = nullptr, *bad = nullptr;                         // snapped vertices; [0] refused vertices, [1] bad indices
-    int rc = SURFD_OK, flag[2] = {0, 0};
+    int *q = nullptr;                                         // snapped vertices
+    CreateFlags bad(2);                                       // [0] refused vertices, [1] bad indices
+    int flag[2] = {0, 0};
     auto run = [&]() -> int {
         HIP_TRY(hipMalloc(&m->rec, (size_t)F * 3 * sizeof(int4)));
         HIP_TRY(hipMalloc(&m->tile_box, (size_t)m->ntile * 2 * sizeof(int4)));
         HIP_TRY(hipMalloc(&m->chunk_box, (size_t)m->nchunk * 2 * sizeof(int4)));
         HIP_TRY(hipMalloc(&m->counters, 2 * sizeof(unsigned long long)));
         HIP_TRY(hipMalloc(&q, (size_t)V * 3 * sizeof(int)));
-        HIP_TRY(hipMalloc(&bad, 2 * sizeof(int)));
-        HIP_TRY(hipMemsetAsync(bad, 0, 2 * sizeof(int), st));
+        if (int e = bad.init(st)) return e;
         HIP_TRY(hipMemsetAsync(m->counters, 0, 2 * sizeof(unsigned long long), st));
-        hipLaunchKernelGGL(mi_snap_kernel, dim3((unsigned)ceil_div(V, 256)), dim3(256), 0, st, vertices, V, ldexpf(1.f, lattice_log2), q, bad);
+        hipLaunchKernelGGL(mi_snap_kernel, dim3((unsigned)ceil_div(V, 256)), dim3(256), 0, st, vertices, V, ldexpf(1.f, lattice_log2), q, bad.dev);
         LAUNCH_CHECK();
-        hipLaunchKernelGGL(mi_gather_kernel, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, st, (const int *)q, V, triangles, F, m->rec, bad + 1);
+        hipLaunchKernelGGL(mi_gather_kernel, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, st, (const int *)q, V, triangles, F, m->rec, bad.dev + 1);
         LAUNCH_CHECK();
         hipLaunchKernelGGL(mi_bounds_kernel, dim3((unsigned)ceil_div(m->ntile, 64)), dim3(64), 0, st, (const int4 *)m->rec, F, MI_TILE, m->ntile,
                            m->tile_box);
@@ -397,19 +388,15 @@ int surfd_isect_create(const float *vertices, int V, const int32_t *triangles, i
         hipLaunchKernelGGL(mi_bounds_kernel, dim3((unsigned)ceil_div(m->nchunk, 64)), dim3(64), 0, st, (const int4 *)m->rec, F, MI_CHUNK,
                            m->nchunk, m->chunk_box);
         LAUNCH_CHECK();
-        HIP_TRY(hipMemcpyAsync(flag, bad, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return SURFD_OK;
+        return bad.read(flag, st);
     };
     rc = run();
     (void)hipFree(q);
-    (void)hipFree(bad);
     if (rc == SURFD_OK && flag[0]) {
         set_error("surfd_isect_create: %d of %d vertices are NaN or beyond the lattice (|x * 2^%d| > 2^19)", flag[0], V, lattice_log2);
         rc = SURFD_ERR_ARG;
     } else if (rc == SURFD_OK && flag[1]) {
-        set_error("surfd_isect_create: a triangle names a vertex outside [0, %d)", V);
-        rc = SURFD_ERR_ARG;
+        rc = mesh_bad_index("surfd_isect_create", V);
     }
     if (rc != SURFD_OK) { surfd_isect_destroy(m); return rc; }
     *out = m;
@@ -447,13 +434,7 @@ int surfd_isect_between(surfd_isect *a, surfd_isect *b, int flags, int32_t *hits
 
 int surfd_isect_skipped(surfd_isect *m, int64_t *skipped, int64_t *total, surfd_stream s) {
     if (!m || !skipped || !total) SURFD_FAIL(SURFD_ERR_ARG, "surfd_isect_skipped: null argument");
-    hipStream_t st = as_stream(s);
-    unsigned long long v = 0;
-    HIP_TRY(hipMemcpyAsync(&v, m->counters + 1, sizeof(v), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *skipped = (int64_t)v;
-    *total = (int64_t)m->last_total;
-    return SURFD_OK;
+    return read_counter(m->counters + 1, m->last_total, skipped, total, as_stream(s));
 }
 
 }  // extern "C"

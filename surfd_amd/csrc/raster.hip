@@ -44,8 +44,9 @@
 // atomic), and the resolve kernel runs after the raster kernels in stream order.  The list of large triangles is filled through
 // an atomicAdd counter; its order varies from run to run, the image does not (the minimum is order-free).  The per-view dropped
 // counts are integer atomicAdd.  Every loop is bounded by the clipped box or the list length; no kernel waits on another
-// workgroup; no LDS.
+// workgroup; no LDS.  The projected vertices and the list live in the handle's arena (meshscene.h).
 #include "common.h"
+#include "meshscene.h"
 #include <cmath>
 #include <climits>
 #include <cstring>
@@ -326,18 +327,8 @@ struct surfd_raster {
     float *cams_pinned = nullptr;         // the same in pinned host memory: the source of the asynchronous copy
     hipEvent_t cams_done = nullptr;       // recorded after that copy; waited for before the pinned buffer is written again
     bool cams_pending = false;
-    void *ws = nullptr;                   // projected vertices [views, V] and the list of large triangles [views * F] (grows)
-    size_t ws_bytes = 0;
+    DeviceArena ws;                       // projected vertices [views, V] and the list of large triangles [views * F]
 };
-
-static int rs_ws(surfd_raster *r, size_t bytes, hipStream_t st) {
-    if (bytes <= r->ws_bytes) return SURFD_OK;
-    HIP_TRY(hipStreamSynchronize(st));                // the previous call's kernels may still read the old arena
-    (void)hipFree(r->ws); r->ws = nullptr; r->ws_bytes = 0;
-    HIP_TRY(hipMalloc(&r->ws, bytes));
-    r->ws_bytes = bytes;
-    return SURFD_OK;
-}
 
 extern "C" {
 
@@ -373,7 +364,8 @@ int surfd_raster_create(int H, int W, int max_views, surfd_raster **out) {
 
 void surfd_raster_destroy(surfd_raster *r) {
     if (!r) return;
-    (void)hipFree(r->keys); (void)hipFree(r->counters); (void)hipFree(r->cams); (void)hipFree(r->ws);
+    (void)hipFree(r->keys); (void)hipFree(r->counters); (void)hipFree(r->cams);
+    r->ws.release();
     (void)hipHostFree(r->cams_pinned);
     if (r->cams_done) (void)hipEventDestroy(r->cams_done);
     delete r;
@@ -407,9 +399,9 @@ int surfd_raster_render(surfd_raster *r, const float *vertices, int V, const int
     const int W = r->W, H = r->H;
     const size_t vert_bytes = ((size_t)n_views * V * sizeof(RsVert) + 255) / 256 * 256;
     const size_t list_bytes = (size_t)n_views * F * sizeof(unsigned long long);
-    if (int rc = rs_ws(r, vert_bytes + list_bytes, st)) return rc;
-    RsVert *verts = reinterpret_cast<RsVert *>(r->ws);
-    unsigned long long *list = reinterpret_cast<unsigned long long *>(static_cast<char *>(r->ws) + vert_bytes);
+    if (int rc = r->ws.reserve(vert_bytes + list_bytes, st)) return rc;
+    RsVert *verts = reinterpret_cast<RsVert *>(r->ws.ptr);
+    unsigned long long *list = reinterpret_cast<unsigned long long *>(static_cast<char *>(r->ws.ptr) + vert_bytes);
     // the caller's cameras are copied into the handle's pinned buffer here, so the caller may free them when the call returns
     if (r->cams_pending) HIP_TRY(hipEventSynchronize(r->cams_done));       // the previous call's copy has read the buffer
     memcpy(r->cams_pinned, cameras, (size_t)n_views * RS_CAM * sizeof(float));

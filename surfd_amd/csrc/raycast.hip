@@ -98,13 +98,14 @@
 //   nothing and meets every triangle.  The needle caveat carries over as it stands; nothing else is excused.
 //
 // Bounds: ray n >= R reads ray R - 1 and writes nothing.  Staging reads records below F only; LDS is indexed with u < cnt <= 256.
-// The sphere arrays are indexed with c < nchunk and c * 8 + tt < ntile.  Partial results [S, R] live in the handle's workspace:
-// one stream at a time per handle.  Hazards: the LDS chunk is bracketed by a barrier on both sides.  bvr_trace_kernel reads
+// The sphere arrays are indexed with c < nchunk and c * 8 + tt < ntile.  Partial results [S, R] live in the handle's arena
+// (meshscene.h).  Hazards: the LDS chunk is bracketed by a barrier on both sides.  bvr_trace_kernel reads
 // node off[level] + node with node < size[level] and leaf_tri[child] with child < nleaf: only children whose box exists are ever
 // entered (meshbvh_layout.h); a triangle index outside [0, F) is not read.  Its LDS holds the level offsets, written once
 // before one barrier.
 #include "common.h"
 #include "meshbvh.h"
+#include "meshscene.h"
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -542,28 +543,9 @@ struct surfd_rayscene {
     float4 *chunk_sph = nullptr;      // [nchunk]
     unsigned long long *skipped = nullptr;   // (wave, tile) visits the last call with SURFD_RAY_COUNT_SKIPPED skipped
     long long last_total = 0;         // and how many visits that call had in all
-    mutable void *ws = nullptr;       // partial results (grows)
-    mutable size_t ws_bytes = 0;
+    DeviceArena ws;                   // partial results
     MeshBvh bvh;                      // the hierarchy of surfd_rayscene_build_bvh (meshbvh.hip)
 };
-
-static int rc_ws(const surfd_rayscene *m, size_t bytes, hipStream_t st) {
-    if (bytes <= m->ws_bytes) return SURFD_OK;
-    HIP_TRY(hipStreamSynchronize(st));                // the previous call's kernels may still read the old arena
-    (void)hipFree(m->ws); m->ws = nullptr; m->ws_bytes = 0;
-    HIP_TRY(hipMalloc(&m->ws, bytes));
-    m->ws_bytes = bytes;
-    return SURFD_OK;
-}
-
-// splits of the chunk range per block of rays: about 2048 workgroups over the chip (8 per CU), whole chunks per split
-static void rc_splits(int R, int nchunk, int *S, int *span) {
-    const long rb = ceil_div<long>(R, RC_CHUNK);
-    long s = std::max<long>(1, ceil_div<long>(2048, rb));
-    s = std::min<long>({s, (long)RC_MAX_SPLITS, (long)nchunk});
-    *span = (int)ceil_div<long>(nchunk, s);
-    *S = ceil_div(nchunk, *span);
-}
 
 static int rc_check(const char *who, const surfd_rayscene *m, const float *rays, int R, float tmin, float tmax, int flags) {
     if (R < 0) SURFD_FAIL(SURFD_ERR_ARG, "%s: R = %d is negative", who, R);
@@ -583,15 +565,15 @@ static int rc_check(const char *who, const surfd_rayscene *m, const float *rays,
 template <bool COUNT>
 static int rc_trace(surfd_rayscene *m, const float *rays, int R, float tmin, float tmax, int flags, unsigned long long **pk, int **pc,
                     int *S_out, hipStream_t st) {
-    int S, span, rc;
+    int rc;
     const bool brute = flags & SURFD_RAY_BRUTE_FORCE;
     const bool tree = (flags & SURFD_RAY_BVH) && !brute;      // the brute-force flag wins
-    rc_splits(R, m->nchunk, &S, &span);
-    if (tree) S = 1;
+    const Split sp = split_units(R, RC_CHUNK, m->nchunk, RC_MAX_SPLITS);      // splits of the chunk range per block of rays
+    const int S = tree ? 1 : sp.S, span = sp.span;
     const size_t np = (size_t)S * R;
-    if ((rc = rc_ws(m, np * sizeof(unsigned long long), st))) return rc;
-    *pk = (unsigned long long *)m->ws;
-    *pc = (int *)m->ws;
+    if ((rc = m->ws.reserve(np * sizeof(unsigned long long), st))) return rc;
+    *pk = (unsigned long long *)m->ws.ptr;
+    *pc = (int *)m->ws.ptr;
     *S_out = S;
     if (m->bvh.built && (flags & SURFD_RAY_COUNT_VISITS) && (rc = bvh_visits_reset(&m->bvh, st))) return rc;
     if (tree) {
@@ -625,27 +607,23 @@ static int rc_trace(surfd_rayscene *m, const float *rays, int R, float tmin, flo
 extern "C" {
 
 int surfd_rayscene_create(const float *vertices, int V, const int32_t *triangles, int F, surfd_stream s, surfd_rayscene **out) {
-    if (!out) SURFD_FAIL(SURFD_ERR_ARG, "surfd_rayscene_create: null out");
-    *out = nullptr;
-    if (!vertices || !triangles) SURFD_FAIL(SURFD_ERR_ARG, "surfd_rayscene_create: null vertices or triangles");
-    if (V < 1 || F < 1) SURFD_FAIL(SURFD_ERR_ARG, "surfd_rayscene_create: V = %d, F = %d must be positive", V, F);
-    if (F > (1 << 28)) SURFD_FAIL(SURFD_ERR_UNSUPPORTED, "surfd_rayscene_create: F = %d is beyond the supported size", F);
+    int rc = mesh_create_args("surfd_rayscene_create", vertices, V, triangles, F, out, 1 << 28);
+    if (rc != SURFD_OK) return rc;
     hipStream_t st = as_stream(s);
     surfd_rayscene *m = new surfd_rayscene();
     m->F = F;
     m->ntile = ceil_div(F, RC_TILE);
     m->nchunk = ceil_div(F, RC_CHUNK);
-    int *bad = nullptr;
-    int rc = SURFD_OK, flag = 0;
+    CreateFlags bad(1);
+    int flag = 0;
     auto run = [&]() -> int {
         HIP_TRY(hipMalloc(&m->rec, (size_t)F * RC_REC4 * sizeof(float4)));
         HIP_TRY(hipMalloc(&m->tile_sph, (size_t)m->ntile * sizeof(float4)));
         HIP_TRY(hipMalloc(&m->chunk_sph, (size_t)m->nchunk * sizeof(float4)));
         HIP_TRY(hipMalloc(&m->skipped, sizeof(unsigned long long)));
-        HIP_TRY(hipMalloc(&bad, sizeof(int)));
-        HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int), st));
+        if (int e = bad.init(st)) return e;
         HIP_TRY(hipMemsetAsync(m->skipped, 0, sizeof(unsigned long long), st));
-        hipLaunchKernelGGL(rc_gather_kernel, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, st, vertices, V, triangles, F, m->rec, bad);
+        hipLaunchKernelGGL(rc_gather_kernel, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, st, vertices, V, triangles, F, m->rec, bad.dev);
         LAUNCH_CHECK();
         hipLaunchKernelGGL(rc_bounds_kernel, dim3((unsigned)ceil_div(m->ntile, 64)), dim3(64), 0, st, (const float4 *)m->rec, F, RC_TILE,
                            m->ntile, m->tile_sph);
@@ -653,16 +631,10 @@ int surfd_rayscene_create(const float *vertices, int V, const int32_t *triangles
         hipLaunchKernelGGL(rc_bounds_kernel, dim3((unsigned)ceil_div(m->nchunk, 64)), dim3(64), 0, st, (const float4 *)m->rec, F, RC_CHUNK,
                            m->nchunk, m->chunk_sph);
         LAUNCH_CHECK();
-        HIP_TRY(hipMemcpyAsync(&flag, bad, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return SURFD_OK;
+        return bad.read(&flag, st);
     };
     rc = run();
-    (void)hipFree(bad);
-    if (rc == SURFD_OK && flag) {
-        set_error("surfd_rayscene_create: a triangle names a vertex outside [0, %d)", V);
-        rc = SURFD_ERR_ARG;
-    }
+    if (rc == SURFD_OK && flag) rc = mesh_bad_index("surfd_rayscene_create", V);
     if (rc != SURFD_OK) { surfd_rayscene_destroy(m); return rc; }
     *out = m;
     return SURFD_OK;
@@ -670,7 +642,8 @@ int surfd_rayscene_create(const float *vertices, int V, const int32_t *triangles
 
 void surfd_rayscene_destroy(surfd_rayscene *m) {
     if (!m) return;
-    (void)hipFree(m->rec); (void)hipFree(m->tile_sph); (void)hipFree(m->chunk_sph); (void)hipFree(m->skipped); (void)hipFree(m->ws);
+    (void)hipFree(m->rec); (void)hipFree(m->tile_sph); (void)hipFree(m->chunk_sph); (void)hipFree(m->skipped);
+    m->ws.release();
     bvh_free(&m->bvh);
     delete m;
 }
@@ -708,13 +681,7 @@ int surfd_rayscene_count(surfd_rayscene *m, const float *rays, int R, float tmin
 
 int surfd_rayscene_skipped(surfd_rayscene *m, int64_t *skipped, int64_t *total, surfd_stream s) {
     if (!m || !skipped || !total) SURFD_FAIL(SURFD_ERR_ARG, "surfd_rayscene_skipped: null argument");
-    hipStream_t st = as_stream(s);
-    unsigned long long v = 0;
-    HIP_TRY(hipMemcpyAsync(&v, m->skipped, sizeof(v), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *skipped = (int64_t)v;
-    *total = (int64_t)m->last_total;
-    return SURFD_OK;
+    return read_counter(m->skipped, m->last_total, skipped, total, as_stream(s));
 }
 
 int surfd_rayscene_build_bvh(surfd_rayscene *m, surfd_stream s) {

@@ -44,8 +44,9 @@
 // 256 c + cnt <= F, so the index is below 9 F <= 3 (2^31 - 1) and is formed in 64 bits; LDS is indexed with 9 u + 8 < 9 cnt <= 2304;
 // the workspace with g Q + n < ngroup Q (64 bits), Q the slab's query count, and it holds ngroup * slab doubles with Q <= slab.
 // wn_finish_kernel reads the same range and points[3 n .. 3 n + 2], writes w[n], n < Q.  Hazards: the LDS chunk is bracketed by a
-// barrier on both sides.  No workgroup waits for another.  Partial results live in the handle: one stream at a time per handle.
+// barrier on both sides.  No workgroup waits for another.  Partial results live in the handle's arena (meshscene.h).
 #include "common.h"
+#include "meshscene.h"
 #include <cmath>
 #include <algorithm>
 
@@ -148,18 +149,8 @@ using namespace surfd;
 struct surfd_winding {
     int F = 0, nchunk = 0, ngroup = 0;
     float *rec = nullptr;             // [F] triangles of 9 fp32
-    void *ws = nullptr;               // partial sums [ngroup, slab] (grows)
-    size_t ws_bytes = 0;
+    DeviceArena ws;                   // partial sums [ngroup, slab]
 };
-
-static int wn_ws(surfd_winding *m, size_t bytes, hipStream_t st) {
-    if (bytes <= m->ws_bytes) return SURFD_OK;
-    HIP_TRY(hipStreamSynchronize(st));                // the previous call's kernels may still read the old arena
-    (void)hipFree(m->ws); m->ws = nullptr; m->ws_bytes = 0;
-    HIP_TRY(hipMalloc(&m->ws, bytes));
-    m->ws_bytes = bytes;
-    return SURFD_OK;
-}
 
 // queries per slab: as many as keep ngroup * slab doubles within WN_WS_MAX, in whole workgroups where that leaves one (whole waves
 // otherwise: ngroup <= 174 763 for 3 F < 2^31, and 174 763 * 64 * 8 bytes is 85 MiB)
@@ -168,50 +159,34 @@ static long wn_slab(int ngroup) {
     return fit >= WN_CHUNK ? fit / WN_CHUNK * WN_CHUNK : std::max<long>(64, fit / 64 * 64);
 }
 
-// splits of the group range per block of queries: about 2048 workgroups over the chip (8 per CU), whole groups per split
-static void wn_splits(int Q, int ngroup, bool one, int *S, int *gspan) {
-    const long qb = ceil_div<long>(Q, WN_CHUNK);
-    long s = one ? 1 : std::max<long>(1, ceil_div<long>(2048, qb));
-    s = std::min<long>({s, (long)ngroup, 65535L});
-    *gspan = (int)ceil_div<long>(ngroup, s);
-    *S = ceil_div(ngroup, *gspan);
-}
-
 extern "C" {
 
 int surfd_winding_create(const float *vertices, int V, const int32_t *triangles, int F, surfd_stream s, surfd_winding **out) {
-    if (!out) SURFD_FAIL(SURFD_ERR_ARG, "surfd_winding_create: null out");
-    *out = nullptr;
-    if (!vertices || !triangles) SURFD_FAIL(SURFD_ERR_ARG, "surfd_winding_create: null vertices or triangles");
-    if (V < 1 || F < 1) SURFD_FAIL(SURFD_ERR_ARG, "surfd_winding_create: V = %d, F = %d must be positive", V, F);
+    int rc = mesh_create_args("surfd_winding_create", vertices, V, triangles, F, out, INT_MAX);  // the size test below is this file's
+    if (rc != SURFD_OK) return rc;
     if ((long long)F * 3 >= (1ll << 31)) SURFD_FAIL(SURFD_ERR_ARG, "surfd_winding_create: F = %d: 3 F must stay below 2^31", F);
     hipStream_t st = as_stream(s);
     surfd_winding *m = new surfd_winding();
     m->F = F;
     m->nchunk = ceil_div(F, WN_CHUNK);
     m->ngroup = ceil_div(m->nchunk, WN_GROUP_CHUNKS);
-    int *bad = nullptr;                                       // [0] vertices that are not finite, [1] bad indices
-    int rc = SURFD_OK, flag[2] = {0, 0};
+    CreateFlags bad(2);                                       // [0] vertices that are not finite, [1] bad indices
+    int flag[2] = {0, 0};
     auto run = [&]() -> int {
         HIP_TRY(hipMalloc(&m->rec, (size_t)F * WN_REC * sizeof(float)));
-        HIP_TRY(hipMalloc(&bad, 2 * sizeof(int)));
-        HIP_TRY(hipMemsetAsync(bad, 0, 2 * sizeof(int), st));
-        hipLaunchKernelGGL(wn_check_kernel, dim3((unsigned)ceil_div(V, 256)), dim3(256), 0, st, vertices, V, bad);
+        if (int e = bad.init(st)) return e;
+        hipLaunchKernelGGL(wn_check_kernel, dim3((unsigned)ceil_div(V, 256)), dim3(256), 0, st, vertices, V, bad.dev);
         LAUNCH_CHECK();
-        hipLaunchKernelGGL(wn_gather_kernel, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, st, vertices, V, triangles, F, m->rec, bad + 1);
+        hipLaunchKernelGGL(wn_gather_kernel, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, st, vertices, V, triangles, F, m->rec, bad.dev + 1);
         LAUNCH_CHECK();
-        HIP_TRY(hipMemcpyAsync(flag, bad, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return SURFD_OK;
+        return bad.read(flag, st);
     };
     rc = run();
-    (void)hipFree(bad);
     if (rc == SURFD_OK && flag[0]) {
         set_error("surfd_winding_create: %d of %d vertices hold a NaN or an Inf", flag[0], V);
         rc = SURFD_ERR_ARG;
     } else if (rc == SURFD_OK && flag[1]) {
-        set_error("surfd_winding_create: a triangle names a vertex outside [0, %d)", V);
-        rc = SURFD_ERR_ARG;
+        rc = mesh_bad_index("surfd_winding_create", V);
     }
     if (rc != SURFD_OK) { surfd_winding_destroy(m); return rc; }
     *out = m;
@@ -220,7 +195,8 @@ int surfd_winding_create(const float *vertices, int V, const int32_t *triangles,
 
 void surfd_winding_destroy(surfd_winding *m) {
     if (!m) return;
-    (void)hipFree(m->rec); (void)hipFree(m->ws);
+    (void)hipFree(m->rec);
+    m->ws.release();
     delete m;
 }
 
@@ -235,15 +211,15 @@ int surfd_winding_eval(surfd_winding *m, const float *points, int64_t Q, int fla
     hipStream_t st = as_stream(s);
     const long slab = wn_slab(m->ngroup);
     int rc;
-    if ((rc = wn_ws(m, (size_t)m->ngroup * (size_t)std::min<long>(slab, (long)Q) * sizeof(double), st))) return rc;
+    if ((rc = m->ws.reserve((size_t)m->ngroup * (size_t)std::min<long>(slab, (long)Q) * sizeof(double), st))) return rc;
     for (long q0 = 0; q0 < Q; q0 += slab) {
         const int Qs = (int)std::min<long>(slab, (long)Q - q0);
-        int S, gspan;
-        wn_splits(Qs, m->ngroup, flags & SURFD_WINDING_ONE_SPLIT, &S, &gspan);
-        hipLaunchKernelGGL(wn_kernel, dim3((unsigned)ceil_div(Qs, WN_CHUNK), (unsigned)S), dim3(256), 0, st, (const float *)m->rec, m->F,
-                           m->nchunk, m->ngroup, gspan, points + q0 * 3, Qs, (double *)m->ws);
+        // splits of the group range per block of queries; 65535: the most a grid has along y
+        const Split sp = split_units(Qs, WN_CHUNK, m->ngroup, 65535, (flags & SURFD_WINDING_ONE_SPLIT) ? 1 : 2048);
+        hipLaunchKernelGGL(wn_kernel, dim3((unsigned)ceil_div(Qs, WN_CHUNK), (unsigned)sp.S), dim3(256), 0, st, (const float *)m->rec, m->F,
+                           m->nchunk, m->ngroup, sp.span, points + q0 * 3, Qs, (double *)m->ws.ptr);
         LAUNCH_CHECK();
-        hipLaunchKernelGGL(wn_finish_kernel, dim3((unsigned)ceil_div(Qs, 256)), dim3(256), 0, st, (const double *)m->ws, m->ngroup,
+        hipLaunchKernelGGL(wn_finish_kernel, dim3((unsigned)ceil_div(Qs, 256)), dim3(256), 0, st, (const double *)m->ws.ptr, m->ngroup,
                            points + q0 * 3, Qs, w + q0);
         LAUNCH_CHECK();
     }

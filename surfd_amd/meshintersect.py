@@ -19,7 +19,6 @@ faces with the same three points (duplicates, in either winding) always do.  Fac
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Dict, Optional
 
@@ -27,7 +26,7 @@ import torch
 from torch import Tensor
 
 from . import _native as N
-from .meshprep import _check_mesh, morton_order
+from .meshprep import _MeshScene
 
 BRUTE_FORCE = 1
 COUNT_SKIPPED = 2
@@ -62,7 +61,7 @@ def _sorted_pairs(keys: Tensor, perm_a: Tensor, perm_b: Tensor, order: bool) -> 
     return torch.stack([k >> 32, k & 0xFFFFFFFF], 1)
 
 
-class IntersectionScene:
+class IntersectionScene(_MeshScene):
     """One mesh, snapped to the lattice 2^-lattice_log2 and kept for repeated calls.
 
     The triangles are handed to the library in Morton order of their centroids, so that its tiles of 32 faces are compact and
@@ -70,31 +69,17 @@ class IntersectionScene:
     two scenes can be compared only when they were made with the same value.  Host syncs: the constructor (the lattice, the
     library's refusal flags) and every query (the pair count)."""
 
+    _abi = "surfd_isect"
+
     def __init__(self, vertices: Tensor, triangles: Tensor, lattice_log2: Optional[int] = None):
-        _check_mesh(vertices, triangles, need_cuda=False)          # shapes and dtypes first, the CPU-tensor refusal last
-        if not (vertices.is_cuda and triangles.is_cuda):
-            raise RuntimeError("mesh intersection runs only on the GPU through libsurfd_hip.so (no CPU fallback): move the mesh with .cuda()")
-        self._handle = None
-        if lattice_log2 is None:
-            lattice_log2 = lattice_for(vertices)
-        if isinstance(lattice_log2, bool) or not isinstance(lattice_log2, int):
-            raise TypeError(f"lattice_log2 must be an int, got {lattice_log2!r}")
-        v = vertices.contiguous()
-        t = triangles.long()
-        self.device = v.device
-        self.lattice_log2 = lattice_log2
-        self.num_triangles = int(t.shape[0])
-        # the order only decides how compact the tiles are: a bad index or a NaN must reach the library, which refuses it
-        centroids = torch.nan_to_num(v, nan=0.0, posinf=0.0, neginf=0.0)[t.clamp(0, v.shape[0] - 1)].mean(1)
-        self._perm = morton_order(centroids)
-        ts = t[self._perm].to(torch.int32).contiguous()
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            N.check(N.lib().surfd_isect_create(N.ptr(v), v.shape[0], N.ptr(ts), ts.shape[0], lattice_log2, N.stream(), C.byref(h)))
-        self._handle = h
-        assert N.lib().surfd_isect_num_triangles(h) == self.num_triangles
-        self.last_skipped_tiles: Optional[int] = None
-        self.last_total_tiles: Optional[int] = None
+        def lattice() -> tuple:
+            self.lattice_log2 = lattice_for(vertices) if lattice_log2 is None else lattice_log2
+            if isinstance(self.lattice_log2, bool) or not isinstance(self.lattice_log2, int):
+                raise TypeError(f"lattice_log2 must be an int, got {self.lattice_log2!r}")
+            return (self.lattice_log2,)
+
+        # no checks of the values here: a bad index or a NaN must reach the library, which refuses it
+        self._open(vertices, triangles, what="mesh intersection", check_values=False, extra=lattice)
 
     def _unsort(self, x: Tensor) -> Tensor:
         out = torch.empty_like(x)
@@ -137,9 +122,7 @@ class IntersectionScene:
                     break
                 cap = n
             if count_skipped:
-                s, t = C.c_int64(), C.c_int64()
-                N.check(L.surfd_isect_skipped(self._handle, C.byref(s), C.byref(t), N.stream()))
-                self.last_skipped_tiles, self.last_total_tiles = int(s.value), int(t.value)
+                self.last_skipped_tiles, self.last_total_tiles = self._read_counters("skipped")
         return n, hits_a, hits_b, (keys[:n] if return_pairs else None)
 
     def self_intersections(self, return_pairs: bool = True, brute_force: bool = False, count_skipped: bool = False,
@@ -180,13 +163,6 @@ class IntersectionScene:
         if return_pairs:
             out["pairs"] = _sorted_pairs(keys, self._perm, other._perm, False)
         return out
-
-    def __del__(self):
-        try:
-            if self._handle is not None:
-                N.lib().surfd_isect_destroy(self._handle)
-        except Exception:                                       # interpreter shutdown
-            pass
 
 
 def self_intersections(vertices: Tensor, triangles: Tensor, lattice_log2: Optional[int] = None, **kw) -> Dict[str, object]:

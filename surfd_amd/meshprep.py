@@ -71,7 +71,8 @@ def read_mesh(mesh_path, dtype: torch.dtype = torch.float) -> Tuple[Tensor, Tens
 
 
 # ---- checks -------------------------------------------------------------------------------------------------------------------
-def _check_mesh(vertices: Tensor, triangles: Tensor, need_cuda: bool = True) -> None:
+def _check_mesh(vertices: Tensor, triangles: Tensor, need_cuda: bool = True, what: str = "the mesh distance") -> None:
+    """shapes and dtypes first, the CPU-tensor refusal last"""
     if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.shape[0] < 1:
         raise ValueError(f"vertices must be [V, 3] with V >= 1, got {tuple(vertices.shape)}")
     if vertices.dtype != torch.float32:
@@ -81,7 +82,7 @@ def _check_mesh(vertices: Tensor, triangles: Tensor, need_cuda: bool = True) -> 
     if triangles.dtype not in (torch.int32, torch.int64):
         raise TypeError(f"triangles must be int32 or int64, got {triangles.dtype}")
     if need_cuda and not (vertices.is_cuda and triangles.is_cuda):
-        raise RuntimeError("the mesh distance runs only on the GPU through libsurfd_hip.so (no CPU fallback): move the mesh with .cuda()")
+        raise RuntimeError(f"{what} runs only on the GPU through libsurfd_hip.so (no CPU fallback): move the mesh with .cuda()")
 
 
 def _check_points(name: str, p: Tensor, need_cuda: bool = True) -> None:
@@ -123,21 +124,91 @@ def _check_accel(accel: str) -> None:
         raise ValueError(f"accel must be 'tiles' or 'bvh', got {accel!r}")
 
 
-def _read_bvh(handle, info_fn, read_fn, device) -> dict:
-    """the hierarchy of a handle as the library holds it: {"level_sizes": [levels] ints (level 0 = the nodes above the leaves),
-    "boxes": [nodes, 6, 4] float32 (lo.xyz, hi.xyz of a node's 4 children), "leaves": [leaves, 4] int32 (the HANDLE's triangle
-    indices, -1 past the end)}, on the device"""
-    levels, leaves, nodes = C.c_int(), C.c_int(), C.c_int()
-    sizes = (C.c_int32 * 16)()
-    N.check(info_fn(handle, C.byref(levels), C.byref(leaves), C.byref(nodes), sizes, 16))
-    boxes = torch.empty(nodes.value, 6, 4, device=device, dtype=torch.float32)
-    tri = torch.empty(leaves.value, 4, device=device, dtype=torch.int32)
-    with torch.cuda.device(device):
-        N.check(read_fn(handle, N.ptr(boxes), N.ptr(tri), N.stream()))
-    return {"level_sizes": [int(sizes[k]) for k in range(levels.value)], "boxes": boxes, "leaves": tri}
+class _MeshScene:
+    """What the objects that keep one mesh in the library share (MeshDistance, RaycastingScene, WindingScene,
+    IntersectionScene): the handle and its device, ``num_triangles``, the counters the last call left, and ``_open``, the
+    constructors' common work.  ``_abi`` is the prefix of the library's functions for the handle."""
+
+    _abi = ""
+    _handle = None
+    _perm: Optional[Tensor] = None                  # handle index -> the caller's triangle index; None: the caller's order
+    last_skipped_tiles: Optional[int] = None
+    last_total_tiles: Optional[int] = None
+    last_box_tests: Optional[int] = None
+    last_pair_tests: Optional[int] = None
+
+    def _fn(self, name: str):
+        return getattr(N.lib(), f"{self._abi}_{name}")
+
+    def _open(self, vertices: Tensor, triangles: Tensor, what: str = "the mesh distance", check_values: bool = True,
+              morton: bool = True, prepare=None, extra=None) -> Tuple[Tensor, Tensor]:
+        """Checks the mesh, hands it to the library's create and returns (vertices, int64 triangles) as the caller ordered
+        them.  ``extra()`` gives create's further arguments and runs right after the shape checks.  ``check_values``: the
+        finiteness and index-range checks (three host syncs); without them a NaN or a bad index reaches the library, which
+        refuses it.  ``prepare(v, t)`` may replace the triangles.  ``morton``: the library gets the triangles in Morton order
+        of their centroids and ``_perm`` maps its indices back."""
+        _check_mesh(vertices, triangles, what=what)
+        args = extra() if extra is not None else ()
+        if check_values and not bool(torch.isfinite(vertices).all()):
+            raise ValueError("vertices contain NaN or Inf")
+        v, t = vertices.contiguous(), triangles.long()
+        if check_values and (int(t.min()) < 0 or int(t.max()) >= v.shape[0]):
+            raise ValueError(f"triangles name vertices outside [0, {v.shape[0]})")
+        if prepare is not None:
+            t = prepare(v, t)
+        self.device = v.device
+        self.num_triangles = int(t.shape[0])
+        ts = t
+        if morton:                                   # the order only decides how compact the tiles are
+            corners = v[t] if check_values else torch.nan_to_num(v, nan=0.0, posinf=0.0, neginf=0.0)[t.clamp(0, v.shape[0] - 1)]
+            self._perm = morton_order(corners.mean(1))
+            ts = t[self._perm]
+        ts = ts.to(torch.int32).contiguous()
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            N.check(self._fn("create")(N.ptr(v), v.shape[0], N.ptr(ts), ts.shape[0], *args, N.stream(), C.byref(h)))
+        self._handle = h
+        assert self._fn("num_triangles")(h) == self.num_triangles
+        return v, t
+
+    def _read_counters(self, name: str) -> Tuple[int, int]:
+        """the two int64 that the library's ``name`` reads back ("visits", "skipped"): one host sync"""
+        a, b = C.c_int64(), C.c_int64()
+        N.check(self._fn(name)(self._handle, C.byref(a), C.byref(b), N.stream()))
+        return int(a.value), int(b.value)
+
+    def __del__(self):
+        try:
+            if self._handle is not None:
+                self._fn("destroy")(self._handle)
+        except Exception:                                       # interpreter shutdown
+            pass
 
 
-class MeshDistance:
+class _BvhScene(_MeshScene):
+    """a scene that can carry the box hierarchy of csrc/meshbvh.hip (``accel="bvh"``)"""
+
+    def _set_accel(self, accel: str) -> None:
+        self.accel = accel
+        if accel == "bvh":
+            with torch.cuda.device(self.device):
+                N.check(self._fn("build_bvh")(self._handle, N.stream()))
+
+    def read_bvh(self) -> dict:
+        """the hierarchy (``accel="bvh"`` only) as the library holds it, for tests: {"level_sizes": [levels] ints (level 0 = the
+        nodes above the leaves), "boxes": [nodes, 6, 4] float32 (lo.xyz, hi.xyz of a node's 4 children), "leaves": [leaves, 4]
+        int32 (the HANDLE's triangle indices, -1 past the end), "perm": handle index -> the caller's}, on the device"""
+        levels, leaves, nodes = C.c_int(), C.c_int(), C.c_int()
+        sizes = (C.c_int32 * 16)()
+        N.check(self._fn("bvh_info")(self._handle, C.byref(levels), C.byref(leaves), C.byref(nodes), sizes, 16))
+        boxes = torch.empty(nodes.value, 6, 4, device=self.device, dtype=torch.float32)
+        tri = torch.empty(leaves.value, 4, device=self.device, dtype=torch.int32)
+        with torch.cuda.device(self.device):
+            N.check(self._fn("bvh_read")(self._handle, N.ptr(boxes), N.ptr(tri), N.stream()))
+        return {"level_sizes": [int(sizes[k]) for k in range(levels.value)], "boxes": boxes, "leaves": tri, "perm": self._perm}
+
+
+class MeshDistance(_BvhScene):
     """The closest-point structure of one mesh, kept for repeated calls (the role of open3d's RaycastingScene).
 
     The triangles are handed to the library in Morton order of their centroids and every call's queries in Morton order of
@@ -150,39 +221,12 @@ class MeshDistance:
     ``accel="bvh"`` also builds the box hierarchy of csrc/meshbvh.hip (one more host sync); ``closest`` then walks it instead of
     the tiles unless ``brute_force=True``.  The results are the same bits either way."""
 
+    _abi = "surfd_mesh"
+
     def __init__(self, vertices: Tensor, triangles: Tensor, accel: str = "tiles"):
         _check_accel(accel)
-        _check_mesh(vertices, triangles)
-        if not bool(torch.isfinite(vertices).all()):
-            raise ValueError("vertices contain NaN or Inf")
-        self._handle = None
-        v = vertices.contiguous()
-        t = triangles.long()
-        if int(t.min()) < 0 or int(t.max()) >= v.shape[0]:
-            raise ValueError(f"triangles name vertices outside [0, {v.shape[0]})")
-        self.device = v.device
-        self._perm = morton_order(v[t].mean(1))
-        ts = t[self._perm].to(torch.int32).contiguous()
-        self.num_triangles = int(t.shape[0])
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            N.check(N.lib().surfd_mesh_create(N.ptr(v), v.shape[0], N.ptr(ts), ts.shape[0], N.stream(), C.byref(h)))
-        self._handle = h
-        assert N.lib().surfd_mesh_num_triangles(h) == self.num_triangles
-        self.accel = accel
-        if accel == "bvh":
-            with torch.cuda.device(self.device):
-                N.check(N.lib().surfd_mesh_build_bvh(h, N.stream()))
-        self.last_skipped_tiles: Optional[int] = None
-        self.last_total_tiles: Optional[int] = None
-        self.last_box_tests: Optional[int] = None
-        self.last_pair_tests: Optional[int] = None
-
-    def read_bvh(self) -> dict:
-        """the hierarchy (``accel="bvh"`` only), for tests: see ``_read_bvh``; ``perm`` maps a handle index to the caller's"""
-        out = _read_bvh(self._handle, N.lib().surfd_mesh_bvh_info, N.lib().surfd_mesh_bvh_read, self.device)
-        out["perm"] = self._perm
-        return out
+        self._open(vertices, triangles)
+        self._set_accel(accel)
 
     def closest(self, queries: Tensor, brute_force: bool = False, count_skipped: bool = False,
                 count_visits: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
@@ -213,9 +257,7 @@ class MeshDistance:
                 N.check(N.lib().surfd_mesh_closest_bvh(self._handle, N.ptr(qs), Q, MESH_COUNT_VISITS if count_visits else 0, N.ptr(dist),
                                                        N.ptr(pts), N.ptr(tri), N.ptr(skipped), N.stream()))
                 if count_visits:
-                    b, p = C.c_int64(), C.c_int64()
-                    N.check(N.lib().surfd_mesh_visits(self._handle, C.byref(b), C.byref(p), N.stream()))
-                    self.last_box_tests, self.last_pair_tests = int(b.value), int(p.value)
+                    self.last_box_tests, self.last_pair_tests = self._read_counters("visits")
             else:
                 N.check(N.lib().surfd_mesh_closest(self._handle, N.ptr(qs), Q, MESH_BRUTE_FORCE if brute_force else 0, N.ptr(dist),
                                                    N.ptr(pts), N.ptr(tri), N.ptr(skipped), N.stream()))
@@ -225,13 +267,6 @@ class MeshDistance:
         inv = torch.empty_like(order)
         inv[order] = torch.arange(Q, device=self.device)
         return dist[inv], pts[inv], self._perm[tri.long()][inv]
-
-    def __del__(self):
-        try:
-            if self._handle is not None:
-                N.lib().surfd_mesh_destroy(self._handle)
-        except Exception:                                       # interpreter shutdown
-            pass
 
 
 def closest_points(vertices: Tensor, triangles: Tensor, queries: Tensor, brute_force: bool = False,

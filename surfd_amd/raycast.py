@@ -18,7 +18,6 @@ and surfd_amd/winding.py (WindingScene: |winding number| >= 1/2) is the answer t
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Dict, Optional, Tuple, Union
 
@@ -26,7 +25,7 @@ import torch
 from torch import Tensor
 
 from . import _native as N
-from .meshprep import MeshDistance, _check_accel, _check_mesh, _check_points, _read_bvh, morton_order
+from .meshprep import MeshDistance, _BvhScene, _check_accel, _check_points, morton_order
 
 BRUTE_FORCE = 1
 COUNT_SKIPPED = 2
@@ -59,7 +58,7 @@ def _check_nsamples(nsamples: int) -> None:
         raise ValueError(f"nsamples must be 1 (+z) or 3 (+z, +x, +y), got {nsamples}")
 
 
-class RaycastingScene:
+class RaycastingScene(_BvhScene):
     """One mesh, kept for repeated calls.
 
     The triangles are handed to the library in Morton order of their centroids and every call's rays in Morton order of their
@@ -72,42 +71,13 @@ class RaycastingScene:
     ``accel="bvh"`` also builds the box hierarchy of csrc/meshbvh.hip (one more host sync); every method then walks it instead
     of the tiles unless ``brute_force=True``, and ``mesh_distance()`` is built with it too.  The results are the same bits."""
 
+    _abi = "surfd_rayscene"
+
     def __init__(self, vertices: Tensor, triangles: Tensor, accel: str = "tiles"):
         _check_accel(accel)
-        _check_mesh(vertices, triangles, need_cuda=False)          # shapes and dtypes first, the CPU-tensor refusal last
-        _check_mesh(vertices, triangles)
-        if not bool(torch.isfinite(vertices).all()):
-            raise ValueError("vertices contain NaN or Inf")
-        self._handle = None
         self._distance: Optional[MeshDistance] = None
-        v = vertices.contiguous()
-        t = triangles.long()
-        if int(t.min()) < 0 or int(t.max()) >= v.shape[0]:
-            raise ValueError(f"triangles name vertices outside [0, {v.shape[0]})")
-        self.device = v.device
-        self.vertices, self.triangles = v, t
-        self._perm = morton_order(v[t].mean(1))
-        ts = t[self._perm].to(torch.int32).contiguous()
-        self.num_triangles = int(t.shape[0])
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            N.check(N.lib().surfd_rayscene_create(N.ptr(v), v.shape[0], N.ptr(ts), ts.shape[0], N.stream(), C.byref(h)))
-        self._handle = h
-        assert N.lib().surfd_rayscene_num_triangles(h) == self.num_triangles
-        self.accel = accel
-        if accel == "bvh":
-            with torch.cuda.device(self.device):
-                N.check(N.lib().surfd_rayscene_build_bvh(h, N.stream()))
-        self.last_skipped_tiles: Optional[int] = None
-        self.last_total_tiles: Optional[int] = None
-        self.last_box_tests: Optional[int] = None
-        self.last_pair_tests: Optional[int] = None
-
-    def read_bvh(self) -> dict:
-        """the hierarchy (``accel="bvh"`` only), for tests: see ``meshprep._read_bvh``; ``perm`` maps a handle index to the caller's"""
-        out = _read_bvh(self._handle, N.lib().surfd_rayscene_bvh_info, N.lib().surfd_rayscene_bvh_read, self.device)
-        out["perm"] = self._perm
-        return out
+        self.vertices, self.triangles = self._open(vertices, triangles)
+        self._set_accel(accel)
 
     # ---- the two kernels ------------------------------------------------------------------------------------------------------
     def _sorted(self, rays: Tensor):
@@ -128,15 +98,11 @@ class RaycastingScene:
         return (BRUTE_FORCE if brute_force else 0) | (COUNT_SKIPPED if count_skipped else 0) | (BVH if use_bvh else 0) | \
             (COUNT_VISITS if count_visits else 0)
 
-    def _read_visits(self) -> None:
-        b, p = C.c_int64(), C.c_int64()
-        N.check(N.lib().surfd_rayscene_visits(self._handle, C.byref(b), C.byref(p), N.stream()))
-        self.last_box_tests, self.last_pair_tests = int(b.value), int(p.value)
-
-    def _read_skipped(self) -> None:
-        s, t = C.c_int64(), C.c_int64()
-        N.check(N.lib().surfd_rayscene_skipped(self._handle, C.byref(s), C.byref(t), N.stream()))
-        self.last_skipped_tiles, self.last_total_tiles = int(s.value), int(t.value)
+    def _read_counts(self, count_skipped: bool, count_visits: bool) -> None:
+        if count_skipped:
+            self.last_skipped_tiles, self.last_total_tiles = self._read_counters("skipped")
+        if count_visits:
+            self.last_box_tests, self.last_pair_tests = self._read_counters("visits")
 
     def cast_rays(self, rays: Tensor, tmin: float = 0.0, tmax: float = math.inf, brute_force: bool = False,
                   count_skipped: bool = False, count_visits: bool = False) -> Dict[str, Tensor]:
@@ -159,10 +125,7 @@ class RaycastingScene:
         with torch.cuda.device(self.device):
             N.check(N.lib().surfd_rayscene_cast(self._handle, N.ptr(rs), R, tmin, tmax, flags,
                                                 N.ptr(t), N.ptr(tri), N.ptr(uv), N.ptr(nrm), N.stream()))
-            if count_skipped:
-                self._read_skipped()
-            if count_visits:
-                self._read_visits()
+            self._read_counts(count_skipped, count_visits)
         tri = tri.long()
         ids = torch.where(tri >= 0, self._perm[tri.clamp_min(0)], tri)
         return {"t_hit": t[inv], "primitive_ids": ids[inv], "primitive_uvs": uv[inv], "primitive_normals": nrm[inv]}
@@ -180,10 +143,7 @@ class RaycastingScene:
         with torch.cuda.device(self.device):
             N.check(N.lib().surfd_rayscene_count(self._handle, N.ptr(rs), R, tmin, tmax, flags,
                                                  N.ptr(cnt), N.stream()))
-            if count_skipped:
-                self._read_skipped()
-            if count_visits:
-                self._read_visits()
+            self._read_counts(count_skipped, count_visits)
         return cnt[inv]
 
     # ---- what follows from them -----------------------------------------------------------------------------------------------
@@ -234,10 +194,3 @@ class RaycastingScene:
             raise ValueError(f"points_a {tuple(points_a.shape)} and points_b {tuple(points_b.shape)} must have the same shape")
         rays = torch.cat([points_a, points_b - points_a], dim=1)
         return ~self.test_occlusions(rays, tmin=eps, tmax=1.0, brute_force=brute_force)
-
-    def __del__(self):
-        try:
-            if self._handle is not None:
-                N.lib().surfd_rayscene_destroy(self._handle)
-        except Exception:                                       # interpreter shutdown
-            pass

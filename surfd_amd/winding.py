@@ -20,14 +20,13 @@ The fp64 bits of a query's w do not depend on the other queries of the call, on 
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional, Tuple, Union
 
 import torch
 from torch import Tensor
 
 from . import _native as N
-from .meshprep import MeshDistance, _check_mesh, _check_points
+from .meshprep import MeshDistance, _MeshScene, _check_mesh, _check_points
 
 ONE_SPLIT = 1                   # SURFD_WINDING_ONE_SPLIT
 
@@ -39,34 +38,23 @@ def _check_threshold(threshold: float) -> float:
     return threshold
 
 
-class WindingScene:
+class WindingScene(_MeshScene):
     """One mesh, kept for repeated calls.  The triangles reach the library in the caller's order.  Host syncs: the constructor
     checks the vertices and the index range and the library's create reads its flags; the calls themselves do not sync.  One
     stream at a time per object: the library keeps its partial sums in a workspace of the handle."""
 
+    _abi = "surfd_winding"
+
     def __init__(self, vertices: Tensor, triangles: Tensor, orient: Union[bool, str] = False):
-        _check_mesh(vertices, triangles, need_cuda=False)          # shapes and dtypes first, the CPU-tensor refusal last
-        _check_mesh(vertices, triangles)
-        if not bool(torch.isfinite(vertices).all()):
-            raise ValueError("vertices contain NaN or Inf")
-        self._handle = None
         self._distance: Optional[MeshDistance] = None
-        v = vertices.contiguous()
-        t = triangles.long()
-        if int(t.min()) < 0 or int(t.max()) >= v.shape[0]:
-            raise ValueError(f"triangles name vertices outside [0, {v.shape[0]})")
-        if orient is not False:
+
+        def oriented(v: Tensor, t: Tensor) -> Tensor:
+            if orient is False:
+                return t
             from .meshtopo import oriented_for_winding
-            t = oriented_for_winding(v, t, orient)
-        self.device = v.device
-        self.vertices, self.triangles = v, t
-        ts = t.to(torch.int32).contiguous()
-        self.num_triangles = int(t.shape[0])
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            N.check(N.lib().surfd_winding_create(N.ptr(v), v.shape[0], N.ptr(ts), ts.shape[0], N.stream(), C.byref(h)))
-        self._handle = h
-        assert N.lib().surfd_winding_num_triangles(h) == self.num_triangles
+            return oriented_for_winding(v, t, orient)
+
+        self.vertices, self.triangles = self._open(vertices, triangles, morton=False, prepare=oriented)
 
     def _points(self, points: Tensor) -> Tensor:
         _check_points("points", points, need_cuda=False)
@@ -108,13 +96,6 @@ class WindingScene:
         occ = self.compute_occupancy(points, threshold)
         dist = self.mesh_distance().closest(points)[0]
         return torch.where(occ > 0, -dist, dist)
-
-    def __del__(self):
-        try:
-            if self._handle is not None:
-                N.lib().surfd_winding_destroy(self._handle)
-        except Exception:                                       # interpreter shutdown
-            pass
 
 
 def winding_number(vertices: Tensor, triangles: Tensor, points: Tensor, orient: Union[bool, str] = False) -> Tensor:

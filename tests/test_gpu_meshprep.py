@@ -214,6 +214,25 @@ def test_repeated_calls_are_bit_identical(M, cases):
         assert torch.equal(x, y)
 
 
+@pytest.mark.parametrize("name", ["cube", "sheet"])
+def test_workspace_regrowth_changes_nothing(M, name):
+    """One handle: 64 queries, then 5000, then the first 64 again.  The handle's arena (csrc/meshscene.h) holds S * Q partial
+    results, so the second call has to free and allocate it and the third runs in an arena larger than it needs.  Every call
+    equals the same call on a fresh handle.  cube: 12 triangles, one chunk, S = 1; sheet: 450 triangles, two chunks, S = 2."""
+    import raycast_ref as rr
+    v, t = rr.cube() if name == "cube" else rr.wavy_sheet(16)
+    assert len(t) == (12 if name == "cube" else 450)
+    vd, td = cu(v), cu(t)
+    q = cu(np.random.default_rng(11).uniform(-1, 1, (5000, 3)).astype(np.float32))
+    small = q[:64].contiguous()
+    md = M.MeshDistance(vd, td)
+    for queries in (small, q, small):
+        got = md.closest(queries)
+        fresh = M.MeshDistance(vd, td).closest(queries)
+        for x, y in zip(got, fresh):
+            assert torch.equal(x, y)
+
+
 def test_bad_indices_are_a_return_code(M):
     import ctypes as C
     from surfd_amd import _native as N

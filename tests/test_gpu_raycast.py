@@ -199,6 +199,28 @@ def test_ten_repeats_give_identical_bits():
         same_bits(scene.cast(rays, tmin, tmax), first, f"repeat {i + 1}")
 
 
+@pytest.mark.parametrize("name", ["cube", "sheet"])
+def test_workspace_regrowth_changes_nothing(name):
+    """One handle: 64 rays, then 5000, then the first 64 again, a cast and a count each time.  The handle's arena
+    (csrc/meshscene.h) holds S * R partial results, 64-bit keys for the cast and 32-bit counts for the count in the same
+    bytes, so the second round has to free and allocate it and the third runs in an arena larger than it needs.  Every call
+    equals the same call on a fresh handle.  cube: 12 triangles, one chunk, S = 1; sheet: 450 triangles, two chunks, S = 2."""
+    from surfd_amd.raycast import RaycastingScene
+    mesh = rr.cube() if name == "cube" else rr.wavy_sheet(16)
+    assert len(mesh[1]) == (12 if name == "cube" else 450)
+    vd, fd = cu(mesh[0]), cu(mesh[1])
+    rays = cu(rr.mixed_rays(mesh, 5000, 21))
+    small = rays[:64].contiguous()
+    scene = RaycastingScene(vd, fd)
+    for r in (small, rays, small):
+        hit, cnt = scene.cast_rays(r), scene.count_intersections(r)
+        fresh = RaycastingScene(vd, fd).cast_rays(r)
+        assert sorted(hit) == sorted(fresh)
+        for key in hit:
+            assert torch.equal(hit[key], fresh[key]), key
+        assert torch.equal(cnt, RaycastingScene(vd, fd).count_intersections(r))
+
+
 # ---- 6: inside / outside against mathematics ------------------------------------------------------------------------------------
 def _occupancy(mesh, pts, nsamples):
     from surfd_amd.raycast import RaycastingScene

@@ -150,6 +150,27 @@ def test_bits_do_not_depend_on_batch_position_repeat_or_splits():
     assert torch.equal(one_by_one, among[[0, 7, 299]])
 
 
+@pytest.mark.parametrize("name", ["cube", "sheet", "F-16896"])
+def test_workspace_regrowth_changes_nothing(name):
+    """One handle: 64 queries, then 5000, then the first 64 again, each also with ``one_split``.  The handle's arena
+    (csrc/meshscene.h) holds ngroup * Q partial sums, so the second round has to free and allocate it and the third runs in an
+    arena larger than it needs.  Every call equals the same call on a fresh handle.  cube: 12 triangles; sheet: 450; both are
+    one group, so S = 1 either way.  F-16896: five groups, S = 5, and 1 with ``one_split``."""
+    from surfd_amd.winding import WindingScene
+    v, f = {"cube": rr.cube, "sheet": lambda: rr.wavy_sheet(16), "F-16896": big_torus}[name]()
+    assert len(f) == {"cube": 12, "sheet": 450, "F-16896": 16896}[name]
+    vd, fd = cu(v), cu(f)
+    q = cu(uniform_queries(5000, 31))
+    small = q[:64].contiguous()
+    scene = WindingScene(vd, fd)
+    for points in (small, q, small):
+        w = scene.winding_number(points)
+        single = scene.winding_number(points, one_split=True)
+        assert torch.equal(w, WindingScene(vd, fd).winding_number(points))
+        assert torch.equal(single, w)
+        assert not bool(torch.isnan(w).any())
+
+
 # ---- 3. face permutation and corner rotation -------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["mesh-torus", "mesh-spliced_sheet", "F-16896"])
 def test_face_order_and_corner_rotation_stay_within_the_bound(name):
