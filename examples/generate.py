@@ -60,6 +60,7 @@ def parse(argv=None):
     ap.add_argument("--embedding", help="text / image / sketch modes: file with the 512-d CLIP embedding(s)")
     ap.add_argument("--prompt", default=None, help="text mode: only used to name the output files")
     ap.add_argument("--watertight", action="store_true", help="text / image modes: closed 0.01 level set instead of the open UDF mesh")
+    ap.add_argument("--device_mc", action="store_true", help="--watertight: mesh the grid and drop small components on the GPU (same mesh; the grid is not copied to the host)")
     ap.add_argument("--respacing", default="", help="e.g. ddim50 for a quick run (the reference always runs 1000 steps)")
     ap.add_argument("--seed", type=int, default=10)
     ap.add_argument("--synthetic", action="store_true", help="create synthetic checkpoints under --output_dir and use them")
@@ -183,6 +184,9 @@ def run(a):
         field = make_udf_func(decoder, latents[k], sample=k)
 
         def shape_mesh():
+            if a.watertight and a.device_mc:
+                verts, faces = get_watertight_mesh(field, a.resolution, max_batch=2 ** 16, device=True, min_faces=5000)
+                return verts.cpu().numpy(), faces.cpu().numpy()
             if a.watertight:
                 verts, faces = get_watertight_mesh(field, a.resolution, max_batch=2 ** 16)
                 return meshproc.keep_components_with_at_least(verts, faces, 5000)

@@ -42,6 +42,7 @@ def parse(argv=None):
     ap.add_argument("--num_points_pcd", type=int, default=10000)
     ap.add_argument("--resolution", type=int, default=512)
     ap.add_argument("--watertight", action="store_true")
+    ap.add_argument("--device_mc", action="store_true", help="--watertight: mesh the grid on the GPU (same mesh; the grid is not copied to the host)")
     ap.add_argument("--batch", type=int, default=1, help="clouds per encoder call (export_meshes.py:75 uses 1)")
     ap.add_argument("--seed", type=int, default=10)
     ap.add_argument("--output_dir", default="outputs/reconstruct")
@@ -216,6 +217,9 @@ def run(a):
         field = make_udf_func(decoder, latents[k], sample=k)
 
         def shape_mesh():
+            if a.watertight and a.device_mc:
+                v, t = get_watertight_mesh(field, a.resolution, max_batch=2 ** 16, device=True)
+                return v.cpu().numpy(), t.cpu().numpy()
             if a.watertight:
                 return get_watertight_mesh(field, a.resolution, max_batch=2 ** 16)
             v, t = get_mesh_from_udf(field, coords_range=(-1, 1), max_dist=0.1, N=a.resolution, max_batch=2 ** 16, differentiable=False)

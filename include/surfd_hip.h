@@ -356,6 +356,37 @@ int surfd_mc_lut_count(void);
 int surfd_mc_lut(int i, const char **name, const signed char **values, int *ndim, int dims[3]);
 
 /* ------------------------------------------------------------------------------------ */
+/* Level-set marching cubes on the device (csrc/mcdevice.hip): the mesh of surfd_mc_iso   */
+/* with step 1 from a volume that stays on the GPU (the watertight path,                  */
+/* sample/generate_text.py:139-141).  The result equals surfd_mc_iso + surfd_mc_copy on    */
+/* the same volume bit for bit: vertex order, face order, every float, -0 / +0.  No step   */
+/* > 1, no mask, one volume per call.                                                      */
+/* ------------------------------------------------------------------------------------ */
+typedef struct surfd_mcd surfd_mcd;
+/* A handle for volumes [nz, ny, nx], each extent >= 2 (SURFD_ERR_ARG below), nz ny nx < 2^31 (SURFD_ERR_UNSUPPORTED beyond).
+ * Owns 0.31 bytes of device scratch per voxel, plus 24 bytes per active cube of the largest run it has seen.  Reusable for any
+ * number of volumes of that shape; no run sees anything of the run before.  One stream and one host thread at a time. */
+int surfd_mcd_create(int nz, int ny, int nx, surfd_mcd **out);
+void surfd_mcd_destroy(surfd_mcd *h);
+/* volume[nz,ny,nx] fp32 on the device, contiguous; it must stay unchanged until surfd_mcd_emit has run.  Finds the cubes the
+ * level crosses (corner above iff (double)value - level > 0.0), counts and numbers their triangles and vertices in the scan order
+ * of the host mesher.  classic as in surfd_mc_iso.  num_vertices / num_faces (host, nullable): the sizes surfd_mcd_emit fills.
+ * More than 2^31 - 1 vertices or faces: SURFD_ERR_UNSUPPORTED, nothing is emitted.  host-sync (the three totals are read back:
+ * the one read of the path). */
+int surfd_mcd_run(surfd_mcd *h, const float *volume, double level, int classic, surfd_stream s, int64_t *num_vertices, int64_t *num_faces);
+/* The mesh of the last surfd_mcd_run (SURFD_ERR_STATE without one), on the same stream: vertices[V,3] fp32 in (z, y, x) voxel
+ * units, faces[F,3] int32 (winding of gradient_direction="descent"), normals[V,3] (unit; nullable), values[V] (nullable), device
+ * memory, as surfd_mc_copy hands them out.  An empty run (V = F = 0) writes nothing and accepts null pointers.  Does not sync. */
+int surfd_mcd_emit(surfd_mcd *h, float *vertices, int32_t *faces, float *normals, float *values, surfd_stream s);
+/* no reference counterpart; the number of cubes the level crosses in the last run, for measurements:
+ * host memory.  SURFD_ERR_STATE without a run. */
+int surfd_mcd_active(const surfd_mcd *h, int64_t *active);
+/* no reference counterpart; the first pass of surfd_mcd_run alone, for measurements against the time to stream the volume once:
+ * reads the volume, leaves the per-chunk masks and counts in the handle.  It overwrites those of the last run: surfd_mcd_emit is
+ * SURFD_ERR_STATE until the next surfd_mcd_run.  Does not sync. */
+int surfd_mcd_classify(surfd_mcd *h, const float *volume, double level, int classic, surfd_stream s);
+
+/* ------------------------------------------------------------------------------------ */
 /* CrossAttention over [b, n, c] tokens (modules/attention.py:152-193) — SURVEY §8 a19.  */
 /* No Surf-D configuration instantiates the module (use_spatial_transformer is False);    */
 /* a standalone op with its own handle, fp32 on the matrix pipe.                           */

@@ -184,6 +184,12 @@ _SIGS = {
     "surfd_voxel_iou": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "surfd_mc_lut_count": (C.c_int, []),
     "surfd_mc_lut": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.POINTER(C.c_byte)), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "surfd_mcd_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "surfd_mcd_destroy": (None, [_P]),
+    "surfd_mcd_run": (C.c_int, [_P, _P, C.c_double, C.c_int, _P, c_i64p, c_i64p]),
+    "surfd_mcd_emit": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "surfd_mcd_active": (C.c_int, [_P, c_i64p]),
+    "surfd_mcd_classify": (C.c_int, [_P, _P, C.c_double, C.c_int, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 

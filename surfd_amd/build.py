@@ -36,6 +36,7 @@ SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshtopo.hip")          # edges, co
 # cloudnn.hip: without SLP vectorisation the pair test stays 8 plain fp32 instructions + half a v_min3; with it the compiler packs
 # half of them into v_pk_*_f32 (issued at half rate, so nothing is gained) and pads the loop with s_nop
 # cloudnormals.hip: the same pair test in its scan; measured 0.5-2.7 % slower with the vectoriser on
+SOURCES.insert(SOURCES.index("mcubes.cpp"), "mcdevice.hip")          # level-set marching cubes on the device (surfd_amd/mcubes.py: marching_cubes_device)
 FILE_FLAGS = {"cloudnn.hip": ["-fno-slp-vectorize"], "cloudnormals.hip": ["-fno-slp-vectorize"]}
 
 

@@ -5,6 +5,9 @@
 The C++ mesher restates the reference's Cython extension (meshudf/_marching_cubes_lewiner_cy.pyx) and reproduces its
 output bit for bit (tests/test_mcubes_cpu.py compares with the reference's own compiled extension and with committed
 fixtures).  Host-side code: no GPU involved; one call meshes one shape on one core.
+
+  marching_cubes_device(volume, isovalue, ...)  the level-set mesher `marching_cubes` on the device (csrc/mcdevice.hip): the same
+                                                mesh bit for bit from a grid that stays on the GPU
 """
 from __future__ import annotations
 
@@ -78,6 +81,91 @@ def marching_cubes(volume, isovalue: float, classic: bool = True) -> Tuple[np.nd
         raise ValueError("volume must be a 3D array of at least 2x2x2")
     v, f, _, _ = _run(volume, None, 1, isovalue, classic)
     return v.astype(np.float64), f.astype(np.int64)          # wound outward for the solid {volume < isovalue}
+
+
+class DeviceMesher:
+    """Level-set marching cubes on the device for volumes of one shape (csrc/mcdevice.hip): what `_run(volume, None, 1, level,
+    classic)` gives on the host copy of the volume, bit for bit, as device tensors.  Reusable; one stream at a time."""
+
+    def __init__(self, shape):
+        nz, ny, nx = (int(s) for s in shape)
+        if min(nz, ny, nx) < 2:
+            raise ValueError("volume must be a 3D array of at least 2x2x2")
+        h = C.c_void_p()
+        N.check(N.lib().surfd_mcd_create(nz, ny, nx, C.byref(h)))
+        self.shape, self._h = (nz, ny, nx), h
+        self.active_cubes = 0
+
+    def run(self, volume, level: float, classic: bool = True, normals: bool = False, values: bool = False):
+        """(vertices fp32 [V,3] in (z,y,x), faces int32 [F,3], normals fp32 [V,3] or None, values fp32 [V] or None) on the
+        volume's device.  One host read (V, F) sizes the tensors; everything else is ordered on the current stream."""
+        import torch
+        if not volume.is_cuda:
+            raise ValueError("marching_cubes_device runs only on the GPU through libsurfd_hip.so (no CPU fallback): move the volume with .cuda()")
+        if tuple(volume.shape) != self.shape or volume.dtype != torch.float32:
+            raise ValueError(f"volume must be float32 {self.shape}, got {volume.dtype} {tuple(volume.shape)}")
+        L = N.lib()
+        nv, nf, na = C.c_int64(), C.c_int64(), C.c_int64()
+        with torch.cuda.device(volume.device):
+            N.check(L.surfd_mcd_run(self._h, N.ptr(volume), float(level), int(bool(classic)), N.stream(), C.byref(nv), C.byref(nf)))
+            N.check(L.surfd_mcd_active(self._h, C.byref(na)))
+            self.active_cubes = int(na.value)
+            v = torch.empty((nv.value, 3), device=volume.device, dtype=torch.float32)
+            f = torch.empty((nf.value, 3), device=volume.device, dtype=torch.int32)
+            n = torch.empty((nv.value, 3), device=volume.device, dtype=torch.float32) if normals else None
+            s = torch.empty((nv.value,), device=volume.device, dtype=torch.float32) if values else None
+            N.check(L.surfd_mcd_emit(self._h, N.ptr(v), N.ptr(f), N.ptr(n), N.ptr(s), N.stream()))
+        return v, f, n, s
+
+    def classify_only(self, volume, level: float, classic: bool = True) -> None:
+        """the first pass alone (measurements: tools/time_mcdevice.py)"""
+        N.check(N.lib().surfd_mcd_classify(self._h, N.ptr(volume), float(level), int(bool(classic)), N.stream()))
+
+    def close(self) -> None:
+        if self._h is not None:
+            N.lib().surfd_mcd_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def marching_cubes_device(volume, isovalue: float, classic: bool = True, return_normals: bool = False, return_values: bool = False):
+    """`marching_cubes` without the host: ``volume`` is a contiguous CUDA tensor [nz, ny, nx] (half / double are converted to
+    fp32, as np.float32 does on the host path) -> (vertices fp32 [V,3] in voxel-index units along the volume's axes, faces int32
+    [F,3], then normals fp32 [V,3] and values fp32 [V] where asked for), device tensors that equal `_run(volume.cpu().numpy(),
+    None, 1, isovalue, classic)` bit for bit.  An empty surface gives empty tensors.  Step 1 only, no mask."""
+    import torch
+    if not isinstance(volume, torch.Tensor) or not volume.is_cuda:
+        raise ValueError("marching_cubes_device runs only on the GPU through libsurfd_hip.so (no CPU fallback): move the volume with .cuda()")
+    if volume.dim() != 3 or min(volume.shape) < 2:
+        raise ValueError("volume must be a 3D array of at least 2x2x2")
+    if not volume.is_contiguous():
+        raise ValueError("volume must be contiguous")
+    if not volume.is_floating_point():
+        raise ValueError(f"volume must be a floating-point tensor, got {volume.dtype}")
+    # the handle of the last shape is kept (its scratch is 0.31 bytes per voxel); a handle serves one stream at a time, so a
+    # call from another stream first waits for the stream of the call before
+    global _last_mesher
+    key = (volume.device.index, tuple(volume.shape))
+    stream = torch.cuda.current_stream(volume.device)
+    if _last_mesher is not None and _last_mesher[0] != key:
+        _last_mesher[1].close()                  # hipFree waits for the device
+        _last_mesher = None
+    if _last_mesher is None:
+        with torch.cuda.device(volume.device):
+            _last_mesher = [key, DeviceMesher(volume.shape), stream]
+    if _last_mesher[2] != stream:
+        _last_mesher[2].synchronize()
+        _last_mesher[2] = stream
+    v, f, n, s = _last_mesher[1].run(volume.float(), isovalue, classic, return_normals, return_values)
+    return (v, f) + ((n,) if return_normals else ()) + ((s,) if return_values else ())
+
+
+_last_mesher = None
 
 
 def lut_tables() -> dict:

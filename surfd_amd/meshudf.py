@@ -397,20 +397,38 @@ def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[
 
 
 def get_watertight_mesh(udf_func: Callable[[Tensor], Tensor], N: int, max_batch: int = 2 ** 16, level: float = 0.01,
-                        normalize: bool = False, classic: bool = True):
+                        normalize: bool = False, classic: bool = True, device: bool = False, min_faces: Optional[int] = None):
     """The --watertight path of the reference's text / image drivers (sample/generate_text.py:132-158 with the
     CPU-resident GridFiller of utils/utils.py:151-339): coarse-to-fine UDF grid WITHOUT gradients, then the closed
     `level` iso-surface of the UDF (a thin solid around the sheet).  Returns (vertices [V,3] float64, faces [F,3]) on
     the host.  Vertices are in voxel-index units like the file the reference ends up writing (it normalises a
     component it then does not export); ``normalize=True`` maps them to [-1, 1]^3.  PyMCubes is not available here:
     the surface comes from the native level-set mesher (classic triangle table by default) — same level set,
-    triangulation parity with PyMCubes unpinned.  Small-component removal is the caller's next step (5000 faces)."""
-    from .mcubes import marching_cubes
+    triangulation parity with PyMCubes unpinned.  Small-component removal is the caller's next step (5000 faces), or
+    ``min_faces=K`` here: components (by shared vertices) with fewer faces go.
+    ``device=True``: the grid is meshed where it lies (mcubes.marching_cubes_device: the same mesh bit for bit, no copy of the
+    grid to the host) and the result stays there — (vertices float64, faces int64) as device tensors, ``min_faces`` through
+    meshtopo.keep_components_with_at_least — ready for the device stages that follow (winding, voxelize, render, raycast)."""
+    from .mcubes import marching_cubes, marching_cubes_device
     udf, _ = GridFiller(N).fill_grid(udf_func, max_batch, with_grads=False)
     udf[udf < 0] = 0
+    if device:
+        if not udf.is_cuda:
+            raise ValueError("get_watertight_mesh(device=True) runs only on the GPU through libsurfd_hip.so (no CPU fallback)")
+        verts, faces = marching_cubes_device(udf.detach().contiguous(), level, classic=classic)
+        verts, faces = verts.double(), faces.long()
+        if normalize:
+            verts = verts * (2.0 / N) - 1.0
+        if min_faces is not None:
+            from . import meshtopo
+            verts, faces = meshtopo.keep_components_with_at_least(verts, faces, int(min_faces))
+        return verts, faces
     verts, faces = marching_cubes(udf.detach().cpu().numpy(), level, classic=classic)
     if normalize:
         verts = verts * (2.0 / N) - 1.0
+    if min_faces is not None:
+        from . import meshproc
+        verts, faces = meshproc.keep_components_with_at_least(verts, faces, int(min_faces))
     return verts, faces
 
 
