@@ -61,6 +61,9 @@ def parse(argv=None):
     ap.add_argument("--prompt", default=None, help="text mode: only used to name the output files")
     ap.add_argument("--watertight", action="store_true", help="text / image modes: closed 0.01 level set instead of the open UDF mesh")
     ap.add_argument("--device_mc", action="store_true", help="--watertight: mesh the grid and drop small components on the GPU (same mesh; the grid is not copied to the host)")
+    ap.add_argument("--device_post", action="store_true",
+                    help="open meshes: border smoothing, Laplacian smoothing and small-component removal on the GPU (surfd_amd.meshsmooth / meshtopo); "
+                         "the mesh is copied to the host once, for the OBJ file")
     ap.add_argument("--respacing", default="", help="e.g. ddim50 for a quick run (the reference always runs 1000 steps)")
     ap.add_argument("--seed", type=int, default=10)
     ap.add_argument("--synthetic", action="store_true", help="create synthetic checkpoints under --output_dir and use them")
@@ -190,7 +193,15 @@ def run(a):
             if a.watertight:
                 verts, faces = get_watertight_mesh(field, a.resolution, max_batch=2 ** 16)
                 return meshproc.keep_components_with_at_least(verts, faces, 5000)
-            v, t = get_mesh_from_udf(field, coords_range=(-1, 1), max_dist=0.1, N=a.resolution, max_batch=2 ** 16, differentiable=False)
+            device_post = bool(getattr(a, "device_post", False))
+            v, t = get_mesh_from_udf(field, coords_range=(-1, 1), max_dist=0.1, N=a.resolution, max_batch=2 ** 16, differentiable=False,
+                                     device_post=device_post)
+            if device_post:                                   # the mesh goes to the host once, for write_obj
+                if postprocess_open_mesh(a.mode):
+                    from surfd_amd import meshsmooth, meshtopo
+                    v = meshsmooth.laplacian_smooth(v, t, steps=3)
+                    v, t = meshtopo.keep_components_with_at_least(v, t, 2500)
+                return v.double().cpu().numpy(), t.cpu().numpy()
             verts, faces = v.cpu().numpy(), t.cpu().numpy()
             if postprocess_open_mesh(a.mode):
                 verts = meshproc.laplacian_smooth(verts, faces, steps=3)

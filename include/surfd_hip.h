@@ -688,6 +688,54 @@ int surfd_meshtopo_orient(surfd_meshtopo *m, const float *vertices, unsigned cha
 int surfd_meshtopo_weld(const float *vertices, int V, int32_t *vertex_map, unsigned char *survivor, int64_t *count, surfd_stream s);
 
 /* ------------------------------------------------------------------------------------ */
+/* Mesh smoothing and vertex normals: the vertex-moving steps between the mesh stages.    */
+/* Stands for MeshLab's apply_coord_laplacian_smoothing (sample/generate_uncond.py), the   */
+/* border smoothing loop of meshudf.py and trimesh's weighted_vertex_normals, which the    */
+/* reference runs on the host.  fp64 on the caller's positions, + - * / sqrt (and one      */
+/* acos in the angle-weighted normals), no atomics: every output is a function of the      */
+/* input alone, and the order of summation per vertex is fixed (csrc/meshsmooth.hip        */
+/* states it; tests/meshsmooth_ref.py restates it sequentially in numpy).                  */
+/* ------------------------------------------------------------------------------------ */
+typedef struct surfd_meshsmooth surfd_meshsmooth;
+#define SURFD_MESHSMOOTH_F32 0      /* dtype of the positions given: float */
+#define SURFD_MESHSMOOTH_F64 1      /* double */
+#define SURFD_MESHSMOOTH_ALL 0      /* umbrella set: every half-edge at the vertex */
+#define SURFD_MESHSMOOTH_BORDER 1   /* umbrella set: the border neighbours only; other vertices stay */
+#define SURFD_MESHSMOOTH_ANGLE 0    /* normals: unit face normals weighted by the corner angle */
+#define SURFD_MESHSMOOTH_AREA 1     /* normals: the unnormalised cross products */
+/* no reference counterpart; the neighbourhoods of one connectivity, built once and kept:
+ * triangles[F,3] int32 on the device (copied), V the number of vertices they may name.  Half-edge h = 3 f + c runs from t[f, c]
+ * to t[f, (c + 1) % 3]; it is a border half-edge iff its unordered vertex pair occurs exactly once among all 3 F half-edges
+ * (faces with repeated indices take part: meshproc.border_edge_rows, not the classification of surfd_meshtopo).  Stable radix
+ * sorts give, per vertex, the half-edges that leave it and that arrive at it (ascending in h), its border neighbours and its
+ * corners (ascending in (c, f)).  F >= 0, V >= 0, 3 F < 2^31; an index outside [0, V) is SURFD_ERR_ARG, found on the device
+ * before anything is indexed by it, never a fault.  host-sync (the flag and the two border counts are read back). */
+int surfd_meshsmooth_create(const int32_t *triangles, int F, int V, surfd_stream s, surfd_meshsmooth **out);
+void surfd_meshsmooth_destroy(surfd_meshsmooth *m);
+/* no reference counterpart; what create found, each nullable, host memory: F, V, the border half-edges, the vertices on them. */
+int surfd_meshsmooth_counts(const surfd_meshsmooth *m, int64_t *faces, int64_t *vertices, int64_t *border_halfedges, int64_t *border_vertices);
+/* pymeshlab's apply_coord_laplacian_smoothing(stepsmoothnum, boundary, cotangentweight) as meshproc.laplacian_smooth restates it:
+ * vertices[V,3] on the device, fp32 or fp64 by dtype, -> out[V,3] fp64 (out may be the fp64 input itself; otherwise they must
+ * not overlap).  `steps` Jacobi sweeps, one launch each: an inner vertex moves to (p + sum w_h p_h) / (1 + sum w_h) over the
+ * half-edges that leave it, then those that arrive, w_h = the cotangent of the angle opposite h (1 without `cotangent`; 0 where
+ * the triangle has no area); with `boundary` a vertex on a border half-edge is averaged with itself and its neighbours along
+ * the border only.  A vertex whose weights sum to <= 0 stays.  steps = 0 and F = 0 copy the input.  Does not sync; one stream at a time per handle (the position buffers are the handle's). */
+int surfd_meshsmooth_laplacian(surfd_meshsmooth *m, const void *vertices, int dtype, int steps, int cotangent, int boundary, double *out,
+                               surfd_stream s);
+/* the border smoothing loop of meshudf.py (set = BORDER; meshproc.smooth_borders) and Taubin's lambda | mu smoothing (set = ALL):
+ * `sweeps` Jacobi sweeps p <- p + k (mean of the neighbours - p), k = k0 in sweeps 0, 2, ... and k1 in sweeps 1, 3, ...; the
+ * neighbours are the other ends of every half-edge at the vertex (ALL: leaving, then arriving, a neighbour once per half-edge) or
+ * of its border half-edges (BORDER: those above the vertex ascending, then those below); a vertex without neighbours stays.
+ * Buffers, dtype and stream as for surfd_meshsmooth_laplacian.  Does not sync. */
+int surfd_meshsmooth_umbrella(surfd_meshsmooth *m, const void *vertices, int dtype, double k0, double k1, int sweeps, int set, double *out,
+                              surfd_stream s);
+/* trimesh's geometry.weighted_vertex_normals (ANGLE; meshproc.vertex_normals_by_angle) and mean_vertex_normals by area (AREA):
+ * unit[V,3] and raw[V,3] fp64 on the device, each nullable: raw = the sum over the vertex's corners, in (c, f) order, of the unit
+ * face normal times the corner angle (ANGLE) or of the face's cross product (AREA); unit = raw / |raw|, 0 where that is 0.
+ * Neither may overlap the positions.  Does not sync. */
+int surfd_meshsmooth_vertex_normals(surfd_meshsmooth *m, const void *vertices, int dtype, int weight, double *unit, double *raw, surfd_stream s);
+
+/* ------------------------------------------------------------------------------------ */
 /* Point-cloud metrics: nearest neighbours between clouds and the matrix of directed      */
 /* Chamfer means between two sets of clouds.  No reference counterpart (the reference     */
 /* ships no evaluation code): stands for pytorch3d's knn_points(p1, p2, K=1) /            */

@@ -167,6 +167,12 @@ _SIGS = {
     "surfd_meshtopo_border_loops": (C.c_int, [_P, _P, _P, c_i64p, _P]),
     "surfd_meshtopo_orient": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "surfd_meshtopo_weld": (C.c_int, [_P, C.c_int, _P, _P, c_i64p, _P]),
+    "surfd_meshsmooth_create": (C.c_int, [_P, C.c_int, C.c_int, _P, C.POINTER(_P)]),
+    "surfd_meshsmooth_destroy": (None, [_P]),
+    "surfd_meshsmooth_counts": (C.c_int, [_P, c_i64p, c_i64p, c_i64p, c_i64p]),
+    "surfd_meshsmooth_laplacian": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "surfd_meshsmooth_umbrella": (C.c_int, [_P, _P, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _P, _P]),
+    "surfd_meshsmooth_vertex_normals": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "surfd_cloud_nn": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "surfd_cloud_nn_matrix": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_float, _P, _P, _P]),
     "surfd_cloud_fps_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),

@@ -37,6 +37,7 @@ SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshtopo.hip")          # edges, co
 # half of them into v_pk_*_f32 (issued at half rate, so nothing is gained) and pads the loop with s_nop
 # cloudnormals.hip: the same pair test in its scan; measured 0.5-2.7 % slower with the vectoriser on
 SOURCES.insert(SOURCES.index("mcubes.cpp"), "mcdevice.hip")          # level-set marching cubes on the device (surfd_amd/mcubes.py: marching_cubes_device)
+SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshsmooth.hip")        # Laplacian / Taubin / border smoothing, vertex normals (surfd_amd/meshsmooth.py)
 FILE_FLAGS = {"cloudnn.hip": ["-fno-slp-vectorize"], "cloudnormals.hip": ["-fno-slp-vectorize"]}
 
 

@@ -354,7 +354,7 @@ def get_udf_and_grads(udf_func, coords_range: Tuple[float, float], max_dist: flo
 
 def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[float, float], max_dist: float,
                       N: int = 128, smooth_borders: bool = True, differentiable: bool = True,
-                      max_batch: int = 2 ** 12, use_fast_grid_filler: bool = True) -> Tuple[Tensor, Tensor]:
+                      max_batch: int = 2 ** 12, use_fast_grid_filler: bool = True, device_post: bool = False) -> Tuple[Tensor, Tensor]:
     """Triangulated mesh of the zero set of a UDF — same signature, defaults and return value as the reference
     (meshudf/meshudf.py:307-514): (vertices [V,3] float32, faces [F,3] int64) on the device.
 
@@ -363,7 +363,9 @@ def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[
     end/mid point farther than 1/N from the surface are dropped (3 x 3F extra decoder queries, on the GPU) -> mesh
     cleaning and border smoothing (surfd_amd.meshproc: numpy restatements of the trimesh calls) -> optionally the
     reference's re-attachment of gradients to the vertex positions (``differentiable=True``; the sample scripts pass
-    False)."""
+    False).  ``device_post=True`` (no reference counterpart): the cleaned mesh is uploaded before the border smoothing instead of
+    after it, the 20 sweeps run there (surfd_amd.meshsmooth: the same positions bit for bit) and ``differentiable`` takes its
+    vertex normals from the device too; the cleaning stays on the host."""
     from . import meshproc as mp
     from .mcubes import udf_mc_lewiner
     if not use_fast_grid_filler:
@@ -387,6 +389,18 @@ def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[
     keep = np.ones(len(faces), dtype=bool)
     keep[np.unique(np.tile(edge_face, 3)[far])] = False
     vertices, faces = mp.clean_until_stable(vertices, faces[keep])
+    if device_post:
+        from . import meshsmooth
+        final_faces = torch.tensor(faces).long().to(dev)
+        verts64 = torch.tensor(vertices).to(dev)
+        smoother = meshsmooth.MeshSmoother(final_faces, len(vertices)) if smooth_borders or differentiable else None
+        if smooth_borders:
+            verts64 = smoother.smooth_borders(verts64, lam=0.3, iterations=20)
+        final_verts = verts64.float()
+        if not differentiable:
+            return final_verts, final_faces
+        normals = smoother.vertex_normals(verts64).float()
+        return _reattach_gradients(udf_func, verts64.cpu().numpy(), faces, final_verts, final_faces, 1 / N, max_batch, mp, normals=normals)
     if smooth_borders:
         vertices = mp.smooth_borders(vertices, faces, lam=0.3, iterations=20)
     final_verts = torch.tensor(vertices).float().to(dev)
@@ -432,12 +446,13 @@ def get_watertight_mesh(udf_func: Callable[[Tensor], Tensor], N: int, max_batch:
     return verts, faces
 
 
-def _reattach_gradients(udf_func, vertices, faces, verts, final_faces, th_dist, max_batch, mp):
+def _reattach_gradients(udf_func, vertices, faces, verts, final_faces, th_dist, max_batch, mp, normals=None):
     """meshudf.py:439-512: the vertex positions are re-expressed through udf samples taken at +-th_dist along the
     normals (and, on borders, along the outward in-surface direction) so that d(vertices)/d(udf parameters) exists;
     numerically the positions do not move (every added term is x - x.detach())."""
     dev = verts.device
-    normals = torch.tensor(mp.vertex_normals_by_angle(vertices, faces)).float().to(dev)
+    if normals is None:                                    # device_post hands in the device's (surfd_amd.meshsmooth)
+        normals = torch.tensor(mp.vertex_normals_by_angle(vertices, faces)).float().to(dev)
     s1 = sample_udf(udf_func, verts + th_dist * normals, max_batch, True).unsqueeze(-1)
     s2 = sample_udf(udf_func, verts - th_dist * normals, max_batch, True).unsqueeze(-1)
     z = th_dist * s1 * normals - th_dist * s2 * normals

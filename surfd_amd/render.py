@@ -167,7 +167,8 @@ class Renderer:
         """-> {"face" [n, H, W] int32 (-1 background), "depth" [n, H, W] float32 (camera z, +inf background), "bary" [n, H, W, 3],
         "normal" [n, H, W, 3] (camera space, towards the viewer), "mask" [n, H, W] uint8, "shaded" [n, H, W] float32,
         "dropped" [n] int32 (triangles left out because a vertex is behind ``near`` or far outside the image)}.
-        ``smooth`` takes vertex normals from meshproc.vertex_normals_by_angle (host, fp64); ``vertex_normals`` [V, 3] float32
+        ``smooth`` takes vertex normals from meshproc.vertex_normals_by_angle (host, fp64), ``smooth="device"`` from
+        meshsmooth.vertex_normals_by_angle (the same sums on the GPU, the mesh stays there); ``vertex_normals`` [V, 3] float32
         supplies them; otherwise the geometric face normal is used.  ``light`` is a camera-space direction (default: the
         headlight (0, 0, -1)).  ``flags``: FORCE_SMALL / FORCE_LARGE send every triangle down one path (the same bits).
         Host syncs: one for the index range check (F > 0)."""
@@ -194,7 +195,12 @@ class Renderer:
             raise ValueError("vertices contain NaN or Inf")
         if F and (V == 0 or int(faces.min()) < 0 or int(faces.max()) >= V):
             raise ValueError(f"faces name vertices outside [0, {V})")
-        if smooth:
+        if isinstance(smooth, str) and smooth != "device":
+            raise ValueError(f"smooth must be False, True or 'device', got {smooth!r}")
+        if smooth == "device":
+            from .meshsmooth import vertex_normals_by_angle as device_normals
+            vertex_normals = device_normals(vertices, faces).float() if V else torch.zeros(0, 3, device=self.device)
+        elif smooth:
             from .meshproc import vertex_normals_by_angle
             vn = vertex_normals_by_angle(vertices.cpu().numpy(), faces.cpu().numpy()) if V else np.zeros((0, 3))
             vertex_normals = torch.from_numpy(np.ascontiguousarray(vn, dtype=np.float32)).to(self.device)
