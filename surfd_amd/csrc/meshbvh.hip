@@ -34,9 +34,9 @@
 // records f = sorted[i] in [0, F) (the sort permutes 0 .. F - 1); a level kernel reads the boxes of children below
 // bvh_child_count() only.
 #include "meshbvh.h"
+#include "devscratch.h"
 #include <cfloat>
 #include <cmath>
-#include <hipcub/hipcub.hpp>
 
 namespace surfd {
 
@@ -217,46 +217,37 @@ int bvh_build(MeshBvh *b, const float4 *rec, int rec4, bool relative, int F, hip
     if (b->built) return SURFD_OK;
     BvhLayout lay;
     if (!bvh_layout(F, &lay)) SURFD_FAIL(SURFD_ERR_UNSUPPORTED, "mesh hierarchy: F = %d needs more than %d levels", F, BVH_MAX_LEVELS);
-    unsigned long long *code_in = nullptr, *code_out = nullptr;
-    int *idx_in = nullptr, *idx_out = nullptr;
-    float *bb = nullptr;
-    void *tmp = nullptr;
-    auto run = [&]() -> int {
-        HIP_TRY(hipMalloc(&b->boxes, (size_t)lay.nodes * BVH_BOX4 * sizeof(float4)));
-        HIP_TRY(hipMalloc(&b->leaf_tri, (size_t)lay.nleaf * sizeof(int4)));
-        HIP_TRY(hipMalloc(&b->level_off, BVH_MAX_LEVELS * sizeof(int)));
-        HIP_TRY(hipMalloc(&b->visits, 2 * sizeof(unsigned long long)));
-        HIP_TRY(hipMalloc(&code_in, (size_t)F * sizeof(unsigned long long)));
-        HIP_TRY(hipMalloc(&code_out, (size_t)F * sizeof(unsigned long long)));
-        HIP_TRY(hipMalloc(&idx_in, (size_t)F * sizeof(int)));
-        HIP_TRY(hipMalloc(&idx_out, (size_t)F * sizeof(int)));
-        HIP_TRY(hipMalloc(&bb, 6 * sizeof(float)));
-        HIP_TRY(hipMemsetAsync(b->visits, 0, 2 * sizeof(unsigned long long), st));
-        HIP_TRY(hipMemcpyAsync(b->level_off, lay.off, BVH_MAX_LEVELS * sizeof(int), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(bvh_bounds_kernel, dim3(1), dim3(1024), 0, st, rec, rec4, (int)relative, F, bb);
+    std::unique_ptr<MeshBvh, void (*)(MeshBvh *)> undo(b, bvh_free);      // a refusal frees what was allocated up to it
+    HIP_TRY(hipMalloc(&b->boxes, (size_t)lay.nodes * BVH_BOX4 * sizeof(float4)));
+    HIP_TRY(hipMalloc(&b->leaf_tri, (size_t)lay.nleaf * sizeof(int4)));
+    HIP_TRY(hipMalloc(&b->level_off, BVH_MAX_LEVELS * sizeof(int)));
+    HIP_TRY(hipMalloc(&b->visits, 2 * sizeof(unsigned long long)));
+    DeviceScratch scratch;
+    CubWorkspace cub{&scratch};
+    unsigned long long *code_in, *code_out;
+    int *idx_in, *idx_out;
+    float *bb;
+    SURFD_TRY(scratch.get(&code_in, F)); SURFD_TRY(scratch.get(&code_out, F)); SURFD_TRY(scratch.get(&idx_in, F)); SURFD_TRY(scratch.get(&idx_out, F));
+    SURFD_TRY(scratch.get(&bb, 6));
+    HIP_TRY(hipMemsetAsync(b->visits, 0, 2 * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemcpyAsync(b->level_off, lay.off, BVH_MAX_LEVELS * sizeof(int), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(bvh_bounds_kernel, dim3(1), dim3(1024), 0, st, rec, rec4, (int)relative, F, bb);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(bvh_codes_kernel, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, st, rec, rec4, (int)relative, F, (const float *)bb,
+                       code_in, idx_in);
+    LAUNCH_CHECK();
+    SURFD_TRY(cub.sort_pairs(code_in, code_out, idx_in, idx_out, F, 64, st));
+    hipLaunchKernelGGL(bvh_leaf_kernel, dim3((unsigned)ceil_div(lay.size[0], 64)), dim3(64), 0, st, rec, rec4, (int)relative, F, lay.nleaf,
+                       lay.size[0], (const int *)idx_out, b->leaf_tri, b->boxes);
+    LAUNCH_CHECK();
+    for (int k = 1; k < lay.levels; ++k) {
+        hipLaunchKernelGGL(bvh_level_kernel, dim3((unsigned)ceil_div(lay.size[k], 64)), dim3(64), 0, st,
+                           (const float4 *)(b->boxes + (size_t)lay.off[k - 1] * BVH_BOX4), lay.size[k - 1],
+                           b->boxes + (size_t)lay.off[k] * BVH_BOX4, lay.size[k]);
         LAUNCH_CHECK();
-        hipLaunchKernelGGL(bvh_codes_kernel, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, st, rec, rec4, (int)relative, F, (const float *)bb,
-                           code_in, idx_in);
-        LAUNCH_CHECK();
-        size_t tmp_bytes = 0;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, code_in, code_out, idx_in, idx_out, F, 0, 64, st));
-        HIP_TRY(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16));
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, code_in, code_out, idx_in, idx_out, F, 0, 64, st));
-        hipLaunchKernelGGL(bvh_leaf_kernel, dim3((unsigned)ceil_div(lay.size[0], 64)), dim3(64), 0, st, rec, rec4, (int)relative, F, lay.nleaf,
-                           lay.size[0], (const int *)idx_out, b->leaf_tri, b->boxes);
-        LAUNCH_CHECK();
-        for (int k = 1; k < lay.levels; ++k) {
-            hipLaunchKernelGGL(bvh_level_kernel, dim3((unsigned)ceil_div(lay.size[k], 64)), dim3(64), 0, st,
-                               (const float4 *)(b->boxes + (size_t)lay.off[k - 1] * BVH_BOX4), lay.size[k - 1],
-                               b->boxes + (size_t)lay.off[k] * BVH_BOX4, lay.size[k]);
-            LAUNCH_CHECK();
-        }
-        HIP_TRY(hipStreamSynchronize(st));
-        return SURFD_OK;
-    };
-    const int rc = run();
-    (void)hipFree(code_in); (void)hipFree(code_out); (void)hipFree(idx_in); (void)hipFree(idx_out); (void)hipFree(bb); (void)hipFree(tmp);
-    if (rc != SURFD_OK) { bvh_free(b); return rc; }
+    }
+    HIP_TRY(hipStreamSynchronize(st));                        // the scratch is freed next
+    undo.release();
     b->lay = lay;
     b->built = true;
     return SURFD_OK;

@@ -58,27 +58,20 @@
 // Bounds: every kernel guards its thread index; lists are walked between offsets that the binary search puts in [0, n]; the
 // neighbour / opposite / corner records hold indices that create validated.
 #include "common.h"
+#include "devscratch.h"
 #include "meshscene.h"
-
-#include <hipcub/hipcub.hpp>
 
 namespace surfd {
 
 typedef unsigned long long ms_u64;
 constexpr int MS_BORDER_BIT = (int)0x80000000u;
 
-static inline unsigned ms_grid(long n) { return (unsigned)std::max<long>(1, ceil_div<long>(n, 256)); }
-// the thread's index in 64 bits: a grid over close to 2^31 items overflows an int before the guard sees it
-__device__ __forceinline__ long ms_tid() { return blockIdx.x * (long)blockDim.x + threadIdx.x; }
-template <class T>
-static inline size_t ms_bytes(long n) { return (size_t)std::max<long>(n, 1) * sizeof(T); }
-
 // ---- create ----------------------------------------------------------------------------------------------------------------
 // the only kernel that sees unvalidated indices: they are compared and packed, never used as addresses
 __global__ void ms_keys_kernel(const int32_t *__restrict__ tri, int F, int V, ms_u64 *__restrict__ ekey, int *__restrict__ eh, unsigned *__restrict__ okey,
                                unsigned *__restrict__ ikey, unsigned *__restrict__ ckey, int *__restrict__ cpay, int *__restrict__ bad) {
-    if (ms_tid() >= F) return;
-    const int f = (int)ms_tid();
+    if (dev_tid() >= F) return;
+    const int f = (int)dev_tid();
     const int t[3] = {tri[3 * (long)f], tri[3 * (long)f + 1], tri[3 * (long)f + 2]};
     if (t[0] < 0 || t[0] >= V || t[1] < 0 || t[1] >= V || t[2] < 0 || t[2] >= V) *bad = 1;      // every writer stores the same 1
 #pragma unroll
@@ -96,21 +89,17 @@ __global__ void ms_keys_kernel(const int32_t *__restrict__ tri, int F, int V, ms
 }
 
 __global__ void ms_border_flags_kernel(const ms_u64 *__restrict__ skey, int n, int *__restrict__ flag) {
-    if (ms_tid() >= n) return;
-    const int i = (int)ms_tid();
+    if (dev_tid() >= n) return;
+    const int i = (int)dev_tid();
     const ms_u64 k = skey[i];
     flag[i] = ((i == 0 || skey[i - 1] != k) && (i == n - 1 || skey[i + 1] != k)) ? 1 : 0;
-}
-
-__global__ void ms_total_kernel(const int *__restrict__ flag, const int *__restrict__ excl, int n, int *__restrict__ out) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) *out = n > 0 ? excl[n - 1] + flag[n - 1] : 0;
 }
 
 // per sorted position: the border byte of its half-edge and, for a border edge of rank r, the two records of BN
 __global__ void ms_border_records_kernel(const ms_u64 *__restrict__ skey, const int *__restrict__ sh, const int *__restrict__ flag, const int *__restrict__ rank,
                                          int n, int B, unsigned char *__restrict__ hborder, unsigned *__restrict__ bsrc, int *__restrict__ bdst) {
-    if (ms_tid() >= n) return;
-    const int i = (int)ms_tid();
+    if (dev_tid() >= n) return;
+    const int i = (int)dev_tid();
     hborder[sh[i]] = (unsigned char)flag[i];
     if (!flag[i]) return;
     const ms_u64 k = skey[i];
@@ -134,16 +123,16 @@ __global__ void ms_offsets_kernel(const unsigned *__restrict__ sorted, unsigned 
 // the records of OUT (arriving = 0) or IN (arriving = 1) in their sorted order
 __global__ void ms_adjacency_kernel(const int32_t *__restrict__ tri, const int *__restrict__ sh, const unsigned char *__restrict__ hborder, int n, int arriving,
                                     int *__restrict__ nbr, int *__restrict__ opp) {
-    if (ms_tid() >= n) return;
-    const int i = (int)ms_tid();
+    if (dev_tid() >= n) return;
+    const int i = (int)dev_tid();
     const int h = sh[i], f = h / 3, c = h - 3 * f;
     nbr[i] = arriving ? tri[h] : tri[3 * (long)f + (c + 1) % 3];
     opp[i] = tri[3 * (long)f + (c + 2) % 3] | (hborder[h] ? MS_BORDER_BIT : 0);
 }
 
 __global__ void ms_vertex_border_kernel(const unsigned *__restrict__ boff, int V, unsigned char *__restrict__ vborder, int *__restrict__ vflag) {
-    if (ms_tid() >= V) return;
-    const int v = (int)ms_tid();
+    if (dev_tid() >= V) return;
+    const int v = (int)dev_tid();
     const int on = boff[v + 1] > boff[v] ? 1 : 0;
     vborder[v] = (unsigned char)on;
     vflag[v] = on;
@@ -177,8 +166,8 @@ template <int COT>
 __global__ void __launch_bounds__(256) ms_laplacian_kernel(const double *__restrict__ p, double *__restrict__ q, int V, const unsigned *__restrict__ ooff,
                                                            const unsigned *__restrict__ ioff, const int *__restrict__ nbr, const int *__restrict__ opp,
                                                            const unsigned char *__restrict__ vborder) {
-    if (ms_tid() >= V) return;
-    const int v = (int)ms_tid();
+    if (dev_tid() >= V) return;
+    const int v = (int)dev_tid();
     const ms_d3 pv = ms_load(p, v);
     const bool onb = vborder != nullptr && vborder[v] != 0;        // vborder == nullptr: boundary = 0, no half-edge is a border half-edge
     ms_d3 acc = onb ? pv : ms_d3{0.0, 0.0, 0.0};
@@ -217,8 +206,8 @@ __global__ void __launch_bounds__(256) ms_laplacian_kernel(const double *__restr
 // off1 (nullable): a second list walked after the first, over the same nbr array
 __global__ void __launch_bounds__(256) ms_umbrella_kernel(const double *__restrict__ p, double *__restrict__ q, int V, const unsigned *__restrict__ off0,
                                                           const unsigned *__restrict__ off1, const int *__restrict__ nbr, double k) {
-    if (ms_tid() >= V) return;
-    const int v = (int)ms_tid();
+    if (dev_tid() >= V) return;
+    const int v = (int)dev_tid();
     const ms_d3 pv = ms_load(p, v);
     ms_d3 acc = {0.0, 0.0, 0.0};
     unsigned deg = 0;
@@ -243,8 +232,8 @@ __global__ void __launch_bounds__(256) ms_umbrella_kernel(const double *__restri
 template <class T, int ANGLE>
 __global__ void __launch_bounds__(256) ms_normals_kernel(const T *__restrict__ p, const int32_t *__restrict__ tri, int V, const unsigned *__restrict__ coff,
                                                          const int *__restrict__ ch, double *__restrict__ unit, double *__restrict__ raw) {
-    if (ms_tid() >= V) return;
-    const int v = (int)ms_tid();
+    if (dev_tid() >= V) return;
+    const int v = (int)dev_tid();
     ms_d3 acc = {0.0, 0.0, 0.0};
     const unsigned e = coff[v + 1];
     for (unsigned i = coff[v]; i < e; ++i) {
@@ -307,108 +296,77 @@ extern "C" int surfd_meshsmooth_create(const int32_t *triangles, int F, int V, s
     if (F > 0 && !triangles) SURFD_FAIL(SURFD_ERR_ARG, "surfd_meshsmooth_create: null argument");
     if ((long)F * 3 > (long)INT_MAX) SURFD_FAIL(SURFD_ERR_ARG, "surfd_meshsmooth_create: 3 F must stay below 2^31, F = %d", F);
     hipStream_t st = as_stream(s);
-    surfd_meshsmooth *m = new surfd_meshsmooth();
+    std::unique_ptr<surfd_meshsmooth, void (*)(surfd_meshsmooth *)> owner(new surfd_meshsmooth(), ms_free);      // freed on every early return
+    surfd_meshsmooth *m = owner.get();
     m->F = F; m->V = V;
-    const int H = 3 * F;
-    ms_u64 *ekey = nullptr, *ekey2 = nullptr;
-    int *eh = nullptr, *eh2 = nullptr, *cpay = nullptr, *flag = nullptr, *rank = nullptr, *bdst = nullptr, *sh = nullptr, *scal = nullptr, *vflag = nullptr;
-    unsigned *okey = nullptr, *ikey = nullptr, *ckey = nullptr, *skey = nullptr, *bsrc = nullptr;
-    unsigned char *hborder = nullptr;
-    void *tmp = nullptr;
-    auto run = [&]() -> int {
-        if (F == 0) return SURFD_OK;
-        HIP_TRY(hipMalloc(&m->tri, ms_bytes<int32_t>(H)));
-        HIP_TRY(hipMalloc(&m->ooff, ms_bytes<unsigned>(V + 1L))); HIP_TRY(hipMalloc(&m->ioff, ms_bytes<unsigned>(V + 1L)));
-        HIP_TRY(hipMalloc(&m->coff, ms_bytes<unsigned>(V + 1L))); HIP_TRY(hipMalloc(&m->boff, ms_bytes<unsigned>(V + 1L)));
-        HIP_TRY(hipMalloc(&m->nbr, ms_bytes<int>(2L * H))); HIP_TRY(hipMalloc(&m->opp, ms_bytes<int>(2L * H)));
-        HIP_TRY(hipMalloc(&m->ch, ms_bytes<int>(H)));
-        HIP_TRY(hipMalloc(&m->vborder, ms_bytes<unsigned char>(V)));
-        HIP_TRY(hipMalloc(&ekey, ms_bytes<ms_u64>(H))); HIP_TRY(hipMalloc(&ekey2, ms_bytes<ms_u64>(H)));
-        HIP_TRY(hipMalloc(&eh, ms_bytes<int>(H))); HIP_TRY(hipMalloc(&eh2, ms_bytes<int>(H))); HIP_TRY(hipMalloc(&cpay, ms_bytes<int>(H)));
-        HIP_TRY(hipMalloc(&flag, ms_bytes<int>(H))); HIP_TRY(hipMalloc(&rank, ms_bytes<int>(H))); HIP_TRY(hipMalloc(&sh, ms_bytes<int>(H)));
-        HIP_TRY(hipMalloc(&okey, ms_bytes<unsigned>(H))); HIP_TRY(hipMalloc(&ikey, ms_bytes<unsigned>(H))); HIP_TRY(hipMalloc(&ckey, ms_bytes<unsigned>(H)));
-        HIP_TRY(hipMalloc(&skey, ms_bytes<unsigned>(H)));
-        HIP_TRY(hipMalloc(&hborder, ms_bytes<unsigned char>(H)));
-        HIP_TRY(hipMalloc(&vflag, ms_bytes<int>(V)));
-        HIP_TRY(hipMalloc(&scal, 4 * sizeof(int)));
-        HIP_TRY(hipMemsetAsync(scal, 0, 4 * sizeof(int), st));
-        HIP_TRY(hipMemcpyAsync(m->tri, triangles, (size_t)H * sizeof(int32_t), hipMemcpyDefault, st));
-        hipLaunchKernelGGL(ms_keys_kernel, dim3(ms_grid(F)), dim3(256), 0, st, (const int32_t *)m->tri, F, V, ekey, eh, okey, ikey, ckey, cpay, scal);
-        LAUNCH_CHECK();
-        // one workspace for every sort, scan and reduction below (2 B <= 2 H items at most)
-        size_t b[5] = {0, 0, 0, 0, 0};
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, b[0], ekey, ekey2, eh, eh2, H, 0, 64, st));
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, b[1], okey, skey, eh, sh, H, 0, 32, st));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, b[2], flag, rank, H, st));
-        HIP_TRY(hipcub::DeviceReduce::Sum(nullptr, b[3], vflag, scal, V, st));
-        size_t tmp_bytes = std::max(std::max(b[0], b[1]), std::max(b[2], b[3]));
-        tmp_bytes = 2 * tmp_bytes + 256;                     // the sort of the 2 B <= 2 H border records is sized below and checked
-        HIP_TRY(hipMalloc(&tmp, tmp_bytes));
-        size_t bytes = tmp_bytes;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, ekey, ekey2, eh, eh2, H, 0, 64, st));
-        hipLaunchKernelGGL(ms_border_flags_kernel, dim3(ms_grid(H)), dim3(256), 0, st, (const ms_u64 *)ekey2, H, flag);
-        LAUNCH_CHECK();
-        bytes = tmp_bytes;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, bytes, flag, rank, H, st));
-        hipLaunchKernelGGL(ms_total_kernel, dim3(1), dim3(64), 0, st, (const int *)flag, (const int *)rank, H, scal + 1);
-        LAUNCH_CHECK();
-        int hs[4];
-        HIP_TRY(hipMemcpyAsync(hs, scal, sizeof(hs), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (hs[0]) return mesh_bad_index("surfd_meshsmooth_create", V);        // nothing below this line sees an unvalidated index
-        const int B = hs[1];
-        m->B = B;
-        HIP_TRY(hipMalloc(&m->bnbr, ms_bytes<int>(2L * B)));
-        HIP_TRY(hipMalloc(&bsrc, ms_bytes<unsigned>(2L * B)));
-        HIP_TRY(hipMalloc(&bdst, ms_bytes<int>(2L * B)));
-        hipLaunchKernelGGL(ms_border_records_kernel, dim3(ms_grid(H)), dim3(256), 0, st, (const ms_u64 *)ekey2, (const int *)eh2, (const int *)flag,
-                           (const int *)rank, H, B, hborder, bsrc, bdst);
-        LAUNCH_CHECK();
-        // BN: the sorted keys (2 B <= 2 H words) go to ekey (8 H bytes), which the first sort has read and nothing needs any more
-        unsigned *bsorted = (unsigned *)ekey;
-        if (B > 0) {
-            bytes = 0;
-            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, bsrc, bsorted, bdst, m->bnbr, 2 * B, 0, 32, st));
-            if (bytes > tmp_bytes) SURFD_FAIL(SURFD_ERR_STATE, "surfd_meshsmooth_create: the sort workspace is too small (%zu > %zu bytes)", bytes, tmp_bytes);
-            bytes = tmp_bytes;
-            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, bsrc, bsorted, bdst, m->bnbr, 2 * B, 0, 32, st));
-        }
-        hipLaunchKernelGGL(ms_offsets_kernel, dim3(ms_grid(V + 1L)), dim3(256), 0, st, (const unsigned *)bsorted, 2u * (unsigned)B, V, 0u, m->boff);
-        LAUNCH_CHECK();
-        hipLaunchKernelGGL(ms_vertex_border_kernel, dim3(ms_grid(V)), dim3(256), 0, st, (const unsigned *)m->boff, V, m->vborder, vflag);
-        LAUNCH_CHECK();
-        if (V > 0) {
-            bytes = tmp_bytes;
-            HIP_TRY(hipcub::DeviceReduce::Sum(tmp, bytes, vflag, scal + 2, V, st));
-        }
-        // OUT, IN
-        for (int arriving = 0; arriving < 2; ++arriving) {
-            bytes = tmp_bytes;
-            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, arriving ? ikey : okey, skey, eh, sh, H, 0, 32, st));
-            const long base = arriving ? H : 0;
-            hipLaunchKernelGGL(ms_offsets_kernel, dim3(ms_grid(V + 1L)), dim3(256), 0, st, (const unsigned *)skey, (unsigned)H, V, (unsigned)base,
-                               arriving ? m->ioff : m->ooff);
-            LAUNCH_CHECK();
-            hipLaunchKernelGGL(ms_adjacency_kernel, dim3(ms_grid(H)), dim3(256), 0, st, (const int32_t *)m->tri, (const int *)sh, (const unsigned char *)hborder, H,
-                               arriving, m->nbr + base, m->opp + base);
-            LAUNCH_CHECK();
-        }
-        // corners, ascending in (c, f) inside a vertex
-        bytes = tmp_bytes;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, ckey, skey, cpay, m->ch, H, 0, 32, st));
-        hipLaunchKernelGGL(ms_offsets_kernel, dim3(ms_grid(V + 1L)), dim3(256), 0, st, (const unsigned *)skey, (unsigned)H, V, 0u, m->coff);
-        LAUNCH_CHECK();
-        HIP_TRY(hipMemcpyAsync(hs, scal, sizeof(hs), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));                    // the temporaries are freed next
-        m->n_border_vertices = hs[2];
+    if (F == 0) {
+        *out = owner.release();
         return SURFD_OK;
-    };
-    const int rc = run();
-    (void)hipFree(ekey); (void)hipFree(ekey2); (void)hipFree(eh); (void)hipFree(eh2); (void)hipFree(cpay); (void)hipFree(flag); (void)hipFree(rank);
-    (void)hipFree(bdst); (void)hipFree(sh); (void)hipFree(scal); (void)hipFree(vflag); (void)hipFree(okey); (void)hipFree(ikey); (void)hipFree(ckey);
-    (void)hipFree(skey); (void)hipFree(bsrc); (void)hipFree(hborder); (void)hipFree(tmp);
-    if (rc != SURFD_OK) { ms_free(m); return rc; }
-    *out = m;
+    }
+    const int H = 3 * F;
+    HIP_TRY(hipMalloc(&m->tri, dev_bytes<int32_t>(H)));
+    HIP_TRY(hipMalloc(&m->ooff, dev_bytes<unsigned>(V + 1L))); HIP_TRY(hipMalloc(&m->ioff, dev_bytes<unsigned>(V + 1L)));
+    HIP_TRY(hipMalloc(&m->coff, dev_bytes<unsigned>(V + 1L))); HIP_TRY(hipMalloc(&m->boff, dev_bytes<unsigned>(V + 1L)));
+    HIP_TRY(hipMalloc(&m->nbr, dev_bytes<int>(2L * H))); HIP_TRY(hipMalloc(&m->opp, dev_bytes<int>(2L * H)));
+    HIP_TRY(hipMalloc(&m->ch, dev_bytes<int>(H)));
+    HIP_TRY(hipMalloc(&m->vborder, dev_bytes<unsigned char>(V)));
+    DeviceScratch scratch;
+    CubWorkspace cub{&scratch};                             // one workspace for every sort, scan and reduction below
+    ms_u64 *ekey, *ekey2;
+    int *eh, *eh2, *cpay, *flag, *rank, *bdst, *sh, *scal, *vflag;
+    unsigned *okey, *ikey, *ckey, *skey, *bsrc;
+    unsigned char *hborder;
+    SURFD_TRY(scratch.get(&ekey, H)); SURFD_TRY(scratch.get(&ekey2, H)); SURFD_TRY(scratch.get(&eh, H)); SURFD_TRY(scratch.get(&eh2, H));
+    SURFD_TRY(scratch.get(&cpay, H)); SURFD_TRY(scratch.get(&flag, H)); SURFD_TRY(scratch.get(&rank, H)); SURFD_TRY(scratch.get(&sh, H));
+    SURFD_TRY(scratch.get(&okey, H)); SURFD_TRY(scratch.get(&ikey, H)); SURFD_TRY(scratch.get(&ckey, H)); SURFD_TRY(scratch.get(&skey, H));
+    SURFD_TRY(scratch.get(&hborder, H)); SURFD_TRY(scratch.get(&vflag, V)); SURFD_TRY(scratch.get(&scal, 4));
+    HIP_TRY(hipMemsetAsync(scal, 0, 4 * sizeof(int), st));
+    HIP_TRY(hipMemcpyAsync(m->tri, triangles, (size_t)H * sizeof(int32_t), hipMemcpyDefault, st));
+    hipLaunchKernelGGL(ms_keys_kernel, dim3(dev_grid(F)), dim3(256), 0, st, (const int32_t *)m->tri, F, V, ekey, eh, okey, ikey, ckey, cpay, scal);
+    LAUNCH_CHECK();
+    SURFD_TRY(cub.sort_pairs(ekey, ekey2, eh, eh2, H, 64, st));
+    hipLaunchKernelGGL(ms_border_flags_kernel, dim3(dev_grid(H)), dim3(256), 0, st, (const ms_u64 *)ekey2, H, flag);
+    LAUNCH_CHECK();
+    SURFD_TRY(cub.exclusive_sum(flag, rank, H, st));
+    SURFD_TRY(scan_total(flag, rank, H, scal + 1, st));
+    int hs[4];
+    HIP_TRY(hipMemcpyAsync(hs, scal, sizeof(hs), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (hs[0]) return mesh_bad_index("surfd_meshsmooth_create", V);        // nothing below this line sees an unvalidated index
+    const int B = m->B = hs[1];
+    HIP_TRY(hipMalloc(&m->bnbr, dev_bytes<int>(2L * B)));
+    SURFD_TRY(scratch.get(&bsrc, 2L * B));
+    SURFD_TRY(scratch.get(&bdst, 2L * B));
+    hipLaunchKernelGGL(ms_border_records_kernel, dim3(dev_grid(H)), dim3(256), 0, st, (const ms_u64 *)ekey2, (const int *)eh2, (const int *)flag,
+                       (const int *)rank, H, B, hborder, bsrc, bdst);
+    LAUNCH_CHECK();
+    // BN: the sorted keys (2 B <= 2 H words) go to ekey (8 H bytes), which the first sort has read and nothing needs any more
+    unsigned *bsorted = (unsigned *)ekey;
+    if (B > 0) SURFD_TRY(cub.sort_pairs(bsrc, bsorted, bdst, m->bnbr, 2 * B, 32, st));
+    hipLaunchKernelGGL(ms_offsets_kernel, dim3(dev_grid(V + 1L)), dim3(256), 0, st, (const unsigned *)bsorted, 2u * (unsigned)B, V, 0u, m->boff);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(ms_vertex_border_kernel, dim3(dev_grid(V)), dim3(256), 0, st, (const unsigned *)m->boff, V, m->vborder, vflag);
+    LAUNCH_CHECK();
+    if (V > 0) SURFD_TRY(cub.reduce_sum(vflag, scal + 2, V, st));
+    // OUT, IN
+    for (int arriving = 0; arriving < 2; ++arriving) {
+        SURFD_TRY(cub.sort_pairs(arriving ? ikey : okey, skey, eh, sh, H, 32, st));
+        const long base = arriving ? H : 0;
+        hipLaunchKernelGGL(ms_offsets_kernel, dim3(dev_grid(V + 1L)), dim3(256), 0, st, (const unsigned *)skey, (unsigned)H, V, (unsigned)base,
+                           arriving ? m->ioff : m->ooff);
+        LAUNCH_CHECK();
+        hipLaunchKernelGGL(ms_adjacency_kernel, dim3(dev_grid(H)), dim3(256), 0, st, (const int32_t *)m->tri, (const int *)sh, (const unsigned char *)hborder, H,
+                           arriving, m->nbr + base, m->opp + base);
+        LAUNCH_CHECK();
+    }
+    // corners, ascending in (c, f) inside a vertex
+    SURFD_TRY(cub.sort_pairs(ckey, skey, cpay, m->ch, H, 32, st));
+    hipLaunchKernelGGL(ms_offsets_kernel, dim3(dev_grid(V + 1L)), dim3(256), 0, st, (const unsigned *)skey, (unsigned)H, V, 0u, m->coff);
+    LAUNCH_CHECK();
+    HIP_TRY(hipMemcpyAsync(hs, scal, sizeof(hs), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));                        // the scratch is freed next
+    m->n_border_vertices = hs[2];
+    *out = owner.release();
     return SURFD_OK;
 }
 
@@ -445,7 +403,7 @@ int ms_import(const void *vertices, int dtype, long n, double *dst, hipStream_t 
     if (dtype == SURFD_MESHSMOOTH_F64) {
         if (vertices != (const void *)dst) HIP_TRY(hipMemcpyAsync(dst, vertices, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
     } else {
-        hipLaunchKernelGGL(ms_convert_kernel<float>, dim3(ms_grid(n)), dim3(256), 0, st, (const float *)vertices, n, dst);
+        hipLaunchKernelGGL(ms_convert_kernel<float>, dim3(dev_grid(n)), dim3(256), 0, st, (const float *)vertices, n, dst);
         LAUNCH_CHECK();
     }
     return SURFD_OK;
@@ -477,7 +435,7 @@ extern "C" int surfd_meshsmooth_laplacian(surfd_meshsmooth *m, const void *verti
     for (int i = 0; i < steps; ++i) {
         double *dst = i == steps - 1 ? out : (src == buf.a ? buf.b : buf.a);
         auto kernel = cotangent ? ms_laplacian_kernel<1> : ms_laplacian_kernel<0>;
-        hipLaunchKernelGGL(kernel, dim3(ms_grid(V)), dim3(256), 0, st, src, dst, V, (const unsigned *)m->ooff, (const unsigned *)m->ioff, (const int *)m->nbr,
+        hipLaunchKernelGGL(kernel, dim3(dev_grid(V)), dim3(256), 0, st, src, dst, V, (const unsigned *)m->ooff, (const unsigned *)m->ioff, (const int *)m->nbr,
                            (const int *)m->opp, vb);
         LAUNCH_CHECK();
         src = dst;
@@ -502,7 +460,7 @@ extern "C" int surfd_meshsmooth_umbrella(surfd_meshsmooth *m, const void *vertic
     const double *src = buf.a;
     for (int i = 0; i < sweeps; ++i) {
         double *dst = i == sweeps - 1 ? out : (src == buf.a ? buf.b : buf.a);
-        hipLaunchKernelGGL(ms_umbrella_kernel, dim3(ms_grid(V)), dim3(256), 0, st, src, dst, V, (const unsigned *)(border ? m->boff : m->ooff),
+        hipLaunchKernelGGL(ms_umbrella_kernel, dim3(dev_grid(V)), dim3(256), 0, st, src, dst, V, (const unsigned *)(border ? m->boff : m->ooff),
                            (const unsigned *)(border ? nullptr : m->ioff), (const int *)(border ? m->bnbr : m->nbr), (i & 1) ? k1 : k0);
         LAUNCH_CHECK();
         src = dst;
@@ -525,7 +483,7 @@ extern "C" int surfd_meshsmooth_vertex_normals(surfd_meshsmooth *m, const void *
         if (raw) HIP_TRY(hipMemsetAsync(raw, 0, (size_t)V * 3 * sizeof(double), st));
         return SURFD_OK;
     }
-    const dim3 grid(ms_grid(V)), block(256);
+    const dim3 grid(dev_grid(V)), block(256);
     const unsigned *coff = m->coff;
     const int *ch = m->ch;
     const int32_t *tri = m->tri;

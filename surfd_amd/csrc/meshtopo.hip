@@ -80,10 +80,9 @@
 // Bounds: every kernel guards its thread index against the count it is launched for; vertex-indexed arrays are indexed only
 // by indices that create validated; edge ids come from the exclusive sum and lie in [0, E); pair nodes lie in [0, n).
 #include "common.h"
-#include <algorithm>
+#include "devscratch.h"
 #include <climits>
 #include <cmath>
-#include <hipcub/hipcub.hpp>
 
 namespace surfd {
 
@@ -96,8 +95,7 @@ enum { MT_CNT_BAD = 0, MT_CNT_FIRST_BAD = 1, MT_CNT_DEGENERATE = 2, MT_CNT_REFER
 
 // ---- the connected-components routine ------------------------------------------------------------------------------------
 __global__ void mt_iota_kernel(int *__restrict__ a, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) a[i] = i;
+    if (dev_tid() < n) a[dev_tid()] = (int)dev_tid();
 }
 
 __device__ __forceinline__ int cc_find(int *parent, int x) {
@@ -112,8 +110,8 @@ __device__ __forceinline__ int cc_find(int *parent, int x) {
 }
 
 __global__ void cc_hook_kernel(int *parent, const int2 *__restrict__ pairs, int n_pairs) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_pairs) return;
+    if (dev_tid() >= n_pairs) return;
+    const int i = (int)dev_tid();
     int a = pairs[i].x, b = pairs[i].y;
     if (a < 0) return;
     for (;;) {
@@ -128,8 +126,8 @@ __global__ void cc_hook_kernel(int *parent, const int2 *__restrict__ pairs, int 
 }
 
 __global__ void cc_compress_kernel(int *parent, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+    if (dev_tid() >= n) return;
+    const int i = (int)dev_tid();
     int r = i;
     for (;;) {
         const int p = MT_LD(parent + r);
@@ -155,8 +153,8 @@ static int cc_run(int *parent, int n, const int2 *pairs, int n_pairs, hipStream_
 // ---- edges ---------------------------------------------------------------------------------------------------------------
 __global__ void mt_keys_kernel(const int32_t *__restrict__ tri, int F, int V, u64 *__restrict__ keys, int *__restrict__ hidx,
                                unsigned char *__restrict__ degenerate, int *used, int *cnt) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= F) return;
+    if (dev_tid() >= F) return;
+    const int f = (int)dev_tid();
     const int t[3] = {tri[3 * (long)f], tri[3 * (long)f + 1], tri[3 * (long)f + 2]};
     const bool bad = t[0] < 0 || t[0] >= V || t[1] < 0 || t[1] >= V || t[2] < 0 || t[2] >= V;
     const bool deg = !bad && (t[0] == t[1] || t[1] == t[2] || t[0] == t[2]);
@@ -175,21 +173,17 @@ __global__ void mt_keys_kernel(const int32_t *__restrict__ tri, int F, int V, u6
 }
 
 __global__ void mt_heads_kernel(const u64 *__restrict__ skeys, int n, int *__restrict__ head) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+    if (dev_tid() >= n) return;
+    const int i = (int)dev_tid();
     const u64 k = skeys[i];
     head[i] = (k != MT_KEY_NONE && (i == 0 || skeys[i - 1] != k)) ? 1 : 0;
-}
-
-__global__ void mt_total_kernel(const int *__restrict__ flag, const int *__restrict__ excl, int n, int *__restrict__ out) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) *out = n > 0 ? excl[n - 1] + flag[n - 1] : 0;
 }
 
 __global__ void mt_fill_kernel(const u64 *__restrict__ skeys, const int *__restrict__ shidx, const int *__restrict__ head,
                                const int *__restrict__ excl, int H, int E, int32_t *__restrict__ edges, int32_t *__restrict__ edge_offsets,
                                int32_t *__restrict__ edge_halfedges, int32_t *__restrict__ face_edges) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= H) return;
+    if (dev_tid() >= H) return;
+    const int i = (int)dev_tid();
     const int e = excl[i] + head[i] - 1;
     const int h = shidx[i];
     face_edges[h] = e;
@@ -205,8 +199,8 @@ __global__ void mt_fill_kernel(const u64 *__restrict__ skeys, const int *__restr
 
 __global__ void mt_neighbors_kernel(int H, int E, const int32_t *__restrict__ edge_offsets, const int32_t *__restrict__ edge_halfedges,
                                     const int32_t *__restrict__ face_edges, int32_t *__restrict__ valence, int32_t *__restrict__ face_neighbors) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= H) return;
+    if (dev_tid() >= H) return;
+    const int i = (int)dev_tid();
     const int h = edge_halfedges[i];
     const int e = face_edges[h];
     const int s = edge_offsets[e], val = edge_offsets[e + 1] - s;
@@ -216,8 +210,8 @@ __global__ void mt_neighbors_kernel(int H, int E, const int32_t *__restrict__ ed
 
 // ---- pair lists ----------------------------------------------------------------------------------------------------------
 __global__ void mt_pairs_vertex_kernel(const int32_t *__restrict__ tri, const unsigned char *__restrict__ degenerate, int F, int2 *__restrict__ pairs) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= F) return;
+    if (dev_tid() >= F) return;
+    const int f = (int)dev_tid();
     const bool deg = degenerate[f] != 0;
     const int a = tri[3 * (long)f], b = tri[3 * (long)f + 1], c = tri[3 * (long)f + 2];
     pairs[2 * (long)f] = deg ? make_int2(-1, -1) : make_int2(a, b);
@@ -226,8 +220,8 @@ __global__ void mt_pairs_vertex_kernel(const int32_t *__restrict__ tri, const un
 
 __global__ void mt_pairs_faces_kernel(int H, const int32_t *__restrict__ edge_offsets, const int32_t *__restrict__ edge_halfedges,
                                       const int32_t *__restrict__ face_edges, int manifold_only, int2 *__restrict__ pairs) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= H) return;
+    if (dev_tid() >= H) return;
+    const int i = (int)dev_tid();
     const int h = edge_halfedges[i];
     const int e = face_edges[h];
     const int s = edge_offsets[e], val = edge_offsets[e + 1] - s;
@@ -236,8 +230,8 @@ __global__ void mt_pairs_faces_kernel(int H, const int32_t *__restrict__ edge_of
 
 __global__ void mt_pairs_orient_kernel(int E, const int32_t *__restrict__ edges, const int32_t *__restrict__ edge_offsets,
                                        const int32_t *__restrict__ edge_halfedges, const int32_t *__restrict__ tri, int2 *__restrict__ pairs) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
+    if (dev_tid() >= E) return;
+    const int e = (int)dev_tid();
     const int s = edge_offsets[e], val = edge_offsets[e + 1] - s;
     int2 p0 = make_int2(-1, -1), p1 = make_int2(-1, -1);
     if (val == 2) {
@@ -253,8 +247,8 @@ __global__ void mt_pairs_orient_kernel(int E, const int32_t *__restrict__ edges,
 }
 
 __global__ void mt_border_vertices_kernel(int E, const int32_t *__restrict__ edges, const int32_t *__restrict__ valence, int *vfirst, int *vdeg) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E || valence[e] != 1) return;
+    if (dev_tid() >= E || valence[dev_tid()] != 1) return;
+    const int e = (int)dev_tid();
     const int lo = edges[2 * (long)e], hi = edges[2 * (long)e + 1];
     atomicMin(vfirst + lo, e); atomicMin(vfirst + hi, e);
     atomicAdd(vdeg + lo, 1); atomicAdd(vdeg + hi, 1);
@@ -262,8 +256,8 @@ __global__ void mt_border_vertices_kernel(int E, const int32_t *__restrict__ edg
 
 __global__ void mt_pairs_border_kernel(int E, const int32_t *__restrict__ edges, const int32_t *__restrict__ valence, const int *__restrict__ vfirst,
                                        const int *__restrict__ vdeg, int2 *__restrict__ pairs, unsigned char *__restrict__ irregular) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
+    if (dev_tid() >= E) return;
+    const int e = (int)dev_tid();
     int2 p0 = make_int2(-1, -1), p1 = make_int2(-1, -1);
     unsigned char irr = 0;
     if (valence[e] == 1) {
@@ -279,8 +273,8 @@ __global__ void mt_pairs_border_kernel(int E, const int32_t *__restrict__ edges,
 
 // ---- labels --------------------------------------------------------------------------------------------------------------
 __global__ void mt_minface_kernel(const int32_t *__restrict__ tri, const unsigned char *__restrict__ degenerate, int F, const int *__restrict__ parent, int *minface) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= F || degenerate[f]) return;
+    if (dev_tid() >= F || degenerate[dev_tid()]) return;
+    const int f = (int)dev_tid();
     int *slot = minface + parent[tri[3 * (long)f]];
     if (f < MT_LD(slot)) atomicMin(slot, f);      // the word only falls, so a face that is not below it cannot be the minimum: one
                                                   // large component would otherwise send every face's atomic to one address
@@ -288,31 +282,31 @@ __global__ void mt_minface_kernel(const int32_t *__restrict__ tri, const unsigne
 
 __global__ void mt_rootface_vertex_kernel(const int32_t *__restrict__ tri, const unsigned char *__restrict__ degenerate, int F, const int *__restrict__ parent,
                                           const int *__restrict__ minface, int *__restrict__ rootface) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= F) return;
+    if (dev_tid() >= F) return;
+    const int f = (int)dev_tid();
     rootface[f] = degenerate[f] ? -1 : minface[parent[tri[3 * (long)f]]];
 }
 
 __global__ void mt_rootface_faces_kernel(const unsigned char *__restrict__ degenerate, int F, const int *__restrict__ parent, int *__restrict__ rootface) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= F) return;
+    if (dev_tid() >= F) return;
+    const int f = (int)dev_tid();
     rootface[f] = degenerate[f] ? -1 : parent[f];
 }
 
 __global__ void mt_rootface_border_kernel(const int32_t *__restrict__ valence, int E, const int *__restrict__ parent, int *__restrict__ rootface) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
+    if (dev_tid() >= E) return;
+    const int e = (int)dev_tid();
     rootface[e] = valence[e] == 1 ? parent[e] : -1;
 }
 
 __global__ void mt_isroot_kernel(const int *__restrict__ rootface, int n, int *__restrict__ isroot) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) isroot[i] = rootface[i] == i ? 1 : 0;
+    const int i = (int)dev_tid();
+    if (dev_tid() < n) isroot[i] = rootface[i] == i ? 1 : 0;
 }
 
 __global__ void mt_labels_kernel(const int *__restrict__ rootface, const int *__restrict__ rank, int n, int32_t *__restrict__ labels) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+    if (dev_tid() >= n) return;
+    const int i = (int)dev_tid();
     const int r = rootface[i];
     labels[i] = r < 0 ? -1 : rank[r];
 }
@@ -320,8 +314,8 @@ __global__ void mt_labels_kernel(const int *__restrict__ rootface, const int *__
 // ---- orientation ---------------------------------------------------------------------------------------------------------
 __global__ void mt_flip_kernel(const unsigned char *__restrict__ degenerate, int F, const int *__restrict__ parent, unsigned char *__restrict__ flip,
                                unsigned char *__restrict__ orientable, int32_t *__restrict__ patch_face) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= F) return;
+    if (dev_tid() >= F) return;
+    const int f = (int)dev_tid();
     const int r0 = parent[2 * (long)f], r1 = parent[2 * (long)f + 1];
     const bool deg = degenerate[f] != 0, ok = r0 != r1;
     flip[f] = (!deg && ok) ? (unsigned char)(r0 & 1) : 0;
@@ -330,7 +324,7 @@ __global__ void mt_flip_kernel(const unsigned char *__restrict__ degenerate, int
 }
 
 __global__ void mt_maxabs_kernel(const float *__restrict__ vertices, long n, unsigned *maxbits) {
-    const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    const long i = dev_tid();
     if (i >= n) return;
     const float a = fabsf(vertices[i]);
     if (a <= 3.4028234663852886e38f) atomicMax(maxbits, __float_as_uint(a));      // false for a NaN and for +inf; bits of a >= 0 order as a does
@@ -339,8 +333,8 @@ __global__ void mt_maxabs_kernel(const float *__restrict__ vertices, long n, uns
 __global__ void mt_volume_kernel(const int32_t *__restrict__ tri, const float *__restrict__ vertices, int F, const int32_t *__restrict__ face_edges,
                                  const int32_t *__restrict__ valence, const unsigned char *__restrict__ flip, const int32_t *__restrict__ patch_face,
                                  const unsigned *__restrict__ maxbits, u64 *volume, int *open_patch) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;          // no early return: every lane of a wave takes part in the shuffles
-    const int root = f < F ? patch_face[f] : -1;
+    const int f = (int)dev_tid();                                  // no early return: every lane of a wave takes part in the shuffles
+    const int root = dev_tid() < F ? patch_face[f] : -1;
     long long q = 0;
     int open = 0;
     if (root >= 0) {
@@ -389,8 +383,8 @@ __global__ void mt_volume_kernel(const int32_t *__restrict__ tri, const float *_
 
 __global__ void mt_turn_kernel(int F, const int32_t *__restrict__ patch_face, const unsigned char *__restrict__ orientable, const u64 *__restrict__ volume,
                                const int *__restrict__ open_patch, unsigned char *__restrict__ flip) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= F) return;
+    if (dev_tid() >= F) return;
+    const int f = (int)dev_tid();
     const int root = patch_face[f];
     if (root < 0 || !orientable[f] || open_patch[root]) return;
     if ((long long)volume[root] < 0) flip[f] ^= 1;
@@ -400,22 +394,22 @@ __global__ void mt_turn_kernel(int F, const int32_t *__restrict__ patch_face, co
 __device__ __forceinline__ unsigned mt_coord_bits(float x) { return x == 0.f ? 0u : __float_as_uint(x); }      // -0 -> +0
 
 __global__ void mt_weld_key_z_kernel(const float *__restrict__ vertices, int V, unsigned *__restrict__ key, int *__restrict__ idx) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= V) return;
+    if (dev_tid() >= V) return;
+    const int i = (int)dev_tid();
     key[i] = mt_coord_bits(vertices[3 * (long)i + 2]);
     idx[i] = i;
 }
 
 __global__ void mt_weld_key_xy_kernel(const float *__restrict__ vertices, int V, const int *__restrict__ idx, u64 *__restrict__ key) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= V) return;
+    if (dev_tid() >= V) return;
+    const int i = (int)dev_tid();
     const long v = idx[i];
     key[i] = ((u64)mt_coord_bits(vertices[3 * v]) << 32) | (u64)mt_coord_bits(vertices[3 * v + 1]);
 }
 
 __global__ void mt_weld_heads_kernel(const float *__restrict__ vertices, int V, const int *__restrict__ idx, int *__restrict__ headpos) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= V) return;
+    if (dev_tid() >= V) return;
+    const int i = (int)dev_tid();
     bool same = i > 0;
     if (same) {
         const long a = idx[i], b = idx[i - 1];
@@ -426,8 +420,8 @@ __global__ void mt_weld_heads_kernel(const float *__restrict__ vertices, int V, 
 }
 
 __global__ void mt_weld_rep_kernel(int V, const int *__restrict__ idx, const int *__restrict__ headpos, int *__restrict__ rep, int *__restrict__ survives) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= V) return;
+    if (dev_tid() >= V) return;
+    const int i = (int)dev_tid();
     const int v = idx[i], r = idx[headpos[i]];
     rep[v] = r;
     survives[v] = v == r ? 1 : 0;
@@ -435,8 +429,8 @@ __global__ void mt_weld_rep_kernel(int V, const int *__restrict__ idx, const int
 
 __global__ void mt_weld_map_kernel(int V, const int *__restrict__ rep, const int *__restrict__ survives, const int *__restrict__ newidx,
                                    int32_t *__restrict__ vertex_map, unsigned char *__restrict__ survivor) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= V) return;
+    if (dev_tid() >= V) return;
+    const int i = (int)dev_tid();
     vertex_map[i] = newidx[rep[i]];
     survivor[i] = (unsigned char)survives[i];
 }
@@ -461,21 +455,16 @@ struct surfd_meshtopo {
     u64 *volume = nullptr;                   // F
     int *open_patch = nullptr;               // F
     int *scalars = nullptr;                  // [0] a count, [1] the bits of max |coordinate|
-    void *scan_tmp = nullptr;
-    size_t scan_bytes = 0;
+    CubWorkspace scan;                       // the handle's own: sized by create's scan over 3 F >= max(F, E) items, the longest
 };
 
 static void mt_free(surfd_meshtopo *m) {
     (void)hipFree(m->tri); (void)hipFree(m->edges); (void)hipFree(m->valence); (void)hipFree(m->edge_offsets); (void)hipFree(m->edge_halfedges);
     (void)hipFree(m->face_edges); (void)hipFree(m->face_neighbors); (void)hipFree(m->degenerate); (void)hipFree(m->parent); (void)hipFree(m->pairs);
     (void)hipFree(m->rootface); (void)hipFree(m->isroot); (void)hipFree(m->rank); (void)hipFree(m->vaux); (void)hipFree(m->patch_face);
-    (void)hipFree(m->orientable); (void)hipFree(m->volume); (void)hipFree(m->open_patch); (void)hipFree(m->scalars); (void)hipFree(m->scan_tmp);
+    (void)hipFree(m->orientable); (void)hipFree(m->volume); (void)hipFree(m->open_patch); (void)hipFree(m->scalars); (void)hipFree(m->scan.ptr);
     delete m;
 }
-
-template <typename T>
-static inline size_t mt_bytes(long n) { return (size_t)(n > 0 ? n : 1) * sizeof(T); }
-static inline unsigned mt_grid(long n) { return (unsigned)ceil_div(n > 0 ? n : 1L, 256L); }
 
 extern "C" int surfd_meshtopo_create(const int32_t *triangles, int F, int V, surfd_stream s, surfd_meshtopo **out) {
     if (!out) SURFD_FAIL(SURFD_ERR_ARG, "surfd_meshtopo_create: null argument");
@@ -484,95 +473,77 @@ extern "C" int surfd_meshtopo_create(const int32_t *triangles, int F, int V, sur
     if (F > 0 && !triangles) SURFD_FAIL(SURFD_ERR_ARG, "surfd_meshtopo_create: null argument");
     if ((long)F * 3 > (long)INT_MAX) SURFD_FAIL(SURFD_ERR_ARG, "surfd_meshtopo_create: 3 F must stay below 2^31, F = %d", F);
     hipStream_t st = as_stream(s);
-    surfd_meshtopo *m = new surfd_meshtopo();
+    std::unique_ptr<surfd_meshtopo, void (*)(surfd_meshtopo *)> owner(new surfd_meshtopo(), mt_free);      // freed on every early return
+    surfd_meshtopo *m = owner.get();
     m->F = F; m->V = V;
     const int n3 = 3 * F;
-    u64 *keys = nullptr, *skeys = nullptr;
-    int *hidx = nullptr, *shidx = nullptr, *head = nullptr, *excl = nullptr, *used = nullptr, *cnt = nullptr;
-    void *sort_tmp = nullptr;
-    auto run = [&]() -> int {
-        HIP_TRY(hipMalloc(&m->tri, mt_bytes<int32_t>(n3)));
-        HIP_TRY(hipMalloc(&m->degenerate, mt_bytes<unsigned char>(F)));
-        HIP_TRY(hipMalloc(&m->face_edges, mt_bytes<int32_t>(n3)));
-        HIP_TRY(hipMalloc(&m->face_neighbors, mt_bytes<int32_t>(n3)));
-        HIP_TRY(hipMalloc(&m->scalars, 16));
-        if (F == 0) {
-            HIP_TRY(hipMalloc(&m->edge_offsets, sizeof(int32_t)));
-            HIP_TRY(hipMemsetAsync(m->edge_offsets, 0, sizeof(int32_t), st));
-            HIP_TRY(hipStreamSynchronize(st));
-            return SURFD_OK;
-        }
-        HIP_TRY(hipMalloc(&keys, mt_bytes<u64>(n3)));
-        HIP_TRY(hipMalloc(&skeys, mt_bytes<u64>(n3)));
-        HIP_TRY(hipMalloc(&hidx, mt_bytes<int>(n3)));
-        HIP_TRY(hipMalloc(&shidx, mt_bytes<int>(n3)));
-        HIP_TRY(hipMalloc(&head, mt_bytes<int>(n3)));
-        HIP_TRY(hipMalloc(&excl, mt_bytes<int>(n3)));
-        HIP_TRY(hipMalloc(&used, mt_bytes<int>(V)));
-        HIP_TRY(hipMalloc(&cnt, MT_CNT_WORDS * sizeof(int)));
-        HIP_TRY(hipMemcpyAsync(m->tri, triangles, (size_t)n3 * sizeof(int32_t), hipMemcpyDefault, st));
-        HIP_TRY(hipMemsetAsync(used, 0, mt_bytes<int>(V), st));
-        const int cnt0[MT_CNT_WORDS] = {0, INT_MAX, 0, 0, 0, 0, 0, 0};
-        HIP_TRY(hipMemcpyAsync(cnt, cnt0, sizeof(cnt0), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(m->face_edges, 0xFF, mt_bytes<int32_t>(n3), st));
-        HIP_TRY(hipMemsetAsync(m->face_neighbors, 0xFF, mt_bytes<int32_t>(n3), st));
-        hipLaunchKernelGGL(mt_keys_kernel, dim3(mt_grid(F)), dim3(256), 0, st, (const int32_t *)m->tri, F, V, keys, hidx, m->degenerate, used, cnt);
-        LAUNCH_CHECK();
-        size_t sort_bytes = 0, scan_bytes = 0;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, keys, skeys, hidx, shidx, n3, 0, 64, st));
-        HIP_TRY(hipMalloc(&sort_tmp, sort_bytes ? sort_bytes : 16));
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(sort_tmp, sort_bytes, keys, skeys, hidx, shidx, n3, 0, 64, st));
-        hipLaunchKernelGGL(mt_heads_kernel, dim3(mt_grid(n3)), dim3(256), 0, st, (const u64 *)skeys, n3, head);
-        LAUNCH_CHECK();
-        // the scan workspace of the handle serves every later scan: sized for the longest (3 F >= max(F, E))
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, head, excl, n3, st));
-        m->scan_bytes = scan_bytes ? scan_bytes : 16;
-        HIP_TRY(hipMalloc(&m->scan_tmp, m->scan_bytes));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(m->scan_tmp, scan_bytes, head, excl, n3, st));
-        hipLaunchKernelGGL(mt_total_kernel, dim3(1), dim3(64), 0, st, (const int *)head, (const int *)excl, n3, cnt + MT_CNT_E);
-        LAUNCH_CHECK();
-        int hc[MT_CNT_WORDS];
-        HIP_TRY(hipMemcpyAsync(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMalloc(&m->tri, dev_bytes<int32_t>(n3)));
+    HIP_TRY(hipMalloc(&m->degenerate, dev_bytes<unsigned char>(F)));
+    HIP_TRY(hipMalloc(&m->face_edges, dev_bytes<int32_t>(n3)));
+    HIP_TRY(hipMalloc(&m->face_neighbors, dev_bytes<int32_t>(n3)));
+    HIP_TRY(hipMalloc(&m->scalars, 16));
+    if (F == 0) {
+        HIP_TRY(hipMalloc(&m->edge_offsets, sizeof(int32_t)));
+        HIP_TRY(hipMemsetAsync(m->edge_offsets, 0, sizeof(int32_t), st));
         HIP_TRY(hipStreamSynchronize(st));
-        if (hc[MT_CNT_BAD] > 0)
-            SURFD_FAIL(SURFD_ERR_ARG, "surfd_meshtopo_create: %d faces name vertices outside [0, %d), the first is face %d", hc[MT_CNT_BAD], V, hc[MT_CNT_FIRST_BAD]);
-        m->n_degenerate = hc[MT_CNT_DEGENERATE];
-        m->n_referenced = hc[MT_CNT_REFERENCED];
-        m->E = hc[MT_CNT_E];
-        m->H = 3 * (F - m->n_degenerate);
-        const int E = m->E, H = m->H;
-        HIP_TRY(hipMalloc(&m->edges, mt_bytes<int32_t>(2L * E)));
-        HIP_TRY(hipMalloc(&m->valence, mt_bytes<int32_t>(E)));
-        HIP_TRY(hipMalloc(&m->edge_offsets, mt_bytes<int32_t>(E + 1L)));
-        HIP_TRY(hipMalloc(&m->edge_halfedges, mt_bytes<int32_t>(H)));
-        HIP_TRY(hipMemsetAsync(m->edge_offsets, 0, mt_bytes<int32_t>(E + 1L), st));
-        if (H > 0) {
-            hipLaunchKernelGGL(mt_fill_kernel, dim3(mt_grid(H)), dim3(256), 0, st, (const u64 *)skeys, (const int *)shidx, (const int *)head, (const int *)excl,
-                               H, E, m->edges, m->edge_offsets, m->edge_halfedges, m->face_edges);
-            LAUNCH_CHECK();
-            hipLaunchKernelGGL(mt_neighbors_kernel, dim3(mt_grid(H)), dim3(256), 0, st, H, E, (const int32_t *)m->edge_offsets,
-                               (const int32_t *)m->edge_halfedges, (const int32_t *)m->face_edges, m->valence, m->face_neighbors);
-            LAUNCH_CHECK();
-        }
-        const long n_nodes = std::max(std::max(2L * F, (long)V), (long)E), n_pairs = std::max(3L * F, 2L * E), n_fe = std::max(F, E);
-        HIP_TRY(hipMalloc(&m->parent, mt_bytes<int>(n_nodes)));
-        HIP_TRY(hipMalloc(&m->pairs, mt_bytes<int2>(n_pairs)));
-        HIP_TRY(hipMalloc(&m->rootface, mt_bytes<int>(n_fe)));
-        HIP_TRY(hipMalloc(&m->isroot, mt_bytes<int>(n_fe)));
-        HIP_TRY(hipMalloc(&m->rank, mt_bytes<int>(n_fe)));
-        HIP_TRY(hipMalloc(&m->vaux, mt_bytes<int>(2L * V)));
-        HIP_TRY(hipMalloc(&m->patch_face, mt_bytes<int32_t>(F)));
-        HIP_TRY(hipMalloc(&m->orientable, mt_bytes<unsigned char>(F)));
-        HIP_TRY(hipMalloc(&m->volume, mt_bytes<u64>(F)));
-        HIP_TRY(hipMalloc(&m->open_patch, mt_bytes<int>(F)));
-        HIP_TRY(hipStreamSynchronize(st));                    // the temporaries below are freed next
+        *out = owner.release();
         return SURFD_OK;
-    };
-    const int rc = run();
-    (void)hipFree(keys); (void)hipFree(skeys); (void)hipFree(hidx); (void)hipFree(shidx); (void)hipFree(head); (void)hipFree(excl);
-    (void)hipFree(used); (void)hipFree(cnt); (void)hipFree(sort_tmp);
-    if (rc != SURFD_OK) { mt_free(m); return rc; }
-    *out = m;
+    }
+    DeviceScratch scratch;
+    CubWorkspace cub{&scratch};
+    u64 *keys, *skeys;
+    int *hidx, *shidx, *head, *excl, *used, *cnt;
+    SURFD_TRY(scratch.get(&keys, n3)); SURFD_TRY(scratch.get(&skeys, n3)); SURFD_TRY(scratch.get(&hidx, n3)); SURFD_TRY(scratch.get(&shidx, n3));
+    SURFD_TRY(scratch.get(&head, n3)); SURFD_TRY(scratch.get(&excl, n3)); SURFD_TRY(scratch.get(&used, V)); SURFD_TRY(scratch.get(&cnt, MT_CNT_WORDS));
+    HIP_TRY(hipMemcpyAsync(m->tri, triangles, (size_t)n3 * sizeof(int32_t), hipMemcpyDefault, st));
+    HIP_TRY(hipMemsetAsync(used, 0, dev_bytes<int>(V), st));
+    const int cnt0[MT_CNT_WORDS] = {0, INT_MAX, 0, 0, 0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(cnt, cnt0, sizeof(cnt0), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(m->face_edges, 0xFF, dev_bytes<int32_t>(n3), st));
+    HIP_TRY(hipMemsetAsync(m->face_neighbors, 0xFF, dev_bytes<int32_t>(n3), st));
+    hipLaunchKernelGGL(mt_keys_kernel, dim3(dev_grid(F)), dim3(256), 0, st, (const int32_t *)m->tri, F, V, keys, hidx, m->degenerate, used, cnt);
+    LAUNCH_CHECK();
+    SURFD_TRY(cub.sort_pairs(keys, skeys, hidx, shidx, n3, 64, st));
+    hipLaunchKernelGGL(mt_heads_kernel, dim3(dev_grid(n3)), dim3(256), 0, st, (const u64 *)skeys, n3, head);
+    LAUNCH_CHECK();
+    SURFD_TRY(m->scan.exclusive_sum(head, excl, n3, st));     // sizes the handle's workspace: every later scan is shorter
+    SURFD_TRY(scan_total(head, excl, n3, cnt + MT_CNT_E, st));
+    int hc[MT_CNT_WORDS];
+    HIP_TRY(hipMemcpyAsync(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (hc[MT_CNT_BAD] > 0)
+        SURFD_FAIL(SURFD_ERR_ARG, "surfd_meshtopo_create: %d faces name vertices outside [0, %d), the first is face %d", hc[MT_CNT_BAD], V, hc[MT_CNT_FIRST_BAD]);
+    m->n_degenerate = hc[MT_CNT_DEGENERATE];
+    m->n_referenced = hc[MT_CNT_REFERENCED];
+    m->E = hc[MT_CNT_E];
+    m->H = 3 * (F - m->n_degenerate);
+    const int E = m->E, H = m->H;
+    HIP_TRY(hipMalloc(&m->edges, dev_bytes<int32_t>(2L * E)));
+    HIP_TRY(hipMalloc(&m->valence, dev_bytes<int32_t>(E)));
+    HIP_TRY(hipMalloc(&m->edge_offsets, dev_bytes<int32_t>(E + 1L)));
+    HIP_TRY(hipMalloc(&m->edge_halfedges, dev_bytes<int32_t>(H)));
+    HIP_TRY(hipMemsetAsync(m->edge_offsets, 0, dev_bytes<int32_t>(E + 1L), st));
+    if (H > 0) {
+        hipLaunchKernelGGL(mt_fill_kernel, dim3(dev_grid(H)), dim3(256), 0, st, (const u64 *)skeys, (const int *)shidx, (const int *)head, (const int *)excl,
+                           H, E, m->edges, m->edge_offsets, m->edge_halfedges, m->face_edges);
+        LAUNCH_CHECK();
+        hipLaunchKernelGGL(mt_neighbors_kernel, dim3(dev_grid(H)), dim3(256), 0, st, H, E, (const int32_t *)m->edge_offsets,
+                           (const int32_t *)m->edge_halfedges, (const int32_t *)m->face_edges, m->valence, m->face_neighbors);
+        LAUNCH_CHECK();
+    }
+    const long n_nodes = std::max(std::max(2L * F, (long)V), (long)E), n_pairs = std::max(3L * F, 2L * E), n_fe = std::max(F, E);
+    HIP_TRY(hipMalloc(&m->parent, dev_bytes<int>(n_nodes)));
+    HIP_TRY(hipMalloc(&m->pairs, dev_bytes<int2>(n_pairs)));
+    HIP_TRY(hipMalloc(&m->rootface, dev_bytes<int>(n_fe)));
+    HIP_TRY(hipMalloc(&m->isroot, dev_bytes<int>(n_fe)));
+    HIP_TRY(hipMalloc(&m->rank, dev_bytes<int>(n_fe)));
+    HIP_TRY(hipMalloc(&m->vaux, dev_bytes<int>(2L * V)));
+    HIP_TRY(hipMalloc(&m->patch_face, dev_bytes<int32_t>(F)));
+    HIP_TRY(hipMalloc(&m->orientable, dev_bytes<unsigned char>(F)));
+    HIP_TRY(hipMalloc(&m->volume, dev_bytes<u64>(F)));
+    HIP_TRY(hipMalloc(&m->open_patch, dev_bytes<int>(F)));
+    HIP_TRY(hipStreamSynchronize(st));                        // the scratch is freed next
+    *out = owner.release();
     return SURFD_OK;
 }
 
@@ -606,16 +577,12 @@ extern "C" int surfd_meshtopo_read(const surfd_meshtopo *m, int32_t *edges, int3
 
 // rootface[0 .. n) -> labels and the number of components (read back: the one sync of the call)
 static int mt_number(surfd_meshtopo *m, int n, int32_t *labels, int64_t *count, hipStream_t st) {
-    hipLaunchKernelGGL(mt_isroot_kernel, dim3(mt_grid(n)), dim3(256), 0, st, (const int *)m->rootface, n, m->isroot);
+    hipLaunchKernelGGL(mt_isroot_kernel, dim3(dev_grid(n)), dim3(256), 0, st, (const int *)m->rootface, n, m->isroot);
     LAUNCH_CHECK();
-    size_t bytes = m->scan_bytes;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, m->isroot, m->rank, n, st));
-    if (bytes > m->scan_bytes) SURFD_FAIL(SURFD_ERR_STATE, "mesh topology: the scan workspace is too small (%zu > %zu bytes)", bytes, m->scan_bytes);
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(m->scan_tmp, bytes, m->isroot, m->rank, n, st));
-    hipLaunchKernelGGL(mt_labels_kernel, dim3(mt_grid(n)), dim3(256), 0, st, (const int *)m->rootface, (const int *)m->rank, n, labels);
+    SURFD_TRY(m->scan.exclusive_sum(m->isroot, m->rank, n, st));      // allocates nothing: SURFD_ERR_STATE if create's size did not do
+    hipLaunchKernelGGL(mt_labels_kernel, dim3(dev_grid(n)), dim3(256), 0, st, (const int *)m->rootface, (const int *)m->rank, n, labels);
     LAUNCH_CHECK();
-    hipLaunchKernelGGL(mt_total_kernel, dim3(1), dim3(64), 0, st, (const int *)m->isroot, (const int *)m->rank, n, m->scalars);
-    LAUNCH_CHECK();
+    SURFD_TRY(scan_total(m->isroot, m->rank, n, m->scalars, st));
     int c = 0;
     HIP_TRY(hipMemcpyAsync(&c, m->scalars, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -634,24 +601,24 @@ extern "C" int surfd_meshtopo_components(surfd_meshtopo *m, int connectivity, in
     hipStream_t st = as_stream(s);
     int rc;
     if (connectivity == SURFD_MESHTOPO_VERTEX) {
-        hipLaunchKernelGGL(mt_pairs_vertex_kernel, dim3(mt_grid(F)), dim3(256), 0, st, (const int32_t *)m->tri, (const unsigned char *)m->degenerate, F, m->pairs);
+        hipLaunchKernelGGL(mt_pairs_vertex_kernel, dim3(dev_grid(F)), dim3(256), 0, st, (const int32_t *)m->tri, (const unsigned char *)m->degenerate, F, m->pairs);
         LAUNCH_CHECK();
         if ((rc = cc_run(m->parent, V, m->pairs, 2 * F, st)) != SURFD_OK) return rc;
-        HIP_TRY(hipMemsetAsync(m->vaux, 0x7F, mt_bytes<int>(V), st));         // 0x7F7F7F7F: above every face index
-        hipLaunchKernelGGL(mt_minface_kernel, dim3(mt_grid(F)), dim3(256), 0, st, (const int32_t *)m->tri, (const unsigned char *)m->degenerate, F,
+        HIP_TRY(hipMemsetAsync(m->vaux, 0x7F, dev_bytes<int>(V), st));         // 0x7F7F7F7F: above every face index
+        hipLaunchKernelGGL(mt_minface_kernel, dim3(dev_grid(F)), dim3(256), 0, st, (const int32_t *)m->tri, (const unsigned char *)m->degenerate, F,
                            (const int *)m->parent, m->vaux);
         LAUNCH_CHECK();
-        hipLaunchKernelGGL(mt_rootface_vertex_kernel, dim3(mt_grid(F)), dim3(256), 0, st, (const int32_t *)m->tri, (const unsigned char *)m->degenerate, F,
+        hipLaunchKernelGGL(mt_rootface_vertex_kernel, dim3(dev_grid(F)), dim3(256), 0, st, (const int32_t *)m->tri, (const unsigned char *)m->degenerate, F,
                            (const int *)m->parent, (const int *)m->vaux, m->rootface);
         LAUNCH_CHECK();
     } else {
         if (H > 0) {
-            hipLaunchKernelGGL(mt_pairs_faces_kernel, dim3(mt_grid(H)), dim3(256), 0, st, H, (const int32_t *)m->edge_offsets, (const int32_t *)m->edge_halfedges,
+            hipLaunchKernelGGL(mt_pairs_faces_kernel, dim3(dev_grid(H)), dim3(256), 0, st, H, (const int32_t *)m->edge_offsets, (const int32_t *)m->edge_halfedges,
                                (const int32_t *)m->face_edges, connectivity == SURFD_MESHTOPO_MANIFOLD ? 1 : 0, m->pairs);
             LAUNCH_CHECK();
         }
         if ((rc = cc_run(m->parent, F, m->pairs, H, st)) != SURFD_OK) return rc;
-        hipLaunchKernelGGL(mt_rootface_faces_kernel, dim3(mt_grid(F)), dim3(256), 0, st, (const unsigned char *)m->degenerate, F, (const int *)m->parent, m->rootface);
+        hipLaunchKernelGGL(mt_rootface_faces_kernel, dim3(dev_grid(F)), dim3(256), 0, st, (const unsigned char *)m->degenerate, F, (const int *)m->parent, m->rootface);
         LAUNCH_CHECK();
     }
     return mt_number(m, F, labels, count, st);
@@ -665,16 +632,16 @@ extern "C" int surfd_meshtopo_border_loops(surfd_meshtopo *m, int32_t *labels, u
     if (!labels) SURFD_FAIL(SURFD_ERR_ARG, "surfd_meshtopo_border_loops: null argument");
     hipStream_t st = as_stream(s);
     int *vfirst = m->vaux, *vdeg = m->vaux + V;
-    HIP_TRY(hipMemsetAsync(vfirst, 0x7F, mt_bytes<int>(V), st));
-    HIP_TRY(hipMemsetAsync(vdeg, 0, mt_bytes<int>(V), st));
-    hipLaunchKernelGGL(mt_border_vertices_kernel, dim3(mt_grid(E)), dim3(256), 0, st, E, (const int32_t *)m->edges, (const int32_t *)m->valence, vfirst, vdeg);
+    HIP_TRY(hipMemsetAsync(vfirst, 0x7F, dev_bytes<int>(V), st));
+    HIP_TRY(hipMemsetAsync(vdeg, 0, dev_bytes<int>(V), st));
+    hipLaunchKernelGGL(mt_border_vertices_kernel, dim3(dev_grid(E)), dim3(256), 0, st, E, (const int32_t *)m->edges, (const int32_t *)m->valence, vfirst, vdeg);
     LAUNCH_CHECK();
-    hipLaunchKernelGGL(mt_pairs_border_kernel, dim3(mt_grid(E)), dim3(256), 0, st, E, (const int32_t *)m->edges, (const int32_t *)m->valence, (const int *)vfirst,
+    hipLaunchKernelGGL(mt_pairs_border_kernel, dim3(dev_grid(E)), dim3(256), 0, st, E, (const int32_t *)m->edges, (const int32_t *)m->valence, (const int *)vfirst,
                        (const int *)vdeg, m->pairs, irregular);
     LAUNCH_CHECK();
     int rc;
     if ((rc = cc_run(m->parent, E, m->pairs, 2 * E, st)) != SURFD_OK) return rc;
-    hipLaunchKernelGGL(mt_rootface_border_kernel, dim3(mt_grid(E)), dim3(256), 0, st, (const int32_t *)m->valence, E, (const int *)m->parent, m->rootface);
+    hipLaunchKernelGGL(mt_rootface_border_kernel, dim3(dev_grid(E)), dim3(256), 0, st, (const int32_t *)m->valence, E, (const int *)m->parent, m->rootface);
     LAUNCH_CHECK();
     return mt_number(m, E, labels, count, st);
 }
@@ -687,27 +654,27 @@ extern "C" int surfd_meshtopo_orient(surfd_meshtopo *m, const float *vertices, u
     if (!flip) SURFD_FAIL(SURFD_ERR_ARG, "surfd_meshtopo_orient: null argument");
     hipStream_t st = as_stream(s);
     if (E > 0) {
-        hipLaunchKernelGGL(mt_pairs_orient_kernel, dim3(mt_grid(E)), dim3(256), 0, st, E, (const int32_t *)m->edges, (const int32_t *)m->edge_offsets,
+        hipLaunchKernelGGL(mt_pairs_orient_kernel, dim3(dev_grid(E)), dim3(256), 0, st, E, (const int32_t *)m->edges, (const int32_t *)m->edge_offsets,
                            (const int32_t *)m->edge_halfedges, (const int32_t *)m->tri, m->pairs);
         LAUNCH_CHECK();
     }
     int rc;
     if ((rc = cc_run(m->parent, 2 * F, m->pairs, 2 * E, st)) != SURFD_OK) return rc;
-    hipLaunchKernelGGL(mt_flip_kernel, dim3(mt_grid(F)), dim3(256), 0, st, (const unsigned char *)m->degenerate, F, (const int *)m->parent, flip, m->orientable,
+    hipLaunchKernelGGL(mt_flip_kernel, dim3(dev_grid(F)), dim3(256), 0, st, (const unsigned char *)m->degenerate, F, (const int *)m->parent, flip, m->orientable,
                        m->patch_face);
     LAUNCH_CHECK();
     if (vertices && m->V > 0) {
         unsigned *maxbits = (unsigned *)(m->scalars + 1);
         HIP_TRY(hipMemsetAsync(maxbits, 0, sizeof(unsigned), st));
-        HIP_TRY(hipMemsetAsync(m->volume, 0, mt_bytes<u64>(F), st));
-        HIP_TRY(hipMemsetAsync(m->open_patch, 0, mt_bytes<int>(F), st));
-        hipLaunchKernelGGL(mt_maxabs_kernel, dim3(mt_grid(3L * m->V)), dim3(256), 0, st, vertices, 3L * m->V, maxbits);
+        HIP_TRY(hipMemsetAsync(m->volume, 0, dev_bytes<u64>(F), st));
+        HIP_TRY(hipMemsetAsync(m->open_patch, 0, dev_bytes<int>(F), st));
+        hipLaunchKernelGGL(mt_maxabs_kernel, dim3(dev_grid(3L * m->V)), dim3(256), 0, st, vertices, 3L * m->V, maxbits);
         LAUNCH_CHECK();
-        hipLaunchKernelGGL(mt_volume_kernel, dim3(mt_grid(F)), dim3(256), 0, st, (const int32_t *)m->tri, vertices, F, (const int32_t *)m->face_edges,
+        hipLaunchKernelGGL(mt_volume_kernel, dim3(dev_grid(F)), dim3(256), 0, st, (const int32_t *)m->tri, vertices, F, (const int32_t *)m->face_edges,
                            (const int32_t *)m->valence, (const unsigned char *)flip, (const int32_t *)m->patch_face, (const unsigned *)maxbits, m->volume,
                            m->open_patch);
         LAUNCH_CHECK();
-        hipLaunchKernelGGL(mt_turn_kernel, dim3(mt_grid(F)), dim3(256), 0, st, F, (const int32_t *)m->patch_face, (const unsigned char *)m->orientable,
+        hipLaunchKernelGGL(mt_turn_kernel, dim3(dev_grid(F)), dim3(256), 0, st, F, (const int32_t *)m->patch_face, (const unsigned char *)m->orientable,
                            (const u64 *)m->volume, (const int *)m->open_patch, flip);
         LAUNCH_CHECK();
     }
@@ -724,49 +691,35 @@ extern "C" int surfd_meshtopo_weld(const float *vertices, int V, int32_t *vertex
     if (!vertices || !vertex_map || !survivor) SURFD_FAIL(SURFD_ERR_ARG, "surfd_meshtopo_weld: null argument");
     if ((long)V * 3 > (long)INT_MAX) SURFD_FAIL(SURFD_ERR_ARG, "surfd_meshtopo_weld: 3 V must stay below 2^31, V = %d", V);
     hipStream_t st = as_stream(s);
-    unsigned *kz = nullptr, *kz2 = nullptr;
-    u64 *kxy = nullptr, *kxy2 = nullptr;
-    int *idx0 = nullptr, *idx1 = nullptr, *idx2 = nullptr, *headpos = nullptr, *hp = nullptr, *rep = nullptr, *survives = nullptr, *newidx = nullptr, *total = nullptr;
-    void *tmp = nullptr;
-    auto run = [&]() -> int {
-        HIP_TRY(hipMalloc(&kz, mt_bytes<unsigned>(V))); HIP_TRY(hipMalloc(&kz2, mt_bytes<unsigned>(V)));
-        HIP_TRY(hipMalloc(&kxy, mt_bytes<u64>(V))); HIP_TRY(hipMalloc(&kxy2, mt_bytes<u64>(V)));
-        HIP_TRY(hipMalloc(&idx0, mt_bytes<int>(V))); HIP_TRY(hipMalloc(&idx1, mt_bytes<int>(V))); HIP_TRY(hipMalloc(&idx2, mt_bytes<int>(V)));
-        HIP_TRY(hipMalloc(&headpos, mt_bytes<int>(V))); HIP_TRY(hipMalloc(&hp, mt_bytes<int>(V))); HIP_TRY(hipMalloc(&rep, mt_bytes<int>(V)));
-        HIP_TRY(hipMalloc(&survives, mt_bytes<int>(V))); HIP_TRY(hipMalloc(&newidx, mt_bytes<int>(V))); HIP_TRY(hipMalloc(&total, sizeof(int)));
-        size_t b0 = 0, b1 = 0, b2 = 0, b3 = 0;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, b0, kz, kz2, idx0, idx1, V, 0, 32, st));
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, b1, kxy, kxy2, idx1, idx2, V, 0, 64, st));
-        HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, b2, headpos, hp, hipcub::Max(), V, st));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, b3, survives, newidx, V, st));
-        size_t bytes = std::max(std::max(b0, b1), std::max(b2, b3));
-        if (bytes == 0) bytes = 16;
-        HIP_TRY(hipMalloc(&tmp, bytes));
-        // least significant key first; both sorts are stable, so equal vertices end up adjacent and ascending in index
-        hipLaunchKernelGGL(mt_weld_key_z_kernel, dim3(mt_grid(V)), dim3(256), 0, st, vertices, V, kz, idx0);
-        LAUNCH_CHECK();
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, kz, kz2, idx0, idx1, V, 0, 32, st));
-        hipLaunchKernelGGL(mt_weld_key_xy_kernel, dim3(mt_grid(V)), dim3(256), 0, st, vertices, V, (const int *)idx1, kxy);
-        LAUNCH_CHECK();
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, kxy, kxy2, idx1, idx2, V, 0, 64, st));
-        hipLaunchKernelGGL(mt_weld_heads_kernel, dim3(mt_grid(V)), dim3(256), 0, st, vertices, V, (const int *)idx2, headpos);
-        LAUNCH_CHECK();
-        HIP_TRY(hipcub::DeviceScan::InclusiveScan(tmp, bytes, headpos, hp, hipcub::Max(), V, st));
-        hipLaunchKernelGGL(mt_weld_rep_kernel, dim3(mt_grid(V)), dim3(256), 0, st, V, (const int *)idx2, (const int *)hp, rep, survives);
-        LAUNCH_CHECK();
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, bytes, survives, newidx, V, st));
-        hipLaunchKernelGGL(mt_weld_map_kernel, dim3(mt_grid(V)), dim3(256), 0, st, V, (const int *)rep, (const int *)survives, (const int *)newidx, vertex_map, survivor);
-        LAUNCH_CHECK();
-        hipLaunchKernelGGL(mt_total_kernel, dim3(1), dim3(64), 0, st, (const int *)survives, (const int *)newidx, V, total);
-        LAUNCH_CHECK();
-        int c = 0;
-        HIP_TRY(hipMemcpyAsync(&c, total, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        *count = c;
-        return SURFD_OK;
-    };
-    const int rc = run();
-    (void)hipFree(kz); (void)hipFree(kz2); (void)hipFree(kxy); (void)hipFree(kxy2); (void)hipFree(idx0); (void)hipFree(idx1); (void)hipFree(idx2);
-    (void)hipFree(headpos); (void)hipFree(hp); (void)hipFree(rep); (void)hipFree(survives); (void)hipFree(newidx); (void)hipFree(total); (void)hipFree(tmp);
-    return rc;
+    DeviceScratch scratch;
+    CubWorkspace cub{&scratch};
+    unsigned *kz, *kz2;
+    u64 *kxy, *kxy2;
+    int *idx0, *idx1, *idx2, *headpos, *hp, *rep, *survives, *newidx, *total;
+    SURFD_TRY(scratch.get(&kz, V)); SURFD_TRY(scratch.get(&kz2, V)); SURFD_TRY(scratch.get(&kxy, V)); SURFD_TRY(scratch.get(&kxy2, V));
+    SURFD_TRY(scratch.get(&idx0, V)); SURFD_TRY(scratch.get(&idx1, V)); SURFD_TRY(scratch.get(&idx2, V)); SURFD_TRY(scratch.get(&headpos, V));
+    SURFD_TRY(scratch.get(&hp, V)); SURFD_TRY(scratch.get(&rep, V)); SURFD_TRY(scratch.get(&survives, V)); SURFD_TRY(scratch.get(&newidx, V));
+    SURFD_TRY(scratch.get(&total, 1));
+    SURFD_TRY(cub.sort_pairs(kxy, kxy2, idx1, idx2, V, 64, st, true));      // the second sort is the larger: one workspace allocation
+    // least significant key first; both sorts are stable, so equal vertices end up adjacent and ascending in index
+    hipLaunchKernelGGL(mt_weld_key_z_kernel, dim3(dev_grid(V)), dim3(256), 0, st, vertices, V, kz, idx0);
+    LAUNCH_CHECK();
+    SURFD_TRY(cub.sort_pairs(kz, kz2, idx0, idx1, V, 32, st));
+    hipLaunchKernelGGL(mt_weld_key_xy_kernel, dim3(dev_grid(V)), dim3(256), 0, st, vertices, V, (const int *)idx1, kxy);
+    LAUNCH_CHECK();
+    SURFD_TRY(cub.sort_pairs(kxy, kxy2, idx1, idx2, V, 64, st));
+    hipLaunchKernelGGL(mt_weld_heads_kernel, dim3(dev_grid(V)), dim3(256), 0, st, vertices, V, (const int *)idx2, headpos);
+    LAUNCH_CHECK();
+    SURFD_TRY(cub.inclusive_max(headpos, hp, V, st));
+    hipLaunchKernelGGL(mt_weld_rep_kernel, dim3(dev_grid(V)), dim3(256), 0, st, V, (const int *)idx2, (const int *)hp, rep, survives);
+    LAUNCH_CHECK();
+    SURFD_TRY(cub.exclusive_sum(survives, newidx, V, st));
+    hipLaunchKernelGGL(mt_weld_map_kernel, dim3(dev_grid(V)), dim3(256), 0, st, V, (const int *)rep, (const int *)survives, (const int *)newidx, vertex_map, survivor);
+    LAUNCH_CHECK();
+    SURFD_TRY(scan_total(survives, newidx, V, total, st));
+    int c = 0;
+    HIP_TRY(hipMemcpyAsync(&c, total, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));                        // the scratch is freed next
+    *count = c;
+    return SURFD_OK;
 }

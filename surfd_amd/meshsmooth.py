@@ -20,76 +20,32 @@ pair occurs exactly once among all 3 F half-edges; faces with repeated indices t
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional, Tuple, Union
 
 import torch
 from torch import Tensor
 
 from . import _native as N
+from .meshconn import _MeshConnectivity
 
 DTYPE = {torch.float32: 0, torch.float64: 1}                 # SURFD_MESHSMOOTH_F32 / _F64
 SET = {"all": 0, "border": 1}                                # SURFD_MESHSMOOTH_ALL / _BORDER
 WEIGHT = {"angle": 0, "area": 1}                             # SURFD_MESHSMOOTH_ANGLE / _AREA
-_NO_CPU = "the mesh smoothing runs only on the GPU through libsurfd_hip.so (no CPU fallback): move the mesh with .cuda()"
 
 
-def _check_triangles(triangles: Tensor, need_cuda: bool = True) -> None:
-    if not isinstance(triangles, Tensor) or triangles.dim() != 2 or triangles.shape[1] != 3:
-        raise ValueError(f"triangles must be a tensor [F, 3], got {tuple(getattr(triangles, 'shape', ()))}")
-    if triangles.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"triangles must be int32 or int64, got {triangles.dtype}")
-    if need_cuda and not triangles.is_cuda:
-        raise RuntimeError(_NO_CPU)
-
-
-def _check_vertices(vertices: Tensor, need_cuda: bool = True) -> None:
-    if not isinstance(vertices, Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise ValueError(f"vertices must be a tensor [V, 3], got {tuple(getattr(vertices, 'shape', ()))}")
-    if vertices.dtype not in DTYPE:
-        raise TypeError(f"vertices must be float32 or float64, got {vertices.dtype}")
-    if need_cuda and not vertices.is_cuda:
-        raise RuntimeError(_NO_CPU)
-
-
-class MeshSmoother:
+class MeshSmoother(_MeshConnectivity):
     """The neighbourhoods of one mesh connectivity (per vertex: the half-edges that leave it and that arrive at it, its border
     neighbours, its corners), built once by stable radix sorts and kept.  Host syncs: the constructor only (the bad-index flag
     and the two border counts are read back; ``num_vertices=None`` also reads the largest index); every method only enqueues.
     One stream at a time per object: the library keeps its position buffers in the handle."""
 
-    def __init__(self, triangles: Tensor, num_vertices: Optional[int] = None):
-        _check_triangles(triangles, need_cuda=False)           # shapes and dtypes first, the CPU-tensor refusal last
-        _check_triangles(triangles)
-        self._handle = None
-        self.device = triangles.device
-        F = int(triangles.shape[0])
-        if num_vertices is None:
-            num_vertices = int(triangles.max()) + 1 if F else 0
-        if num_vertices < 0:
-            raise ValueError(f"num_vertices must not be negative, got {num_vertices}")
-        if 3 * F >= 2 ** 31 or int(num_vertices) >= 2 ** 31:
-            raise ValueError(f"3 F and V must stay below 2^31, got F = {F}, V = {num_vertices}")
-        if F and triangles.dtype == torch.int64 and (int(triangles.min()) < -2 ** 31 or int(triangles.max()) >= 2 ** 31):
-            raise ValueError(f"triangles name vertices outside [0, {num_vertices})")
-        self.num_vertices = int(num_vertices)
-        self.num_faces = F
-        ts = triangles.to(torch.int32).contiguous()
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            N.check(N.lib().surfd_meshsmooth_create(N.ptr(ts), F, self.num_vertices, N.stream(), C.byref(h)))
-        self._handle = h
-        c = [C.c_int64() for _ in range(4)]
-        N.check(N.lib().surfd_meshsmooth_counts(h, *[C.byref(x) for x in c]))
-        assert c[0].value == F and c[1].value == self.num_vertices
-        self.num_border_halfedges, self.num_border_vertices = int(c[2].value), int(c[3].value)
+    _abi = "surfd_meshsmooth"
+    _what = "the mesh smoothing"
+    _vertex_dtypes = tuple(DTYPE)
 
-    def _positions(self, vertices: Tensor) -> Tensor:
-        _check_vertices(vertices, need_cuda=False)
-        _check_vertices(vertices)
-        if vertices.shape[0] != self.num_vertices or vertices.device != self.device:
-            raise ValueError(f"vertices must be [{self.num_vertices}, 3] on {self.device}, got {tuple(vertices.shape)} on {vertices.device}")
-        return vertices.detach().contiguous()
+    def __init__(self, triangles: Tensor, num_vertices: Optional[int] = None):
+        faces, vertices, self.num_border_halfedges, self.num_border_vertices = self._open(triangles, num_vertices)
+        assert faces == self.num_faces and vertices == self.num_vertices
 
     def laplacian(self, vertices: Tensor, steps: int = 3, cotangent: bool = True, boundary: bool = True) -> Tensor:
         """[V, 3] float64: ``steps`` Jacobi sweeps of meshproc.laplacian_smooth (MeshLab's apply_coord_laplacian_smoothing with its
@@ -149,20 +105,10 @@ class MeshSmoother:
             N.check(N.lib().surfd_meshsmooth_vertex_normals(self._handle, N.ptr(v), DTYPE[v.dtype], WEIGHT[weight], N.ptr(unit), N.ptr(raw), N.stream()))
         return (unit, raw) if return_raw else unit
 
-    def __del__(self):
-        try:
-            if self._handle is not None:
-                N.lib().surfd_meshsmooth_destroy(self._handle)
-        except Exception:                                       # interpreter shutdown
-            pass
-
 
 # ---- one-shot forms -----------------------------------------------------------------------------------------------------------
 def _smoother(vertices: Tensor, faces: Tensor) -> MeshSmoother:
-    _check_vertices(vertices, need_cuda=False)
-    _check_triangles(faces, need_cuda=False)
-    _check_vertices(vertices)
-    _check_triangles(faces)
+    MeshSmoother._check(faces, vertices)
     return MeshSmoother(faces, int(vertices.shape[0]))
 
 

@@ -28,60 +28,24 @@ import torch
 from torch import Tensor
 
 from . import _native as N
+from .meshconn import _MeshConnectivity
 
 CONNECTIVITY = {"vertex": 0, "edge": 1, "manifold": 2}      # SURFD_MESHTOPO_VERTEX / _EDGE / _MANIFOLD
 
 
-def _check_triangles(triangles: Tensor, need_cuda: bool = True) -> None:
-    if triangles.dim() != 2 or triangles.shape[1] != 3:
-        raise ValueError(f"triangles must be [F, 3], got {tuple(triangles.shape)}")
-    if triangles.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"triangles must be int32 or int64, got {triangles.dtype}")
-    if need_cuda and not triangles.is_cuda:
-        raise RuntimeError("the mesh topology runs only on the GPU through libsurfd_hip.so (no CPU fallback): move the mesh with .cuda()")
-
-
-def _check_vertices(vertices: Tensor, need_cuda: bool = True) -> None:
-    if vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise ValueError(f"vertices must be [V, 3], got {tuple(vertices.shape)}")
-    if vertices.dtype != torch.float32:
-        raise TypeError(f"vertices must be float32, got {vertices.dtype}")
-    if need_cuda and not vertices.is_cuda:
-        raise RuntimeError("the mesh topology runs only on the GPU through libsurfd_hip.so (no CPU fallback): move the mesh with .cuda()")
-
-
-class MeshTopology:
+class MeshTopology(_MeshConnectivity):
     """The edges of one mesh, kept for repeated questions.  Arrays are computed on first use and kept; index arrays come back as
     int64, masks as bool.  Host syncs: the constructor (the number of edges is read back; ``num_vertices=None`` also reads the
     largest index), ``components`` and ``border_loops`` (the number of components); ``orientation`` and the array properties only
     enqueue.  One stream at a time per object: the library keeps its workspaces in the handle."""
 
+    _abi = "surfd_meshtopo"
+    _what = "the mesh topology"
+
     def __init__(self, triangles: Tensor, num_vertices: Optional[int] = None):
-        _check_triangles(triangles, need_cuda=False)           # shapes and dtypes first, the CPU-tensor refusal last
-        _check_triangles(triangles)
-        self._handle = None
-        self.device = triangles.device
-        F = int(triangles.shape[0])
-        if num_vertices is None:
-            num_vertices = int(triangles.max()) + 1 if F else 0
-        if num_vertices < 0:
-            raise ValueError(f"num_vertices must not be negative, got {num_vertices}")
-        if 3 * F >= 2 ** 31 or int(num_vertices) >= 2 ** 31:
-            raise ValueError(f"3 F and V must stay below 2^31, got F = {F}, V = {num_vertices}")
-        if F and triangles.dtype == torch.int64 and (int(triangles.min()) < -2 ** 31 or int(triangles.max()) >= 2 ** 31):
-            raise ValueError(f"triangles name vertices outside [0, {num_vertices})")
-        self.num_vertices = int(num_vertices)
-        self.num_faces = F
+        faces, self.num_edges, self.num_degenerate, self.num_referenced_vertices = self._open(triangles, num_vertices)
+        assert faces == self.num_faces
         self.triangles = triangles.long().contiguous()
-        ts = triangles.to(torch.int32).contiguous()
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            N.check(N.lib().surfd_meshtopo_create(N.ptr(ts), F, self.num_vertices, N.stream(), C.byref(h)))
-        self._handle = h
-        c = [C.c_int64() for _ in range(4)]
-        N.check(N.lib().surfd_meshtopo_counts(h, *[C.byref(x) for x in c]))
-        assert c[0].value == F
-        self.num_edges, self.num_degenerate, self.num_referenced_vertices = int(c[1].value), int(c[2].value), int(c[3].value)
         self._arrays: Optional[Dict[str, Tensor]] = None
         self._components: Dict[str, Tuple[Tensor, Tensor]] = {}
         self._loops: Optional[Tuple[Tensor, Tensor, Tensor]] = None
@@ -167,11 +131,7 @@ class MeshTopology:
             if self._orientation is None:
                 self._orientation = self._orient(None)
             return self._orientation
-        _check_vertices(vertices, need_cuda=False)
-        _check_vertices(vertices)
-        if vertices.shape[0] != self.num_vertices or vertices.device != self.device:
-            raise ValueError(f"vertices must be [{self.num_vertices}, 3] on {self.device}, got {tuple(vertices.shape)} on {vertices.device}")
-        return self._orient(vertices.contiguous())
+        return self._orient(self._positions(vertices))
 
     def oriented_triangles(self, vertices: Optional[Tensor] = None) -> Tensor:
         """the triangles [F, 3] with columns 1 and 2 of the flipped faces swapped (``vertices``: outward, see orientation)"""
@@ -217,23 +177,13 @@ class MeshTopology:
             "patches": patches,
         }
 
-    def __del__(self):
-        try:
-            if self._handle is not None:
-                N.lib().surfd_meshtopo_destroy(self._handle)
-        except Exception:                                       # interpreter shutdown
-            pass
-
 
 # ---- one-shot forms -----------------------------------------------------------------------------------------------------------
 def weld_vertices(vertices: Tensor, triangles: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
     """(vertices_w [W, 3], triangles_w [F, 3], vertex_map [V]): vertices with equal float32 coordinates become one (-0 equals +0, a
     vertex that holds a NaN equals nothing); the survivor is the lowest index of its class, survivors keep their relative order,
     vertex_map[i] is the new index of vertex i's survivor.  There is no tolerance.  Unreferenced vertices stay."""
-    _check_vertices(vertices, need_cuda=False)
-    _check_triangles(triangles, need_cuda=False)
-    _check_vertices(vertices)
-    _check_triangles(triangles)
+    MeshTopology._check(triangles, vertices)
     v = vertices.contiguous()
     V = int(v.shape[0])
     if 3 * V >= 2 ** 31:
@@ -258,10 +208,7 @@ def orient_faces(vertices: Tensor, triangles: Tensor, outward: bool = False, wel
     whose faces share no indices); the returned triangles still name the caller's vertices.  info: ``flip`` [F] bool, ``flipped``
     (how many), ``patches``, ``non_orientable`` (the lowest face of every patch that has no consistent winding; those faces stay
     as they are)."""
-    _check_vertices(vertices, need_cuda=False)
-    _check_triangles(triangles, need_cuda=False)
-    _check_vertices(vertices)
-    _check_triangles(triangles)
+    MeshTopology._check(triangles, vertices)
     if weld:
         vw, tw, _ = weld_vertices(vertices, triangles)
     else:
@@ -306,10 +253,9 @@ def keep_components_with_at_least(vertices: Tensor, faces: Tensor, min_faces: in
     no component here, while meshproc counts them: drop them first)."""
     if vertices.dim() != 2 or vertices.shape[1] != 3:
         raise ValueError(f"vertices must be [V, 3], got {tuple(vertices.shape)}")
-    _check_triangles(faces, need_cuda=False)
-    _check_triangles(faces)
+    MeshTopology._check(faces)
     if not vertices.is_cuda:
-        raise RuntimeError("the mesh topology runs only on the GPU through libsurfd_hip.so (no CPU fallback): move the mesh with .cuda()")
+        raise RuntimeError(MeshTopology._no_cpu())
     f = faces.long()
     if f.shape[0] == 0:
         return vertices, f
