@@ -64,6 +64,9 @@ def parse(argv=None):
     ap.add_argument("--device_post", action="store_true",
                     help="open meshes: border smoothing, Laplacian smoothing and small-component removal on the GPU (surfd_amd.meshsmooth / meshtopo); "
                          "the mesh is copied to the host once, for the OBJ file")
+    ap.add_argument("--device_clean", action="store_true",
+                    help="open meshes: the far-face filter and the cleaning (merge, duplicate and flat faces, small holes) on the GPU too "
+                         "(surfd_amd.meshclean: the same mesh); implies --device_post")
     ap.add_argument("--respacing", default="", help="e.g. ddim50 for a quick run (the reference always runs 1000 steps)")
     ap.add_argument("--seed", type=int, default=10)
     ap.add_argument("--synthetic", action="store_true", help="create synthetic checkpoints under --output_dir and use them")
@@ -193,9 +196,10 @@ def run(a):
             if a.watertight:
                 verts, faces = get_watertight_mesh(field, a.resolution, max_batch=2 ** 16)
                 return meshproc.keep_components_with_at_least(verts, faces, 5000)
-            device_post = bool(getattr(a, "device_post", False))
+            device_clean = bool(getattr(a, "device_clean", False))
+            device_post = bool(getattr(a, "device_post", False)) or device_clean
             v, t = get_mesh_from_udf(field, coords_range=(-1, 1), max_dist=0.1, N=a.resolution, max_batch=2 ** 16, differentiable=False,
-                                     device_post=device_post)
+                                     device_post=device_post, device_clean=device_clean)
             if device_post:                                   # the mesh goes to the host once, for write_obj
                 if postprocess_open_mesh(a.mode):
                     from surfd_amd import meshsmooth, meshtopo

@@ -736,6 +736,48 @@ int surfd_meshsmooth_umbrella(surfd_meshsmooth *m, const void *vertices, int dty
 int surfd_meshsmooth_vertex_normals(surfd_meshsmooth *m, const void *vertices, int dtype, int weight, double *unit, double *raw, surfd_stream s);
 
 /* ------------------------------------------------------------------------------------ */
+/* Mesh cleaning: merge coincident vertices, drop duplicate and flat faces, close holes   */
+/* of 3 and 4 edges.  Stands for the trimesh calls of meshudf.py's cleaning loop          */
+/* (process, remove_duplicate_faces, remove_degenerate_faces, fill_holes), which the      */
+/* reference runs on the host; surfd_amd/meshproc.py restates them in numpy and IS the    */
+/* contract: every output equals meshproc's bit for bit and in the same order.  Integer   */
+/* sorts and scans plus fp64 + - * / sqrt and one round-to-nearest-even; no result        */
+/* depends on launch geometry or on the order in which atomics arrive (csrc/meshclean.hip */
+/* states the contract and the passes; tests/meshclean_ref.py restates it sequentially).  */
+/* Stateless calls: temporaries live for the call, nothing is kept.  Vertices fp64 [V,3], */
+/* faces int32 [F,3], on the device; F >= 0, V >= 0, 3 F < 2^31.  An index outside [0, V) */
+/* is SURFD_ERR_ARG: the kernels compare every caller index before they index by it, and  */
+/* the flag is read back at the end of the call; never a fault.  EVERY CALL HOST-SYNCS    */
+/* ONCE, at its end (its counts and flags are read back on the caller's stream).          */
+/* ------------------------------------------------------------------------------------ */
+/* meshudf.py's Trimesh(..., process=True, validate=False) as meshproc.cull_and_merge restates it:
+ * faces that name a non-finite vertex go; the vertices the other faces name take the key (rint(x scale), rint(y scale),
+ * rint(z scale)) as three int64 (ties to even; -0.0 and 0.0 share a key; scale = 1 / tolerance, worked out by the caller) and
+ * vertices with equal keys become one: the lowest index of a class stays with its own bits, survivors keep their order, faces
+ * keep theirs and are re-indexed.  out_vertices[V,3] and out_faces[F,3] must hold the whole input; counts[5] (host): vertices
+ * and faces written, non-finite vertices, finite vertices no remaining face names, vertices merged into a lower one.  F = 0 or
+ * V = 0 write nothing.  A finite coordinate with |x scale| >= 2^62 is SURFD_ERR_ARG (beyond the keys; never wrapped).  host-sync. */
+int surfd_meshclean_cull_and_merge(const double *vertices, int V, const int32_t *faces, int F, double scale, double *out_vertices,
+                                   int32_t *out_faces, int64_t *counts, surfd_stream s);
+/* meshudf.py's remove_duplicate_faces as meshproc.drop_duplicate_faces restates it:
+ * one face per set of three indices (winding and rotation ignored): the lowest face of each class with its own winding, WRITTEN
+ * IN ASCENDING ORDER of (largest, middle, smallest index) whether or not a face goes.  out_faces[F,3]; count (host) = the faces
+ * written.  Two stable radix sorts (31 and 63 bits); a negative index is SURFD_ERR_ARG.  host-sync. */
+int surfd_meshclean_drop_duplicate_faces(const int32_t *faces, int F, int32_t *out_faces, int64_t *count, surfd_stream s);
+/* meshudf.py's remove_degenerate_faces as meshproc.drop_degenerate_faces restates it:
+ * keeps, in their order, the faces whose two heights 2 area / |edge| over the edges that leave corner 0 both exceed `height` (a
+ * height over an edge no longer than 1e-8 counts as 0; a NaN fails); fp64 in the operation order csrc/meshclean.hip states.
+ * out_faces[F,3]; count (host) = the faces written.  host-sync. */
+int surfd_meshclean_drop_degenerate_faces(const double *vertices, int V, const int32_t *faces, int F, double height, int32_t *out_faces,
+                                          int64_t *count, surfd_stream s);
+/* meshudf.py's fill_holes as meshproc.fill_small_holes restates it:
+ * a border half-edge is one whose unordered vertex pair occurs once among all 3 F half-edges; a loop of exactly 3 or 4 of them
+ * through vertices that one border half-edge leaves is closed against its direction (4 edges: two triangles).  Only the caps are
+ * written, caps[cap_rows,3] with cap_rows >= min(V, 3 F / 2), in ascending order of their smallest vertex: the caller appends
+ * them to its faces.  counts[3] (host): caps written, loops of 3 edges, loops of 4.  F < 3 writes nothing.  host-sync. */
+int surfd_meshclean_fill_small_holes(const int32_t *faces, int F, int V, int32_t *caps, int64_t cap_rows, int64_t *counts, surfd_stream s);
+
+/* ------------------------------------------------------------------------------------ */
 /* Point-cloud metrics: nearest neighbours between clouds and the matrix of directed      */
 /* Chamfer means between two sets of clouds.  No reference counterpart (the reference     */
 /* ships no evaluation code): stands for pytorch3d's knn_points(p1, p2, K=1) /            */

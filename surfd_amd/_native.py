@@ -173,6 +173,10 @@ _SIGS = {
     "surfd_meshsmooth_laplacian": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "surfd_meshsmooth_umbrella": (C.c_int, [_P, _P, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _P, _P]),
     "surfd_meshsmooth_vertex_normals": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "surfd_meshclean_cull_and_merge": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_double, _P, _P, c_i64p, _P]),
+    "surfd_meshclean_drop_duplicate_faces": (C.c_int, [_P, C.c_int, _P, c_i64p, _P]),
+    "surfd_meshclean_drop_degenerate_faces": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_double, _P, c_i64p, _P]),
+    "surfd_meshclean_fill_small_holes": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, c_i64p, _P]),
     "surfd_cloud_nn": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "surfd_cloud_nn_matrix": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_float, _P, _P, _P]),
     "surfd_cloud_fps_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),

@@ -38,6 +38,7 @@ SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshtopo.hip")          # edges, co
 # cloudnormals.hip: the same pair test in its scan; measured 0.5-2.7 % slower with the vectoriser on
 SOURCES.insert(SOURCES.index("mcubes.cpp"), "mcdevice.hip")          # level-set marching cubes on the device (surfd_amd/mcubes.py: marching_cubes_device)
 SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshsmooth.hip")        # Laplacian / Taubin / border smoothing, vertex normals (surfd_amd/meshsmooth.py)
+SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshclean.hip")         # merge / duplicate / degenerate faces, small holes (surfd_amd/meshclean.py)
 FILE_FLAGS = {"cloudnn.hip": ["-fno-slp-vectorize"], "cloudnormals.hip": ["-fno-slp-vectorize"]}
 
 

@@ -354,7 +354,8 @@ def get_udf_and_grads(udf_func, coords_range: Tuple[float, float], max_dist: flo
 
 def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[float, float], max_dist: float,
                       N: int = 128, smooth_borders: bool = True, differentiable: bool = True,
-                      max_batch: int = 2 ** 12, use_fast_grid_filler: bool = True, device_post: bool = False) -> Tuple[Tensor, Tensor]:
+                      max_batch: int = 2 ** 12, use_fast_grid_filler: bool = True, device_post: bool = False,
+                      device_clean: bool = False) -> Tuple[Tensor, Tensor]:
     """Triangulated mesh of the zero set of a UDF — same signature, defaults and return value as the reference
     (meshudf/meshudf.py:307-514): (vertices [V,3] float32, faces [F,3] int64) on the device.
 
@@ -365,7 +366,10 @@ def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[
     reference's re-attachment of gradients to the vertex positions (``differentiable=True``; the sample scripts pass
     False).  ``device_post=True`` (no reference counterpart): the cleaned mesh is uploaded before the border smoothing instead of
     after it, the 20 sweeps run there (surfd_amd.meshsmooth: the same positions bit for bit) and ``differentiable`` takes its
-    vertex normals from the device too; the cleaning stays on the host."""
+    vertex normals from the device too; the cleaning stays on the host.  ``device_clean=True`` (no reference counterpart; implies
+    the device smoothing): the mesher's output is uploaded once, the far-face filter runs on the device tensors (the same probes
+    and the same rule) and the cleaning runs there too (surfd_amd.meshclean: meshproc's result bit for bit), so the mesh does not
+    come down between the probes and the smoothing; the returned tensors equal the default path's."""
     from . import meshproc as mp
     from .mcubes import udf_mc_lewiner
     if not use_fast_grid_filler:
@@ -381,6 +385,9 @@ def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[
     vertices = vertices + coords_range[0]
     faces = faces.astype(np.int64)
 
+    if device_clean:
+        v64, f64 = _clean_on_device(udf_func, vertices, faces, dev, N, max_batch)
+        return _finish_mesh(udf_func, v64, f64, dev, N, smooth_borders, differentiable, max_batch, True)
     # faces whose corners or edge midpoints sit at large udf values are artefacts: drop them (meshudf.py:354-378)
     edges, edge_face = mp.edges_of_faces(faces)
     pa, pb = vertices[edges[:, 0]], vertices[edges[:, 1]]
@@ -389,10 +396,35 @@ def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[
     keep = np.ones(len(faces), dtype=bool)
     keep[np.unique(np.tile(edge_face, 3)[far])] = False
     vertices, faces = mp.clean_until_stable(vertices, faces[keep])
+    return _finish_mesh(udf_func, vertices, faces, dev, N, smooth_borders, differentiable, max_batch, device_post)
+
+
+def _clean_on_device(udf_func, vertices: np.ndarray, faces: np.ndarray, dev, N: int, max_batch: int) -> Tuple[Tensor, Tensor]:
+    """the far-face filter and the cleaning of get_mesh_from_udf on the device: (vertices float64, faces int64) there.  The probes
+    are the host path's: pa, pb and (pa + pb) / 2 in the mesher's precision, then .float(); a face goes when any probe of any of
+    its three edges lies above 1 / N."""
+    from . import meshclean
+    v = torch.from_numpy(np.ascontiguousarray(vertices)).to(dev)
+    f = torch.from_numpy(np.ascontiguousarray(faces)).to(dev)
+    if len(f):
+        edges = f[:, [0, 1, 1, 2, 2, 0]].reshape(-1, 2)
+        pa, pb = v[edges[:, 0]], v[edges[:, 1]]
+        far = sample_udf(udf_func, torch.cat((pa, pb, (pa + pb) / 2)).float(), max_batch) > 1 / N
+        f = f[~far.view(3, len(f), 3).any(dim=2).any(dim=0)]              # probe i belongs to edge i % 3 F, edge e to face e // 3
+    return meshclean.clean_until_stable(v, f)
+
+
+def _finish_mesh(udf_func, vertices, faces, dev, N: int, smooth_borders: bool, differentiable: bool, max_batch: int, device_post: bool):
+    """border smoothing, the float32 / int64 tensors and, with ``differentiable``, the re-attached gradients.  A cleaned mesh that
+    already lies on the device (tensors) takes the device path."""
+    from . import meshproc as mp
     if device_post:
         from . import meshsmooth
-        final_faces = torch.tensor(faces).long().to(dev)
-        verts64 = torch.tensor(vertices).to(dev)
+        on_device = isinstance(vertices, Tensor)
+        final_faces = faces if on_device else torch.tensor(faces).long().to(dev)
+        verts64 = vertices if on_device else torch.tensor(vertices).to(dev)
+        if on_device:
+            faces = None                                     # the host copy is made only where _reattach_gradients needs it
         smoother = meshsmooth.MeshSmoother(final_faces, len(vertices)) if smooth_borders or differentiable else None
         if smooth_borders:
             verts64 = smoother.smooth_borders(verts64, lam=0.3, iterations=20)
@@ -400,6 +432,8 @@ def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[
         if not differentiable:
             return final_verts, final_faces
         normals = smoother.vertex_normals(verts64).float()
+        if faces is None:
+            faces = final_faces.cpu().numpy()
         return _reattach_gradients(udf_func, verts64.cpu().numpy(), faces, final_verts, final_faces, 1 / N, max_batch, mp, normals=normals)
     if smooth_borders:
         vertices = mp.smooth_borders(vertices, faces, lam=0.3, iterations=20)
