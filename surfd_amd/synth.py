@@ -104,8 +104,8 @@ def dgcnn_param_spec(size_latent: int):
 
 def synth_dgcnn_state_dict(size_latent: int = 64, seed: int = 0) -> Dict[str, torch.Tensor]:
     """Encoder weights in the layout of ckpt["encoder"].  BN weights are drawn around +-1 so that every block has channels of
-    both signs (the monotone max / min reduction of csrc/dgcnn.hip takes both branches), and channel 3 of every block has a
-    weight of exactly zero; running variances are positive and spread over [0.25, 2.25)."""
+    both signs (the monotone max / min reduction of csrc/dgcnn.hip takes both branches), and channel 3 of every block (where
+    it has one: size_latent may be below 4) has a weight of exactly zero; running variances are positive and spread over [0.25, 2.25)."""
     sd: Dict[str, torch.Tensor] = {}
     for key, shape in dgcnn_param_spec(size_latent):
         leaf = key.rsplit(".", 1)[-1]
@@ -114,7 +114,8 @@ def synth_dgcnn_state_dict(size_latent: int = 64, seed: int = 0) -> Dict[str, to
             sd[key] = torch.tensor(100, dtype=torch.long)
         elif leaf == "weight" and key.startswith("bn_"):
             w = (torch.rand(shape, generator=g) * 0.8 + 0.6) * torch.where(torch.rand(shape, generator=g) < 0.3, -1.0, 1.0)
-            w[3] = 0.0
+            if shape[0] > 3:
+                w[3] = 0.0
             sd[key] = w
         elif leaf == "bias":
             sd[key] = torch.randn(shape, generator=g) * 0.1

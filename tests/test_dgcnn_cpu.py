@@ -1,6 +1,8 @@
 """CPU-side checks of the point-cloud encoder (surfd_amd/dgcnn.py, csrc/dgcnn.hip): the C ABI enumerates the reference
 checkpoint layout, the kernels are in the code object without spills or scratch, the module refuses what it does not
-implement, random_point_sampling draws what the reference draws, and the g18 fixture has its documented contents."""
+implement, random_point_sampling draws what the reference draws, and the g18 fixture has its documented contents.  The last
+part proves tests/dgcnn_ref.py (the restatement the GPU tests judge the kernels by) on that fixture, and checks on the CPU
+what its exact network cases rest on."""
 import ctypes as C
 import importlib.util
 import os
@@ -9,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import dgcnn_ref as R
 from surfd_amd import _native as N
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -167,3 +170,96 @@ def test_synth_state_dict_exercises_every_branch():
         w, v = sd[f"bn_{i}.weight"], sd[f"bn_{i}.running_var"]
         assert (w < 0).any() and (w > 0).any() and (w == 0).any()
         assert (v > 0).all() and not torch.all(v == 1)
+    Dgcnn(1).load_state_dict(synth_dgcnn_state_dict(1, seed=1), strict=True)   # the latent size knn_points itself creates
+
+
+# ---- tests/dgcnn_ref.py, the restatement the GPU tests judge the kernels by, proven on the reference-made fixture ----------
+@pytest.fixture(scope="module")
+def restated(golden):
+    """{(cloud, L, 'f32' | 'f64'): (latent [L], x1234 [N, 512])} of clouds a and b with the fixture's own neighbours"""
+    from surfd_amd.synth import synth_dgcnn_state_dict
+    z = golden("g18_dgcnn")
+    out = {}
+    for name in ("a", "b"):
+        x = torch.from_numpy(z[f"{name}__pts"])[None]
+        idx = torch.from_numpy(z[f"{name}__knn_idx"].astype(np.int64))[None]
+        for L in (32, 64):
+            sd = synth_dgcnn_state_dict(L, seed=0)
+            for tag, dt in (("f32", torch.float32), ("f64", torch.float64)):
+                lat, x1234 = R.dgcnn_forward(sd, x, idx, dt)
+                assert lat.dtype == dt and x1234.dtype == dt
+                out[name, L, tag] = (lat[0], x1234[0])
+    return out
+
+
+@pytest.mark.parametrize("L", [32, 64])
+def test_restatement_fp64_reproduces_reference_latents(golden, restated, L):
+    z = golden("g18_dgcnn")
+    for name in ("a", "b"):
+        ref = torch.from_numpy(z[f"{name}__latent_L{L}_f64"])
+        err = float((restated[name, L, "f64"][0] - ref).abs().max())
+        assert err <= 1e-12 * float(ref.abs().max()), (name, err)
+
+
+@pytest.mark.parametrize("L", [32, 64])
+def test_restatement_fp32_reproduces_reference_latents(golden, restated, L):
+    z = golden("g18_dgcnn")
+    for name in ("a", "b"):
+        ref = torch.from_numpy(z[f"{name}__latent_L{L}_f32"])
+        err = float((restated[name, L, "f32"][0] - ref).abs().max())
+        assert err <= 1e-5 * float(ref.abs().max()) + 1e-6, (name, err)
+
+
+def test_restatement_fp32_reproduces_reference_features(golden, restated):
+    z = golden("g18_dgcnn")
+    for name in ("a", "b"):
+        got = restated[name, 32, "f32"][1][torch.from_numpy(z[f"{name}__rows"]).long()]
+        ref = torch.from_numpy(z[f"{name}__x1234"])
+        for blk, (c0, c1) in enumerate(R.X_SLICES, 1):
+            err = float((got[:, c0:c1] - ref[:, c0:c1]).abs().max())
+            assert err <= 1e-5 * float(ref[:, c0:c1].abs().max()) + 1e-6, (name, blk, err)
+
+
+def test_restated_knn_reproduces_fixture_indices(golden):
+    z = golden("g18_dgcnn")
+    for name in ("a", "b"):
+        d, i = R.knn_f32(torch.from_numpy(z[f"{name}__pts"])[None], 20)
+        assert d.dtype == torch.float32 and i.dtype == torch.int64
+        assert np.array_equal(i[0].numpy(), z[f"{name}__knn_idx"].astype(np.int64)), name
+        assert bool((d[..., 1:] >= d[..., :-1]).all()) and bool((d[..., 0] == 0).all())
+
+
+def test_exact_running_var():
+    v = np.float32(R.exact_running_var())
+    assert float(v) == R.exact_running_var()                                # an fp32 value
+    assert np.float32(v + np.float32(1e-5)) == np.float32(1.0)
+    t = torch.full((4,), float(v)) + 1e-5                                   # and so in torch's fp32 arithmetic
+    assert bool((t == 1.0).all()) and bool((1 / torch.sqrt(t) == 1.0).all())
+
+
+@pytest.mark.parametrize("k,N,B,L", R.NETWORK_SHAPES)
+def test_exact_case_preconditions(k, N, B, L):
+    """What the exact network cases of tests/test_gpu_dgcnn.py rest on, checked where no GPU is needed: with these inputs
+    the fp32 evaluation has nothing to round, so the answer cannot depend on the order of a sum."""
+    x, idx, sd, info = R.exact_case(k, N, B, L)
+    assert x.shape == (B, N, 3) and idx.shape == (B, N, k)
+    assert torch.equal(x * 8, (x * 8).round())                              # the 1/8 lattice
+    assert B == 1 or not any(torch.equal(x[0], x[b]) for b in range(1, B))  # the clouds of a batch differ
+    for i in range(1, 6):
+        W = sd[f"conv_{i}.weight"]
+        assert bool(((W == 0) | (W.abs() == 1)).all()) and int((W != 0).sum(1).max()) <= 4 and int((W != 0).sum(1).min()) >= 1
+        s, t = R.fold_bn(sd, i, torch.float32)
+        assert torch.equal(s, sd[f"bn_{i}.weight"])                         # the folded scale is bn.weight, exactly
+        assert bool(((s.abs() == 1) | (s.abs() == 2)).all())
+        if i < 5 or L > 1:                                                  # (one channel cannot have both signs)
+            assert bool((s > 0).any()) and bool((s < 0).any())
+        assert torch.equal(t * 8, (t * 8).round())
+    assert bool((sd["bn_5.weight"][0] < 0))                                 # L = 1 takes the min branch
+    lat64, x64 = R.dgcnn_forward(sd, x, idx, torch.float64, fold_dtype=torch.float32)
+    lat32, x32 = R.dgcnn_forward(sd, x, idx, torch.float32)
+    assert torch.equal(x32.double(), x64) and torch.equal(lat32.double(), lat64)
+    assert info["min_act"] > 0 and float(x64.min()) > 0 and float(lat64.min()) > 0
+    assert torch.equal(x64 * 8, (x64 * 8).round()) and torch.equal(lat64 * 8, (lat64 * 8).round())
+    assert 8 * info["bound"] < 2 ** 24, info                                # no partial sum, in any order, leaves the exact range
+    for c0, c1 in R.X_SLICES:                                               # not a constant network: the features vary
+        assert x64[..., c0:c1].unique().numel() > 8 or N * k <= 8

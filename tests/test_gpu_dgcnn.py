@@ -1,6 +1,10 @@
 """GPU tests of the point-cloud encoder (surfd_amd/dgcnn.py, csrc/dgcnn.hip; run with -m gpu on an MI355X): kNN against
 exact brute force, the EdgeConv features and the latents against the reference's own Dgcnn (tests/golden/g18_dgcnn.npz,
-tools/make_golden.py g18), bitwise determinism / batch independence / permutation invariance, and the reconstruction driver."""
+tools/make_golden.py g18), bitwise determinism / batch independence / permutation invariance, and the reconstruction driver.
+
+The second half pins the kernels at the shapes the fixture does not hold, against tests/dgcnn_ref.py (proven on the fixture
+by tests/test_dgcnn_cpu.py): the kNN bit for bit on continuous clouds, the network by value on inputs without rounding, the
+network against fp64 with general weights, and one handle across calls of different sizes."""
 import os
 import subprocess
 import sys
@@ -9,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import dgcnn_ref as R
 from surfd_amd import synth
 from surfd_amd.dgcnn import Dgcnn, knn_points
 
@@ -62,7 +67,7 @@ def test_knn_exact_on_lattice(B, N):
     assert torch.equal(d.double(), rd)
 
 
-@pytest.mark.parametrize("K", [1, 8, 13, 32])
+@pytest.mark.parametrize("K", [1, 8, 13, 16, 24, 32])
 def test_knn_other_k_exact_on_lattice(K):
     x = _lattice_cloud(2, 3000, seed=K)
     d, i = knn_points(x.cuda(), K)
@@ -200,3 +205,135 @@ def test_reconstruct_driver_latents_only(tmp_path):
     lat_b = m(random_point_sampling(b, 4000)[None])[0]
     assert np.array_equal(z["shape_a"], lat_a.cpu().numpy())
     assert np.array_equal(z["shape_b"], lat_b.cpu().numpy())
+
+
+# ---- every shape the handle accepts, against tests/dgcnn_ref.py ------------------------------------------------------------
+def _bits(t):
+    return t.detach().cpu().contiguous().view(torch.int32)
+
+
+def _splits(B, N, k):
+    """dg_splits of csrc/dgcnn.hip restated: the number of candidate splits per query block"""
+    tiles = -(-N // 256)
+    s = min(max(1, -(-1024 // (B * tiles))), 256 // k, tiles)
+    span = -(-(-(-N // s)) // 256) * 256
+    return -(-N // span)
+
+
+# (B, N, K, S).  S by hand from dg_splits: min(ceil(1024 / (B ceil(N / 256))), 256 / K, ceil(N / 256)) splits of whole
+# 256-point tiles.  N <= 256 is one tile, S = 1.  (1, 257, 17): min(512, 15, 2) = 2, the second split holds one candidate.
+# (3, 513, 24): min(114, 10, 3) = 3.  (2, 1100, 21): min(103, 12, 5) = 5 and (1, 1100, 19): min(205, 13, 5) = 5, spans of
+# 256, the last split holds 76.  (70, 300, 8): min(ceil(1024 / 140) = 8, 32, 2) = 2.  K = 16 and 24 are where dg_kth
+# falls through to its default; 17, 19, 21, 24 run the KT = 24 templates, 16 the KT = 16 one.
+KNN_SHAPES = [(1, 16, 16, 1), (2, 24, 24, 1), (1, 257, 17, 2), (3, 513, 24, 3), (2, 1100, 21, 5), (1, 1100, 19, 5), (70, 300, 8, 2)]
+
+
+@pytest.mark.parametrize("offset", [(0.0, 0.0, 0.0), (37.0, -12.0, 5.0)], ids=["centred", "offset"])
+@pytest.mark.parametrize("B,N,K,S", KNN_SHAPES)
+def test_knn_bit_exact_on_continuous_clouds(B, N, K, S, offset):
+    """distances bit-equal and indices equal to the separately rounded fp32 statement (a contracted or reordered distance sum
+    differs in the last bit of some distance; far from the origin the differences cancel and distances tie)"""
+    assert _splits(B, N, K) == S                                             # a changed split rule is to be noticed here
+    x = R.surface_cloud(B, N, seed=N + K, offset=offset)
+    rd, ri = R.knn_f32(x, K)
+    d, i = knn_points(x.cuda(), K)
+    assert d.shape == (B, N, K) and i.dtype == torch.int64
+    nbad = int((_bits(d) != _bits(rd)).sum())
+    assert nbad == 0, f"{nbad} of {d.numel()} distances differ in their bits"
+    assert torch.equal(i.cpu(), ri), f"{int((i.cpu() != ri).sum())} indices differ"
+
+
+def test_knn_identical_points():
+    x = torch.tensor([0.3, -0.7, 1.1]).expand(2, 64, 3).contiguous().cuda()
+    for K in (1, 16, 17, 20, 24, 32):
+        d, i = knn_points(x, K)
+        assert torch.equal(i.cpu(), torch.arange(K).expand(2, 64, K)), K
+        assert bool((_bits(d) == 0).all()), K                                # +0, not -0
+
+
+def _module(sd, L, k):
+    m = Dgcnn(L, k=k)
+    m.load_state_dict(sd, strict=True)
+    return m.cuda().eval()
+
+
+@pytest.mark.parametrize("k,N,B,L", R.NETWORK_SHAPES)
+def test_network_exact_cases(k, N, B, L):
+    """Inputs without rounding (tests/dgcnn_ref.py exact_case): whatever the order of the sums, every element of x1..x4 and of
+    the latent has to equal the fp64 restatement by value.  N == k, one-row and one-candidate tails, k = 1 and 32, the
+    KT = 16 / 24 lists in the forward pass, more than one column block of conv_5 and L = 1."""
+    x, idx, sd, info = R.exact_case(k, N, B, L)
+    # the preconditions, on the CPU before anything touches the GPU
+    lat64, x64 = R.dgcnn_forward(sd, x, idx, torch.float64, fold_dtype=torch.float32)
+    lat32, x32 = R.dgcnn_forward(sd, x, idx, torch.float32)
+    assert torch.equal(x32.double(), x64) and torch.equal(lat32.double(), lat64)
+    for i in range(1, 6):
+        s, _ = R.fold_bn(sd, i, torch.float32)
+        assert torch.equal(s, sd[f"bn_{i}.weight"])
+        assert (i == 5 and L == 1) or (bool((s > 0).any()) and bool((s < 0).any()))
+    assert info["min_act"] > 0 and float(x64.min()) > 0 and float(lat64.min()) > 0
+    assert 8 * info["bound"] < 2 ** 24
+    # the GPU
+    m = _module(sd, L, k)
+    xg = x.cuda()
+    _, gi = m.knn(xg)
+    assert torch.equal(gi.cpu(), idx)                                        # a lattice: the kNN is exact, ties by index
+    rlat, rx = R.dgcnn_forward(sd, x, gi, torch.float64, fold_dtype=torch.float32)
+    lat, x1234 = m.forward_features(xg)
+    for blk, (c0, c1) in enumerate(R.X_SLICES, 1):
+        got, ref = x1234[..., c0:c1].double().cpu().numpy(), rx[..., c0:c1].numpy()
+        assert np.array_equal(got, ref), f"x{blk}: {int((got != ref).sum())} of {ref.size} elements differ"
+    got, ref = lat.double().cpu().numpy(), rlat.numpy()
+    assert np.array_equal(got, ref), f"latent: {int((got != ref).sum())} of {ref.size} elements differ"
+    assert np.array_equal(m(xg).double().cpu().numpy(), ref)                 # and without the feature copy
+
+
+@pytest.mark.parametrize("seed", [0, 1])
+@pytest.mark.parametrize("k,N,B,L", R.NETWORK_SHAPES)
+def test_network_against_fp64(k, N, B, L, seed):
+    """General weights (both scale signs, a zero scale, the leaky branch) on jittered surface clouds: per block of x1..x4 and
+    for the latent, err(GPU, fp64) <= 2 err(fp32 restatement, fp64) + 1e-5 max|fp64|, the reference evaluated with the GPU's
+    own neighbours."""
+    sd = synth.synth_dgcnn_state_dict(L, seed)
+    m = _module(sd, L, k)
+    x = R.surface_cloud(B, N, seed=31 * N + k + seed)
+    _, gi = m.knn(x.cuda())
+    r64, rx64 = R.dgcnn_forward(sd, x, gi, torch.float64)
+    r32, rx32 = R.dgcnn_forward(sd, x, gi, torch.float32)
+    lat, x1234 = m.forward_features(x.cuda())
+    lat, x1234 = lat.double().cpu(), x1234.double().cpu()
+    parts = [(f"x{b}", x1234[..., c0:c1], rx32[..., c0:c1].double(), rx64[..., c0:c1]) for b, (c0, c1) in enumerate(R.X_SLICES, 1)]
+    parts.append(("latent", lat, r32.double(), r64))
+    fails = []
+    for name, g, f32, f64 in parts:
+        e_gpu, e_ref = float((g - f64).abs().max()), float((f32 - f64).abs().max())
+        bound = 2 * e_ref + 1e-5 * float(f64.abs().max())
+        print(f"k={k} N={N} B={B} L={L} seed={seed} {name}: GPU vs fp64 {e_gpu:.3e}, fp32 restatement vs fp64 {e_ref:.3e}, "
+              f"bound {bound:.3e}, ratio {e_gpu / bound:.3f}")
+        if not e_gpu <= bound:
+            fails.append((name, e_gpu, e_ref, bound))
+    assert not fails, fails
+
+
+def test_one_handle_across_sizes():
+    """the arena grows and is reused, and the partial kNN lists overwrite old features: every call equals a fresh module's"""
+    sd = synth.synth_dgcnn_state_dict(64, seed=0)
+    m = _module(sd, 64, 20)
+    shapes = [(2, 1000), (1, 20), (3, 257), (2, 1000)]
+    other_n = [777, 40, 1500, 300]                                           # kNN calls through the same handle, in between
+    clouds = {s: R.surface_cloud(s[0], s[1], seed=s[0] * s[1]).cuda() for s in shapes}
+    outs = []
+    for (B, N), n2 in zip(shapes, other_n):
+        x = clouds[B, N]
+        lat, x1234 = m.forward_features(x)
+        y = R.surface_cloud(2, n2, seed=n2).cuda()
+        d, i = m.knn(y)
+        lat2 = m(x)
+        fresh = _module(sd, 64, 20)
+        flat, fx = fresh.forward_features(x)
+        assert torch.equal(_bits(lat), _bits(flat)) and torch.equal(_bits(x1234), _bits(fx)), (B, N)
+        assert torch.equal(_bits(lat2), _bits(flat)), (B, N)
+        fd, fi = _module(sd, 64, 20).knn(y)
+        assert torch.equal(_bits(d), _bits(fd)) and torch.equal(i, fi), (B, N, n2)
+        outs.append((lat, x1234))
+    assert torch.equal(_bits(outs[0][0]), _bits(outs[3][0])) and torch.equal(_bits(outs[0][1]), _bits(outs[3][1]))
