@@ -82,7 +82,7 @@ int surfd_unet_param_info(const surfd_unet *u, int i, const char **key, int64_t 
  * dev_ptr: device fp32, contiguous; repacked into the private MFMA fragment layout. */
 int surfd_unet_set_param(surfd_unet *u, const char *key, const void *dev_ptr,
                          const int64_t *shape, int ndim, surfd_stream s);
-/* fails with SURFD_ERR_STATE naming the first tensor that was never set */
+/* fails with SURFD_ERR_STATE naming the first tensor that was not set */
 int surfd_unet_finalize(surfd_unet *u, surfd_stream s);
 /* UNetModel.forward (openaimodel.py:710-749) / MDM.forward (mdm.py:91-110):
  * x[B,1,L], t[B] (int64, original-scale timesteps), ctx[B,context_dim] or NULL,

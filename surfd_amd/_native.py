@@ -242,3 +242,58 @@ def stream() -> int:
 
 def shape_arr(shape):
     return (C.c_int64 * max(len(shape), 1))(*shape)
+
+
+class ParamBinder:
+    """Keeps one native handle's copy of a module's weights current (CbnDecoder, Dgcnn, MDM, CrossAttention).
+
+    set_param / finalize: names of the handle's entry points (finalize: None where there is none); wanted: which
+    state_dict keys the handle takes (None: all).  One binder per handle: ``bound`` is the key that handle was last sent."""
+
+    def __init__(self, set_param: str, finalize: Optional[str] = None, wanted=None):
+        self._set_param, self._finalize, self._wanted = set_param, finalize, wanted
+        self._slots = None
+        self.bound = None
+
+    def key(self, module) -> tuple:
+        # (storage address, version) of every tensor the handle is sent.  The SLOTS — (key, owning dict, leaf name) in
+        # state_dict order, parameters and persistent buffers — are collected once (the module tree never changes;
+        # rebuilding a 101-entry state_dict on every udf call is measurable in callback mode); the tensors are looked up in
+        # them on every call, so any rebinding is seen whether or not it goes through a hook: `.to()` / `.cuda()`,
+        # `load_state_dict(assign=True)` on this module or a parent, `decoder.blocks.0.fc_0.weight = nn.Parameter(...)`
+        # (ADVICE r2).
+        if self._slots is None:
+            slots = []
+            for prefix, mod in module.named_modules():
+                for owner in (mod._parameters, mod._buffers):
+                    for name in owner:
+                        k = f"{prefix}.{name}" if prefix else name
+                        if name not in mod._non_persistent_buffers_set and (self._wanted is None or self._wanted(k)):
+                            slots.append((k, owner, name))
+            self._slots = slots
+        return tuple((t.data_ptr(), t._version) for _, d, n in self._slots for t in (d[n],) if t is not None)
+
+    def bind(self, module, handle) -> bool:
+        """Sends every tensor and finalizes if the key changed since this handle was last sent; True when it did."""
+        key = self.key(module)
+        if key == self.bound:
+            return False
+        import torch
+        L, st = lib(), stream()
+        set_param = getattr(L, self._set_param)
+        for k, d, n in self._slots:
+            t = d[n]
+            if t is None:
+                continue
+            if n == "num_batches_tracked":
+                check(set_param(handle, k.encode(), None, shape_arr(()), 0, st))
+                continue
+            t = t.detach()
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                t = t.float().contiguous()
+            check(set_param(handle, k.encode(), ptr(t), shape_arr(tuple(t.shape)), t.dim(), st))
+        if self._finalize:
+            check(getattr(L, self._finalize)(handle, st))
+        torch.cuda.current_stream().synchronize()      # temporaries made above may be freed now
+        self.bound = key
+        return True

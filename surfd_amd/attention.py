@@ -29,24 +29,17 @@ class CrossAttention(nn.Module):
         self.to_v = nn.Linear(context_dim, inner, bias=False)
         self.to_out = nn.Sequential(nn.Linear(inner, query_dim), nn.Dropout(dropout))
         self._handle = None
-        self._bound_key = None
+        self._binder = N.ParamBinder("surfd_xattn_set_param")
 
     def _native(self):
+        if not self.to_q.weight.is_cuda:
+            raise RuntimeError("surfd_amd.attention.CrossAttention runs on the GPU only: move the module with .cuda() (no CPU path)")
         L = N.lib()
-        sd = {k: v for k, v in self.state_dict().items()}
-        key = tuple((k, v.data_ptr(), v._version) for k, v in sd.items())
         if self._handle is None:
             h = C.c_void_p()
             N.check(L.surfd_xattn_create(self.query_dim, self.context_dim, self.heads, self.dim_head, C.byref(h)))
             self._handle = h
-        if key != self._bound_key:
-            for k, v in sd.items():
-                if not v.is_cuda:
-                    raise RuntimeError("surfd_amd.attention.CrossAttention runs on the GPU only: move the module with .cuda() (no CPU path)")
-                t = v.detach().float().contiguous()
-                shape = (C.c_int64 * 4)(*t.shape)
-                N.check(L.surfd_xattn_set_param(self._handle, k.encode(), C.c_void_p(t.data_ptr()), shape, t.dim(), N.stream()))
-            self._bound_key = key
+        self._binder.bind(self, self._handle)
         return L, self._handle
 
     @torch.no_grad()

@@ -134,52 +134,24 @@ class CbnDecoder(nn.Module):
                     t = (torch.rand(shape, generator=g) * 2 - 1) * bound
                 _register(self, key, t, True)
         self._handle = None
-        self._bound_key = None          # (device, versions) the native copy was made from
+        self._binder = N.ParamBinder("surfd_decoder_set_param", "surfd_decoder_finalize")
         self._latents_key = None
-        self._key_slots = None
 
     # ---- native handle management -------------------------------------------------------------
     def _state_key(self):
-        # (storage address, version) of every tensor of the state_dict.  The SLOTS — (owning dict, leaf name) in state_dict
-        # order — are collected once (the module tree never changes; rebuilding a 101-entry state_dict on every udf call is
-        # measurable in callback mode); the tensors are looked up in them on every call, so any rebinding is seen whether or
-        # not it goes through a hook: `.to()` / `.cuda()`, `load_state_dict(assign=True)` on this module or a parent,
-        # `decoder.blocks.0.fc_0.weight = nn.Parameter(...)`.
-        if self._key_slots is None:
-            slots = []
-            for mod_name, mod in self.named_modules():
-                for name in mod._parameters:
-                    slots.append((mod._parameters, name))
-                for name in mod._buffers:
-                    if name not in mod._non_persistent_buffers_set:
-                        slots.append((mod._buffers, name))
-            self._key_slots = slots
-        return tuple((t.data_ptr(), t._version) for d, n in self._key_slots for t in (d[n],) if t is not None)
+        return self._binder.key(self)
 
     def _native(self):
         first = next(self.parameters())
         if not first.is_cuda:
             raise RuntimeError("CbnDecoder runs only on the GPU through libsurfd_hip.so (no CPU fallback); call .cuda() first")
         L = N.lib()
-        key = self._state_key()
         if self._handle is None:
             h = C.c_void_p()
             c = self.cfg
             N.check(L.surfd_decoder_create(c.input_dim, c.latent_dim, c.hidden_dim, c.num_hidden_layers, C.byref(h)))
             self._handle = h
-        if self._bound_key != key:
-            st = N.stream()
-            for k, v in self.state_dict(keep_vars=True).items():
-                if k.endswith("num_batches_tracked"):
-                    N.check(L.surfd_decoder_set_param(self._handle, k.encode(), None, N.shape_arr(()), 0, st))
-                    continue
-                t = v.detach()
-                if t.dtype != torch.float32 or not t.is_contiguous():
-                    t = t.float().contiguous()
-                N.check(L.surfd_decoder_set_param(self._handle, k.encode(), N.ptr(t), N.shape_arr(tuple(t.shape)), t.dim(), st))
-            N.check(L.surfd_decoder_finalize(self._handle, st))
-            torch.cuda.current_stream().synchronize()      # temporaries made above may be freed now
-            self._bound_key = key
+        if self._binder.bind(self, self._handle):
             self._latents_key = None
         return L, self._handle
 

@@ -32,6 +32,27 @@ void set_error(const char *fmt, ...);
 
 static inline hipStream_t as_stream(surfd_stream s) { return reinterpret_cast<hipStream_t>(s); }
 
+// The grow-only workspace of a handle.  A call's partial results live there: ONE STREAM AT A TIME PER HANDLE.
+struct DeviceArena {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+
+    // no-op when the arena is large enough; what it held is lost otherwise
+    int reserve(size_t need, hipStream_t st) {
+        if (need <= bytes) return SURFD_OK;
+        HIP_TRY(hipStreamSynchronize(st));                // the previous call's kernels may still read the old arena
+        release();
+        HIP_TRY(hipMalloc(&ptr, need));
+        bytes = need;
+        return SURFD_OK;
+    }
+    void release() {
+        (void)hipFree(ptr);
+        ptr = nullptr;
+        bytes = 0;
+    }
+};
+
 template <typename T>
 static inline T ceil_div(T a, T b) { return (a + b - 1) / b; }
 

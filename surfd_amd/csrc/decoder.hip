@@ -21,6 +21,7 @@
 //   fully coalesced 16-byte load per lane per 4 MFMAs.
 //   Algorithmic work: 5 308 416 FLOP per forward point, x3 for a gradient point.
 #include "common.h"
+#include "paramtable.h"
 #include "points.h"
 #include <string.h>
 #include <stdlib.h>
@@ -1610,16 +1611,9 @@ int decoder_build_unsafe() { return SURFD_DEC_OVL != 0; }
 
 using namespace surfd;
 
-struct DecTensor {
-    std::string key;
-    std::vector<int64_t> shape;
-    bool is_set = false;
-};
-
 struct surfd_decoder {
     int input_dim = 63, D = 32, hidden = 512, nb = 5, device = -1;
-    std::vector<DecTensor> params;
-    std::map<std::string, int> index;
+    ParamTable params;                // CbnDecoder.state_dict()
     bool allocated = false, finalized = false;
     // private device copies
     float *wpack = nullptr, *vecs = nullptr;
@@ -1635,17 +1629,14 @@ struct surfd_decoder {
     std::vector<void *> allocs;
 };
 
-static void dec_add(surfd_decoder *d, const std::string &k, std::vector<int64_t> shape) {
-    d->index[k] = (int)d->params.size();
-    d->params.push_back({k, std::move(shape)});
-}
+static void dec_add(surfd_decoder *d, const std::string &k, std::initializer_list<int64_t> shape) { d->params.add(k, shape); }
 
 static void dec_add_cbn(surfd_decoder *d, const std::string &p) {
     const int64_t Hh = d->hidden, D = d->D;
     dec_add(d, p + ".conv_gamma.weight", {Hh, D, 1}); dec_add(d, p + ".conv_gamma.bias", {Hh});
     dec_add(d, p + ".conv_beta.weight", {Hh, D, 1});  dec_add(d, p + ".conv_beta.bias", {Hh});
     dec_add(d, p + ".bn.running_mean", {Hh});         dec_add(d, p + ".bn.running_var", {Hh});
-    dec_add(d, p + ".bn.num_batches_tracked", {});
+    d->params.add(p + ".bn.num_batches_tracked", {}, 0, true);
 }
 
 static int dec_alloc(surfd_decoder *d) {
@@ -1739,33 +1730,22 @@ void surfd_decoder_destroy(surfd_decoder *d) {
     delete d;
 }
 
-int surfd_decoder_num_params(const surfd_decoder *d) { return d ? (int)d->params.size() : 0; }
+int surfd_decoder_num_params(const surfd_decoder *d) { return d ? d->params.size() : 0; }
 
 int surfd_decoder_param_info(const surfd_decoder *d, int i, const char **key, int64_t shape[4], int *ndim) {
-    if (!d || i < 0 || i >= (int)d->params.size()) SURFD_FAIL(SURFD_ERR_ARG, "surfd_decoder_param_info: bad index %d", i);
-    *key = d->params[i].key.c_str();
-    *ndim = (int)d->params[i].shape.size();
-    for (int j = 0; j < *ndim; ++j) shape[j] = d->params[i].shape[j];
-    return SURFD_OK;
+    return param_info(d ? &d->params : nullptr, "surfd_decoder_param_info", i, key, shape, ndim);
 }
 
 int surfd_decoder_set_param(surfd_decoder *d, const char *key, const void *dev_ptr, const int64_t *shape, int ndim,
                             surfd_stream s) {
-    if (!d || !key) SURFD_FAIL(SURFD_ERR_ARG, "surfd_decoder_set_param: null argument");
-    auto it = d->index.find(key);
-    if (it == d->index.end()) SURFD_FAIL(SURFD_ERR_ARG, "surfd_decoder_set_param: unexpected key '%s'", key);
-    DecTensor &t = d->params[it->second];
-    if (ndim != (int)t.shape.size()) SURFD_FAIL(SURFD_ERR_ARG, "surfd_decoder_set_param: '%s' rank %d, expected %zu", key, ndim, t.shape.size());
-    size_t numel = 1;
-    for (int j = 0; j < ndim; ++j) {
-        if (shape[j] != t.shape[j]) SURFD_FAIL(SURFD_ERR_ARG, "surfd_decoder_set_param: '%s' dim %d is %lld, expected %lld", key, j, (long long)shape[j], (long long)t.shape[j]);
-        numel *= shape[j];
-    }
-    const std::string k(key);
-    if (k.size() > 19 && k.rfind("num_batches_tracked") == k.size() - 19) { t.is_set = true; return SURFD_OK; }
+    if (!d) SURFD_FAIL(SURFD_ERR_ARG, "surfd_decoder_set_param: null handle");
+    int pi, rc;
+    if ((rc = d->params.match("surfd_decoder_set_param", key, shape, ndim, &pi))) return rc;
+    if (d->params[pi].ignored) { d->params.mark(pi); return SURFD_OK; }
     if (!dev_ptr) SURFD_FAIL(SURFD_ERR_ARG, "surfd_decoder_set_param: '%s' has a null pointer", key);
-    int rc = dec_alloc(d);
-    if (rc) return rc;
+    if ((rc = dec_alloc(d))) return rc;
+    const std::string &k = d->params[pi].key;
+    const size_t numel = d->params.numel(pi);
     hipStream_t st = as_stream(s);
     const float *src = static_cast<const float *>(dev_ptr);
     auto copy = [&](float *dst) -> int {
@@ -1807,15 +1787,15 @@ int surfd_decoder_set_param(surfd_decoder *d, const char *key, const void *dev_p
         }
     }
     if (rc) return rc;
-    t.is_set = true;
+    d->params.mark(pi);
     d->finalized = false;
     return SURFD_OK;
 }
 
 int surfd_decoder_finalize(surfd_decoder *d, surfd_stream s) {
     if (!d) SURFD_FAIL(SURFD_ERR_ARG, "surfd_decoder_finalize: null handle");
-    for (auto &t : d->params)
-        if (!t.is_set) SURFD_FAIL(SURFD_ERR_STATE, "surfd_decoder_finalize: parameter '%s' was never set", t.key.c_str());
+    int rc;
+    if ((rc = d->params.require_all("surfd_decoder_finalize"))) return rc;
     // f16x2 planes of the forward matrices: one power-of-two scale from max |W|, then split (all on the
     // stream, no host round trip); the fp32 packs are the source
     hipStream_t st = as_stream(s);

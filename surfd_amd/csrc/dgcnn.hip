@@ -29,6 +29,7 @@
 // bracketed by __syncthreads() on both sides (every reader of the previous tile is past the barrier before a lane
 // overwrites it); cross-lane values move with __shfl_xor only (the compiler places the waits for ds_bpermute).
 #include "common.h"
+#include "paramtable.h"
 #include <cfloat>
 #include <cmath>
 #include <cstring>
@@ -314,49 +315,19 @@ static int dg_knn_launch(const float *pts, int B, int N, int k, int S, int span,
 
 using namespace surfd;
 
-namespace {
-struct DgParam {
-    std::string key;
-    int64_t shape[2];
-    int ndim;
-    long off;            // float offset in the parameter block, -1 = num_batches_tracked (ignored)
-};
-}  // namespace
-
 struct surfd_dgcnn {
     int L = 0, k = 0;
-    std::vector<DgParam> params;
-    std::vector<bool> have;
+    ParamTable params;                // Dgcnn(L).state_dict(); tag: float offset in pblock
+    int bn0[5] = {}, conv[5] = {};    // table index of bn_<l+1>.weight (bias, running_mean, running_var follow) and conv_<l+1>.weight
     long nparam = 0;
     float *pblock = nullptr;          // the state_dict tensors, fp32
     float *derived = nullptr;         // combined weights of blocks 1-4, BN scale / shift of blocks 1-5
     float *wc[4] = {}, *sc[5] = {}, *sh[5] = {};
     bool finalized = false;
-    // workspace arena (grows; surfd_dgcnn_knn may use it through a const handle)
-    mutable void *ws = nullptr;
-    mutable size_t ws_bytes = 0;
+    mutable DeviceArena ws;           // surfd_dgcnn_knn uses it through a const handle
 };
 
-static const DgParam *dg_find(const surfd_dgcnn *d, const char *key, int *which) {
-    for (size_t i = 0; i < d->params.size(); ++i)
-        if (d->params[i].key == key) { *which = (int)i; return &d->params[i]; }
-    return nullptr;
-}
-
-static float *dg_ptr(const surfd_dgcnn *d, const char *key) {
-    int w;
-    const DgParam *p = dg_find(d, key, &w);
-    return d->pblock + p->off;
-}
-
-static int dg_ws(const surfd_dgcnn *d, size_t bytes, hipStream_t st) {
-    if (bytes <= d->ws_bytes) return SURFD_OK;
-    HIP_TRY(hipStreamSynchronize(st));                // the previous call's kernels may still read the old arena
-    (void)hipFree(d->ws); d->ws = nullptr; d->ws_bytes = 0;
-    HIP_TRY(hipMalloc(&d->ws, bytes));
-    d->ws_bytes = bytes;
-    return SURFD_OK;
-}
+static float *dg_ptr(const surfd_dgcnn *d, int i) { return d->pblock + d->params[i].tag; }
 
 // splits per query block: ~1024 workgroups over the chip, at least one 256-point tile per split, at most 256 / k splits so
 // that the partial lists (2 x S x k words per point) fit in the x1..x4 workspace (512 words per point) of the forward pass
@@ -418,18 +389,18 @@ int surfd_dgcnn_create(int size_latent, int k, surfd_dgcnn **out) {
     long off = 0;
     for (int l = 0; l < 5; ++l) {
         const std::string p = "bn_" + std::to_string(l + 1) + ".";
+        d->bn0[l] = d->params.size();
         for (const char *f : {"weight", "bias", "running_mean", "running_var"}) {
-            d->params.push_back({p + f, {bnc[l], 0}, 1, off});
+            d->params.add(p + f, {bnc[l]}, off);
             off += bnc[l];
         }
-        d->params.push_back({p + "num_batches_tracked", {0, 0}, 0, -1});
+        d->params.add(p + "num_batches_tracked", {}, 0, true);
     }
     const int cin[5] = {6, 128, 128, 256, DG_FEAT};
     for (int l = 0; l < 5; ++l) {
-        d->params.push_back({"conv_" + std::to_string(l + 1) + ".weight", {bnc[l], cin[l]}, 2, off});
+        d->conv[l] = d->params.add("conv_" + std::to_string(l + 1) + ".weight", {bnc[l], cin[l]}, off);
         off += (long)bnc[l] * cin[l];
     }
-    d->have.assign(d->params.size(), false);
     d->nparam = off;
     *out = d;
     return SURFD_OK;
@@ -437,53 +408,41 @@ int surfd_dgcnn_create(int size_latent, int k, surfd_dgcnn **out) {
 
 void surfd_dgcnn_destroy(surfd_dgcnn *d) {
     if (!d) return;
-    (void)hipFree(d->pblock); (void)hipFree(d->derived); (void)hipFree(d->ws);
+    (void)hipFree(d->pblock); (void)hipFree(d->derived);
+    d->ws.release();
     delete d;
 }
 
-int surfd_dgcnn_num_params(const surfd_dgcnn *d) { return d ? (int)d->params.size() : 0; }
+int surfd_dgcnn_num_params(const surfd_dgcnn *d) { return d ? d->params.size() : 0; }
 
 int surfd_dgcnn_param_info(const surfd_dgcnn *d, int i, const char **key, int64_t shape[4], int *ndim) {
-    if (!d || i < 0 || i >= (int)d->params.size() || !key || !shape || !ndim) SURFD_FAIL(SURFD_ERR_ARG, "surfd_dgcnn_param_info: bad argument");
-    const DgParam &p = d->params[i];
-    *key = p.key.c_str();
-    *ndim = p.ndim;
-    for (int j = 0; j < p.ndim; ++j) shape[j] = p.shape[j];
-    return SURFD_OK;
+    return param_info(d ? &d->params : nullptr, "surfd_dgcnn_param_info", i, key, shape, ndim);
 }
 
 int surfd_dgcnn_set_param(surfd_dgcnn *d, const char *key, const void *dev_ptr, const int64_t *shape, int ndim, surfd_stream s) {
-    if (!d || !key) SURFD_FAIL(SURFD_ERR_ARG, "surfd_dgcnn_set_param: null argument");
-    int w;
-    const DgParam *p = dg_find(d, key, &w);
-    if (!p) SURFD_FAIL(SURFD_ERR_ARG, "surfd_dgcnn_set_param: unknown key '%s'", key);
-    if (p->off < 0) { d->have[w] = true; return SURFD_OK; }          // num_batches_tracked: accepted, ignored
-    if (!dev_ptr || !shape || ndim != p->ndim) SURFD_FAIL(SURFD_ERR_ARG, "surfd_dgcnn_set_param: bad tensor for '%s'", key);
-    int rc;
+    if (!d) SURFD_FAIL(SURFD_ERR_ARG, "surfd_dgcnn_set_param: null handle");
+    int i, rc;
+    if ((rc = d->params.match("surfd_dgcnn_set_param", key, shape, ndim, &i))) return rc;
+    if (d->params[i].ignored) { d->params.mark(i); return SURFD_OK; }
+    if (!dev_ptr) SURFD_FAIL(SURFD_ERR_ARG, "surfd_dgcnn_set_param: '%s' has a null pointer", key);
     if ((rc = dg_alloc(d))) return rc;
-    size_t n = 1;
-    for (int j = 0; j < ndim; ++j) {
-        if (shape[j] != p->shape[j]) SURFD_FAIL(SURFD_ERR_ARG, "surfd_dgcnn_set_param: wrong shape for '%s'", key);
-        n *= (size_t)shape[j];
-    }
-    HIP_TRY(hipMemcpyAsync(d->pblock + p->off, dev_ptr, n * sizeof(float), hipMemcpyDeviceToDevice, as_stream(s)));
-    d->have[w] = true;
+    HIP_TRY(hipMemcpyAsync(dg_ptr(d, i), dev_ptr, d->params.numel(i) * sizeof(float), hipMemcpyDeviceToDevice, as_stream(s)));
+    d->params.mark(i);
     d->finalized = false;
     return SURFD_OK;
 }
 
 int surfd_dgcnn_finalize(surfd_dgcnn *d, surfd_stream s) {
     if (!d) SURFD_FAIL(SURFD_ERR_ARG, "surfd_dgcnn_finalize: null handle");
-    for (size_t i = 0; i < d->params.size(); ++i)
-        if (!d->have[i] && d->params[i].off >= 0) SURFD_FAIL(SURFD_ERR_STATE, "surfd_dgcnn_finalize: '%s' not set", d->params[i].key.c_str());
+    int rc;
+    if ((rc = d->params.require_all("surfd_dgcnn_finalize"))) return rc;
     DgPrep pp;
     for (int l = 0; l < 5; ++l) {
-        const std::string c = "conv_" + std::to_string(l + 1) + ".weight", b = "bn_" + std::to_string(l + 1) + ".";
-        if (l < 4) { pp.w[l] = dg_ptr(d, c.c_str()); pp.wc[l] = d->wc[l]; pp.din[l] = DG_DIN[l]; pp.dout[l] = DG_DOUT[l]; }
-        pp.bnw[l] = dg_ptr(d, (b + "weight").c_str());
-        pp.bnb[l] = dg_ptr(d, (b + "bias").c_str());
-        pp.bnm[l] = dg_ptr(d, (b + "running_mean").c_str());
-        pp.bnv[l] = dg_ptr(d, (b + "running_var").c_str());
+        if (l < 4) { pp.w[l] = dg_ptr(d, d->conv[l]); pp.wc[l] = d->wc[l]; pp.din[l] = DG_DIN[l]; pp.dout[l] = DG_DOUT[l]; }
+        pp.bnw[l] = dg_ptr(d, d->bn0[l]);
+        pp.bnb[l] = dg_ptr(d, d->bn0[l] + 1);
+        pp.bnm[l] = dg_ptr(d, d->bn0[l] + 2);
+        pp.bnv[l] = dg_ptr(d, d->bn0[l] + 3);
         pp.sc[l] = d->sc[l]; pp.sh[l] = d->sh[l];
         pp.nbn[l] = l < 4 ? DG_DOUT[l] : d->L;
     }
@@ -501,8 +460,8 @@ int surfd_dgcnn_knn(const surfd_dgcnn *d, const float *pts, int B, int N, float 
     int S, span;
     dg_splits(B, N, d->k, &S, &span);
     const size_t np = (size_t)B * S * d->k * N;
-    if ((rc = dg_ws(d, 2 * np * sizeof(float), st))) return rc;
-    float *pd = (float *)d->ws;
+    if ((rc = d->ws.reserve(2 * np * sizeof(float), st))) return rc;
+    float *pd = (float *)d->ws.ptr;
     return dg_knn_any(d, pts, B, N, pd, (int *)(pd + np), S, span, dists, idx, st);
 }
 
@@ -521,8 +480,8 @@ int surfd_dgcnn_forward_features(surfd_dgcnn *d, const float *pts, int B, int N,
     const int T = ceil_div(N, 64);
     // arena: x1..x4 [B N, 512] | P,Q [B N, <= 512] | idx [B N, k] int32 | conv_5 partials 2 x [B, T, L]
     const size_t nx = (size_t)rows * DG_FEAT, ni = (size_t)rows * k, nr = (size_t)B * T * L;
-    if ((rc = dg_ws(d, (2 * nx + ni + 2 * nr) * sizeof(float), st))) return rc;
-    float *X = (float *)d->ws, *PQ = X + nx;
+    if ((rc = d->ws.reserve((2 * nx + ni + 2 * nr) * sizeof(float), st))) return rc;
+    float *X = (float *)d->ws.ptr, *PQ = X + nx;
     int *idx = (int *)(PQ + nx);
     float *pmax = (float *)(idx + ni), *pmin = pmax + nr;
     int S, span;
@@ -544,7 +503,7 @@ int surfd_dgcnn_forward_features(surfd_dgcnn *d, const float *pts, int B, int N,
     }
     if (x1234) HIP_TRY(hipMemcpyAsync(x1234, X, nx * sizeof(float), hipMemcpyDeviceToDevice, st));
     hipLaunchKernelGGL(dg_linear_kernel<true>, dim3((unsigned)ceil_div(L, 64), (unsigned)T, (unsigned)B), dim3(256), 0, st,
-                       (const float *)X, (long)DG_FEAT, (const float *)dg_ptr(d, "conv_5.weight"), DG_FEAT, L, N, (float *)nullptr, 0L,
+                       (const float *)X, (long)DG_FEAT, (const float *)dg_ptr(d, d->conv[4]), DG_FEAT, L, N, (float *)nullptr, 0L,
                        pmax, pmin);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(dg_global_kernel, dim3((unsigned)ceil_div(B * L, 256)), dim3(256), 0, st,

@@ -1,6 +1,6 @@
 // Host scaffold of the mesh handles (raycast.hip, meshdist.hip, meshintersect.hip, winding.hip, raster.hip), included after
-// common.h.  Host code only: what a kernel computes, and with it every result, is each file's own.
-//   DeviceArena    the grow-only workspace of a handle.  A call's partial results live there: ONE STREAM AT A TIME PER HANDLE.
+// common.h.  Host code only: what a kernel computes, and with it every result, is each file's own.  The handles' grow-only
+// workspace, DeviceArena, is in common.h: the network handles use it too.
 //   split_units    how many workgroups share a call's triangle range, so that a small call still fills the chip.
 //   CreateFlags    the flag words a create's kernels raise; mesh_create_args / mesh_bad_index: the refusals every create makes.
 //   read_counter   a device counter and the host total that goes with it (the *_skipped entry points).
@@ -9,26 +9,6 @@
 #include <climits>
 
 namespace surfd {
-
-struct DeviceArena {
-    void *ptr = nullptr;
-    size_t bytes = 0;
-
-    // no-op when the arena is large enough; what it held is lost otherwise
-    int reserve(size_t need, hipStream_t st) {
-        if (need <= bytes) return SURFD_OK;
-        HIP_TRY(hipStreamSynchronize(st));                // the previous call's kernels may still read the old arena
-        release();
-        HIP_TRY(hipMalloc(&ptr, need));
-        bytes = need;
-        return SURFD_OK;
-    }
-    void release() {
-        (void)hipFree(ptr);
-        ptr = nullptr;
-        bytes = 0;
-    }
-};
 
 // `units` (chunks, groups) are shared by S workgroups per block of `block` items (rays, queries, triangles), `span` whole units
 // each: about `target` workgroups over the chip (2048 = 8 per CU), at most max_splits (the kernel's grid.y).  target = 1: S = 1.

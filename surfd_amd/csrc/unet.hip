@@ -710,10 +710,7 @@ using namespace surfd;
 
 namespace {
 
-void add_param(surfd_unet *u, const std::string &k, std::vector<int64_t> shape) {
-    u->pindex[k] = (int)u->params.size();
-    u->params.push_back({k, std::move(shape)});
-}
+void add_param(surfd_unet *u, const std::string &k, std::initializer_list<int64_t> shape) { u->params.add(k, shape); }
 
 int new_buf(surfd_unet *u, int C, int ds) { u->bufs.push_back({C, ds}); return (int)u->bufs.size() - 1; }
 
@@ -977,8 +974,8 @@ int unet_alloc(surfd_unet *u) {
     HIP_TRY(hipMemset(u->wpack, 0, off * sizeof(float)));
     // ---- vectors: every 1-D parameter raw, then combined biases ----
     size_t voff = 0;
-    for (auto &p : u->params)
-        if (p.shape.size() == 1) { u->vec_off[p.key] = voff; voff += (size_t)ceil_div<int64_t>(p.shape[0], 4) * 4; }
+    for (auto &p : u->params.entries)
+        if (p.ndim == 1) { u->vec_off[p.key] = voff; voff += (size_t)ceil_div<int64_t>(p.shape[0], 4) * 4; }
     auto place_bias = [&](ConvPlan &c) { c.bias_off = voff; voff += (size_t)ceil_div(c.Cout, 4) * 4; };
     for (auto &op : u->ops) if (op.kind == 0) place_bias(op.conv);
     place_bias(u->lin1); place_bias(u->lin2); place_bias(u->lin3);
@@ -1063,31 +1060,21 @@ void surfd_unet_destroy(surfd_unet *u) {
     delete u;
 }
 
-int surfd_unet_num_params(const surfd_unet *u) { return u ? (int)u->params.size() : 0; }
+int surfd_unet_num_params(const surfd_unet *u) { return u ? u->params.size() : 0; }
 
 int surfd_unet_param_info(const surfd_unet *u, int i, const char **key, int64_t shape[4], int *ndim) {
-    if (!u || i < 0 || i >= (int)u->params.size()) SURFD_FAIL(SURFD_ERR_ARG, "surfd_unet_param_info: bad index %d", i);
-    *key = u->params[i].key.c_str();
-    *ndim = (int)u->params[i].shape.size();
-    for (int j = 0; j < *ndim; ++j) shape[j] = u->params[i].shape[j];
-    return SURFD_OK;
+    return param_info(u ? &u->params : nullptr, "surfd_unet_param_info", i, key, shape, ndim);
 }
 
 int surfd_unet_set_param(surfd_unet *u, const char *key, const void *dev_ptr, const int64_t *shape, int ndim, surfd_stream s) {
-    if (!u || !key || !dev_ptr) SURFD_FAIL(SURFD_ERR_ARG, "surfd_unet_set_param: null argument");
-    std::string k(key);
-    if (k.rfind("Unet.", 0) == 0) k = k.substr(5);
-    auto it = u->pindex.find(k);
-    if (it == u->pindex.end()) SURFD_FAIL(SURFD_ERR_ARG, "surfd_unet_set_param: unexpected key '%s'", key);
-    ParamInfo &p = u->params[it->second];
-    if (ndim != (int)p.shape.size()) SURFD_FAIL(SURFD_ERR_ARG, "surfd_unet_set_param: '%s' rank %d, expected %zu", key, ndim, p.shape.size());
-    size_t numel = 1;
-    for (int j = 0; j < ndim; ++j) {
-        if (shape[j] != p.shape[j]) SURFD_FAIL(SURFD_ERR_ARG, "surfd_unet_set_param: '%s' dim %d is %lld, expected %lld", key, j, (long long)shape[j], (long long)p.shape[j]);
-        numel *= shape[j];
-    }
-    int rc = unet_alloc(u);
-    if (rc) return rc;
+    if (!u) SURFD_FAIL(SURFD_ERR_ARG, "surfd_unet_set_param: null handle");
+    const bool prefixed = key && !strncmp(key, "Unet.", 5);          // checkpoint keys carry the module's name
+    int pi, rc;
+    if ((rc = u->params.match("surfd_unet_set_param", prefixed ? key + 5 : key, shape, ndim, &pi))) return rc;
+    if (!dev_ptr) SURFD_FAIL(SURFD_ERR_ARG, "surfd_unet_set_param: '%s' has a null pointer", key);
+    if ((rc = unet_alloc(u))) return rc;
+    const std::string &k = u->params[pi].key;
+    const size_t numel = u->params.numel(pi);
     hipStream_t st = as_stream(s);
     const float *src = static_cast<const float *>(dev_ptr);
     if (ndim == 1) {
@@ -1114,15 +1101,15 @@ int surfd_unet_set_param(surfd_unet *u, const char *key, const void *dev_ptr, co
         }
         if (!placed) SURFD_FAIL(SURFD_ERR_ARG, "surfd_unet_set_param: no plan site for '%s'", key);
     }
-    p.is_set = true;
+    u->params.mark(pi);
     u->finalized = false;
     return SURFD_OK;
 }
 
 int surfd_unet_finalize(surfd_unet *u, surfd_stream s) {
     if (!u) SURFD_FAIL(SURFD_ERR_ARG, "surfd_unet_finalize: null handle");
-    for (auto &p : u->params)
-        if (!p.is_set) SURFD_FAIL(SURFD_ERR_STATE, "surfd_unet_finalize: parameter '%s' was never set", p.key.c_str());
+    int rc;
+    if ((rc = u->params.require_all("surfd_unet_finalize"))) return rc;
     hipStream_t st = as_stream(s);
     // combined biases (e.g. out_layers.3.bias + skip_connection.bias; time_embed.2.bias + sketch_emb.bias)
     auto combine = [&](ConvPlan &c) -> int {
@@ -1132,7 +1119,6 @@ int surfd_unet_finalize(surfd_unet *u, surfd_stream s) {
         LAUNCH_CHECK();
         return SURFD_OK;
     };
-    int rc;
     for (auto &op : u->ops) if (op.kind == 0) if ((rc = combine(op.conv))) return rc;
     if ((rc = combine(u->lin1))) return rc;
     if ((rc = combine(u->lin2))) return rc;

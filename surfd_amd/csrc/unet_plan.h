@@ -2,15 +2,10 @@
 // and conv_f16x2.hip (split-fp16 conv kernel).
 #pragma once
 #include "common.h"
+#include "paramtable.h"
 #include "unet_api.h"
 
 namespace surfd {
-
-struct ParamInfo {
-    std::string key;
-    std::vector<int64_t> shape;
-    bool is_set = false;
-};
 
 struct View { int buf = -1; int choff = 0; };   // buf: index into buffers, -2 = external input, -3 = external output
 
@@ -64,11 +59,10 @@ struct Op { int kind; ConvPlan conv; AttnPlan attn; };   // 0 conv, 1 attn
 }  // namespace surfd
 
 struct surfd_unet {
-    using ParamInfo = surfd::ParamInfo; using BufInfo = surfd::BufInfo; using Op = surfd::Op; using ConvPlan = surfd::ConvPlan;
+    using BufInfo = surfd::BufInfo; using Op = surfd::Op; using ConvPlan = surfd::ConvPlan;
     surfd_unet_cfg cfg;
     int ted = 0;                                  // time-embed dim
-    std::vector<ParamInfo> params;
-    std::map<std::string, int> pindex;
+    surfd::ParamTable params;                    // the "Unet." tensors of the checkpoint, keys without the prefix
     std::vector<BufInfo> bufs;
     std::vector<Op> ops;                          // denoiser body, in execution order
     ConvPlan lin1, lin2, lin3;                    // embedding path

@@ -16,6 +16,7 @@
 // (grid.y of xa_core_kernel), b * n and b * m <= (2^24 - 1) * 64 = 1 073 741 760 token rows (grid.x of xa_linear_kernel,
 // one 64-row tile per workgroup of 256 threads, under 2^32 threads per launch), feature counts <= 65 535 * 64.
 #include "common.h"
+#include "paramtable.h"
 #include <cfloat>
 #include <cmath>
 #include <cstring>
@@ -159,12 +160,13 @@ __global__ __launch_bounds__(256) void xa_core_kernel(const float *Q, const floa
 
 using namespace surfd;
 
+enum { XA_WQ, XA_WK, XA_WV, XA_WO, XA_BO, XA_NW };
+
 struct surfd_xattn {
     int qdim = 0, cdim = 0, heads = 0, dh = 0, inner = 0;
-    float *wq = nullptr, *wk = nullptr, *wv = nullptr, *wo = nullptr, *bo = nullptr;
-    bool have[5] = {false, false, false, false, false};
-    float *ws = nullptr;
-    size_t ws_floats = 0;
+    ParamTable params;                // the reference module's state_dict; tag: index into w
+    float *w[XA_NW] = {};
+    DeviceArena ws;
 };
 
 // Row tiles ride on grid.x (hipDeviceProp_t::maxGridSize = {2^31 - 1, 65 536, 65 536} on gfx950), and a launch may not
@@ -192,13 +194,14 @@ int surfd_xattn_create(int query_dim, int context_dim, int heads, int dim_head, 
     if (context_dim <= 0) context_dim = query_dim;                  // default(context_dim, query_dim), attention.py:156
     surfd_xattn *a = new surfd_xattn();
     a->qdim = query_dim; a->cdim = context_dim; a->heads = heads; a->dh = dim_head; a->inner = heads * dim_head;
-    const size_t n[5] = {(size_t)a->inner * a->qdim, (size_t)a->inner * a->cdim, (size_t)a->inner * a->cdim,
-                         (size_t)a->qdim * a->inner, (size_t)a->qdim};
-    float **p[5] = {&a->wq, &a->wk, &a->wv, &a->wo, &a->bo};
-    for (int i = 0; i < 5; ++i)
-        if (hipMalloc(p[i], n[i] * sizeof(float)) != hipSuccess) {
-            for (int j = 0; j < i; ++j) (void)hipFree(*p[j]);
-            delete a;
+    a->params.add("to_q.weight", {a->inner, a->qdim}, XA_WQ);
+    a->params.add("to_k.weight", {a->inner, a->cdim}, XA_WK);
+    a->params.add("to_v.weight", {a->inner, a->cdim}, XA_WV);
+    a->params.add("to_out.0.weight", {a->qdim, a->inner}, XA_WO);
+    a->params.add("to_out.0.bias", {a->qdim}, XA_BO);
+    for (int i = 0; i < XA_NW; ++i)
+        if (hipMalloc(&a->w[i], a->params.numel(i) * sizeof(float)) != hipSuccess) {
+            surfd_xattn_destroy(a);
             SURFD_FAIL(SURFD_ERR_HIP, "surfd_xattn_create: hipMalloc failed");
         }
     *out = a;
@@ -207,26 +210,18 @@ int surfd_xattn_create(int query_dim, int context_dim, int heads, int dim_head, 
 
 void surfd_xattn_destroy(surfd_xattn *a) {
     if (!a) return;
-    (void)hipFree(a->wq); (void)hipFree(a->wk); (void)hipFree(a->wv); (void)hipFree(a->wo); (void)hipFree(a->bo); (void)hipFree(a->ws);
+    for (float *p : a->w) (void)hipFree(p);
+    a->ws.release();
     delete a;
 }
 
-// state_dict names of the reference module: to_q.weight [inner, query_dim], to_k.weight / to_v.weight [inner, context_dim],
-// to_out.0.weight [query_dim, inner], to_out.0.bias [query_dim]
 int surfd_xattn_set_param(surfd_xattn *a, const char *name, const float *src, const int64_t *shape, int ndim, surfd_stream s) {
-    if (!a || !name || !src || !shape) SURFD_FAIL(SURFD_ERR_ARG, "surfd_xattn_set_param: null argument");
-    static const char *names[5] = {"to_q.weight", "to_k.weight", "to_v.weight", "to_out.0.weight", "to_out.0.bias"};
-    int which = -1;
-    for (int i = 0; i < 5; ++i) if (!strcmp(name, names[i])) which = i;
-    if (which < 0) SURFD_FAIL(SURFD_ERR_ARG, "surfd_xattn_set_param: unknown parameter '%s'", name);
-    const int64_t want[5][2] = {{a->inner, a->qdim}, {a->inner, a->cdim}, {a->inner, a->cdim}, {a->qdim, a->inner}, {a->qdim, 0}};
-    const int wnd = which == 4 ? 1 : 2;
-    if (ndim != wnd || shape[0] != want[which][0] || (wnd == 2 && shape[1] != want[which][1]))
-        SURFD_FAIL(SURFD_ERR_ARG, "surfd_xattn_set_param: wrong shape for '%s'", name);
-    float *dst[5] = {a->wq, a->wk, a->wv, a->wo, a->bo};
-    const size_t n = (size_t)want[which][0] * (wnd == 2 ? (size_t)want[which][1] : 1);
-    HIP_TRY(hipMemcpyAsync(dst[which], src, n * sizeof(float), hipMemcpyDeviceToDevice, as_stream(s)));
-    a->have[which] = true;
+    if (!a) SURFD_FAIL(SURFD_ERR_ARG, "surfd_xattn_set_param: null handle");
+    int i, rc;
+    if ((rc = a->params.match("surfd_xattn_set_param", name, shape, ndim, &i))) return rc;
+    if (!src) SURFD_FAIL(SURFD_ERR_ARG, "surfd_xattn_set_param: '%s' has a null pointer", name);
+    HIP_TRY(hipMemcpyAsync(a->w[a->params[i].tag], src, a->params.numel(i) * sizeof(float), hipMemcpyDeviceToDevice, as_stream(s)));
+    a->params.mark(i);
     return SURFD_OK;
 }
 
@@ -235,7 +230,8 @@ int surfd_xattn_set_param(surfd_xattn *a, const char *name, const float *src, co
 int surfd_xattn_forward(surfd_xattn *a, const float *x, const float *context, const unsigned char *mask, float *out,
                         int B, int N, int M, surfd_stream s) {
     if (!a) SURFD_FAIL(SURFD_ERR_ARG, "surfd_xattn_forward: null handle");
-    for (int i = 0; i < 5; ++i) if (!a->have[i]) SURFD_FAIL(SURFD_ERR_STATE, "surfd_xattn_forward: parameters not loaded");
+    int rc;
+    if ((rc = a->params.require_all("surfd_xattn_forward"))) return rc;
     if (B < 0 || N < 0) SURFD_FAIL(SURFD_ERR_ARG, "surfd_xattn_forward: negative size");
     if (B == 0 || N == 0) return SURFD_OK;                           // empty batch: nothing to do (pointers may be null)
     if (!x || !out) SURFD_FAIL(SURFD_ERR_ARG, "surfd_xattn_forward: null argument");
@@ -250,24 +246,17 @@ int surfd_xattn_forward(surfd_xattn *a, const float *x, const float *context, co
         SURFD_FAIL(SURFD_ERR_UNSUPPORTED, "surfd_xattn_forward: more than %ld token rows (b x n or b x m) are not supported", XA_MAX_ROWS);
     hipStream_t st = as_stream(s);
     const size_t nq = (size_t)B * N * a->inner, nk = (size_t)B * M * a->inner;
-    const size_t need = 2 * nq + 2 * nk;
-    if (need > a->ws_floats) {
-        HIP_TRY(hipStreamSynchronize(st));
-        (void)hipFree(a->ws); a->ws = nullptr; a->ws_floats = 0;
-        HIP_TRY(hipMalloc(&a->ws, need * sizeof(float)));
-        a->ws_floats = need;
-    }
-    float *q = a->ws, *o = q + nq, *k = o + nq, *v = k + nk;
-    int rc;
-    if ((rc = xa_linear(x, a->qdim, a->wq, nullptr, q, a->inner, (long)B * N, a->qdim, a->inner, st))) return rc;
-    if ((rc = xa_linear(context, cdim, a->wk, nullptr, k, a->inner, (long)B * M, cdim, a->inner, st))) return rc;
-    if ((rc = xa_linear(context, cdim, a->wv, nullptr, v, a->inner, (long)B * M, cdim, a->inner, st))) return rc;
+    if ((rc = a->ws.reserve((2 * nq + 2 * nk) * sizeof(float), st))) return rc;
+    float *q = (float *)a->ws.ptr, *o = q + nq, *k = o + nq, *v = k + nk;
+    if ((rc = xa_linear(x, a->qdim, a->w[XA_WQ], nullptr, q, a->inner, (long)B * N, a->qdim, a->inner, st))) return rc;
+    if ((rc = xa_linear(context, cdim, a->w[XA_WK], nullptr, k, a->inner, (long)B * M, cdim, a->inner, st))) return rc;
+    if ((rc = xa_linear(context, cdim, a->w[XA_WV], nullptr, v, a->inner, (long)B * M, cdim, a->inner, st))) return rc;
     const float scale = (float)pow((double)a->dh, -0.5);             // dim_head ** -0.5, a Python float multiplied into an fp32 tensor
     const size_t lds = (size_t)2 * 32 * (a->dh + 1) * sizeof(float);
     hipLaunchKernelGGL(xa_core_kernel, dim3((unsigned)ceil_div(N, 128), (unsigned)(B * a->heads)), dim3(256), lds, st,
                        (const float *)q, (const float *)k, (const float *)v, mask, o, N, M, a->heads, a->dh, a->inner, scale);
     LAUNCH_CHECK();
-    return xa_linear(o, a->inner, a->wo, a->bo, out, a->qdim, (long)B * N, a->inner, a->qdim, st);
+    return xa_linear(o, a->inner, a->w[XA_WO], a->w[XA_BO], out, a->qdim, (long)B * N, a->inner, a->qdim, st);
 }
 
 }  // extern "C"

@@ -38,12 +38,9 @@ class Dgcnn(nn.Module):
         self.conv_4 = nn.Linear(128 * 2, 256, bias=False)
         self.conv_5 = nn.Linear(512, size_latent, bias=False)
         self._handle = None
-        self._bound_key = None
+        self._binder = N.ParamBinder("surfd_dgcnn_set_param", "surfd_dgcnn_finalize")
 
     # ---- native handle ----------------------------------------------------------------------------
-    def _state_key(self):
-        return tuple((t.data_ptr(), t._version) for t in self.state_dict(keep_vars=True).values())
-
     def _native(self):
         if self.aggreate_ops_local != "max" or self.aggreate_ops_global != "max":
             raise NotImplementedError(
@@ -56,20 +53,7 @@ class Dgcnn(nn.Module):
             h = C.c_void_p()
             N.check(L.surfd_dgcnn_create(self.size_latent, self.k, C.byref(h)))
             self._handle = h
-        key = self._state_key()
-        if self._bound_key != key:
-            st = N.stream()
-            for name, v in self.state_dict(keep_vars=True).items():
-                if name.endswith("num_batches_tracked"):
-                    N.check(L.surfd_dgcnn_set_param(self._handle, name.encode(), None, N.shape_arr(()), 0, st))
-                    continue
-                t = v.detach()
-                if t.dtype != torch.float32 or not t.is_contiguous():
-                    t = t.float().contiguous()
-                N.check(L.surfd_dgcnn_set_param(self._handle, name.encode(), N.ptr(t), N.shape_arr(tuple(t.shape)), t.dim(), st))
-            N.check(L.surfd_dgcnn_finalize(self._handle, st))
-            torch.cuda.current_stream().synchronize()          # temporaries made above may be freed now
-            self._bound_key = key
+        self._binder.bind(self, self._handle)
         return L, self._handle
 
     def _check_input(self, x: Tensor) -> Tensor:

@@ -27,6 +27,10 @@ from .cbndec import _register
 from .spec import UNetConfig, unet_param_spec
 
 
+def _is_unet_key(key: str) -> bool:
+    return key.startswith("Unet.")
+
+
 class MDM(nn.Module):
     def __init__(self, modeltype="", num_actions=9, dropout=0.1, activation="gelu", legacy=False,
                  dataset="deepfasion3d", clip_dim=512, arch="OpenUNet", clip_version=None, **kargs):
@@ -58,14 +62,15 @@ class MDM(nn.Module):
                 t = (torch.rand(shape, generator=g) * 2 - 1) / fan_in ** 0.5
             _register(self, key, t, True)
         self._handle = None
-        self._bound_key = None
+        self._binder = self._new_binder()
 
     def parameters_wo_clip(self):
         return [p for name, p in self.named_parameters() if not name.startswith("clip_model.")]
 
     # ---- native handle -------------------------------------------------------------------------------
-    def _state_key(self):
-        return tuple((v.data_ptr(), v._version) for v in self.parameters())
+    @staticmethod
+    def _new_binder():
+        return N.ParamBinder("surfd_unet_set_param", "surfd_unet_finalize", wanted=_is_unet_key)
 
     def _native(self):
         first = next(self.parameters())
@@ -80,19 +85,7 @@ class MDM(nn.Module):
             h = C.c_void_p()
             N.check(L.surfd_unet_create(C.byref(cfg), C.byref(h)))
             self._handle = h
-        key = self._state_key()
-        if self._bound_key != key:
-            st = N.stream()
-            for k, v in self.state_dict(keep_vars=True).items():
-                if not k.startswith("Unet."):
-                    continue
-                t = v.detach()
-                if t.dtype != torch.float32 or not t.is_contiguous():
-                    t = t.float().contiguous()
-                N.check(L.surfd_unet_set_param(self._handle, k.encode(), N.ptr(t), N.shape_arr(tuple(t.shape)), t.dim(), st))
-            N.check(L.surfd_unet_finalize(self._handle, st))
-            torch.cuda.current_stream().synchronize()
-            self._bound_key = key
+        self._binder.bind(self, self._handle)
         return L, self._handle
 
     def replica(self) -> "MDM":
@@ -102,7 +95,7 @@ class MDM(nn.Module):
         import copy
         other = copy.copy(self)              # shallow: _parameters / _buffers dicts are shared, not copied
         other._handle = None
-        other._bound_key = None
+        other._binder = self._new_binder()       # its own bound key over the shared tensors
         return other
 
     def set_precision(self, mode: str) -> None:

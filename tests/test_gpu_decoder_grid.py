@@ -144,6 +144,44 @@ def test_decoder_saturation_edge_cases():
     assert (ng.cpu()[(refg.abs().sum(-1) == 0)] == 0).all()
 
 
+def test_decoder_rebinds_after_weight_updates():
+    """The handle's copy follows the module: a weight written in place, a CBN buffer written in place and a parameter replaced
+    by attribute assignment each give what a fresh module loaded with the changed state_dict gives, bit for bit."""
+    from surfd_amd.cbndec import CbnDecoder
+    g = torch.Generator().manual_seed(11)
+    lat = (torch.randn(1, 32, generator=g) * 0.8).cuda()
+    pts = (torch.rand(256, 3, generator=g) * 2 - 1).cuda()
+
+    def run(dec):
+        dec.bind_latents(lat)
+        return dec._logits_xyz(pts, 0), dec.udf(pts, 0)
+
+    def fresh(sd):
+        f = CbnDecoder(63, 32, 512, 5)
+        f.load_state_dict({k: v.detach().cpu().clone() for k, v in sd.items()}, strict=True)
+        return run(f.cuda().eval())
+
+    dec, _ = _decoder(32)
+    block = getattr(dec.decoder.blocks, "1")
+    prev = run(dec)
+
+    def step():
+        nonlocal prev
+        got, want = run(dec), fresh(dec.state_dict())
+        assert not torch.equal(got[0], prev[0])
+        assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+        prev = got
+
+    with torch.no_grad():
+        block.fc_0.weight.mul_(1.25)
+    step()
+    with torch.no_grad():
+        block.bn_1.bn.running_mean.add_(0.25)
+    step()
+    block.fc_1.bias = torch.nn.Parameter(torch.randn(512, generator=g).cuda() * 0.1)
+    step()
+
+
 def test_decoder_emb_and_reference_closure():
     from surfd_amd.cbndec import CoordsEncoder
     from surfd_amd.meshudf import sample_grads, sample_udf

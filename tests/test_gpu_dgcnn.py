@@ -337,3 +337,28 @@ def test_one_handle_across_sizes():
         assert torch.equal(_bits(d), _bits(fd)) and torch.equal(i, fi), (B, N, n2)
         outs.append((lat, x1234))
     assert torch.equal(_bits(outs[0][0]), _bits(outs[3][0])) and torch.equal(_bits(outs[0][1]), _bits(outs[3][1]))
+
+
+def test_rebinds_after_weight_updates():
+    """The handle's copy follows the module: a parameter written in place, a BUFFER written in place (the key has to see
+    buffers) and a load_state_dict each give what a fresh module loaded with the changed state_dict gives, bit for bit."""
+    def fresh(sd):
+        return _module({k: v.detach().cpu().clone() for k, v in sd.items()}, 32, 20)
+
+    x = R.surface_cloud(2, 64, seed=5).cuda()
+    m = _module(synth.synth_dgcnn_state_dict(32, seed=0), 32, 20)
+    y0 = m(x)
+    with torch.no_grad():
+        m.conv_1.weight.mul_(1.5)
+    y1 = m(x)
+    assert not torch.equal(y1, y0)
+    assert torch.equal(y1, fresh(m.state_dict())(x))
+    with torch.no_grad():
+        m.bn_3.running_var.add_(0.5)
+    y2 = m(x)
+    assert not torch.equal(y2, y1)
+    assert torch.equal(y2, fresh(m.state_dict())(x))
+    m.load_state_dict(synth.synth_dgcnn_state_dict(32, seed=1), strict=True)
+    y3 = m(x)
+    assert not torch.equal(y3, y2)
+    assert torch.equal(y3, fresh(synth.synth_dgcnn_state_dict(32, seed=1))(x))

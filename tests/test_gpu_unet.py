@@ -839,3 +839,33 @@ def test_fused_loop_is_bit_stable_run_to_run(B, L, wide):
         assert torch.isfinite(first).all()
     finally:
         model.set_wide(0)
+
+
+def test_rebinds_after_weight_updates():
+    """The handle's copy follows the module, in every execution context: after a convolution weight and a GroupNorm vector were
+    written in place, the model AND a replica made (and run) before the change give what a fresh model loaded with the changed
+    state_dict gives, bit for bit."""
+    from surfd_amd.mdm import MDM, get_model_args, load_model_wo_clip
+
+    def fresh(sd):
+        m = MDM(**get_model_args(_args("no_cond")))
+        load_model_wo_clip(m, {k: v.detach().cpu().clone() for k, v in sd.items()})
+        m.to("cuda")
+        m.eval()                                   # MDM.train returns None, as the reference's does
+        return m
+
+    g = torch.Generator().manual_seed(17)
+    x = torch.randn(1, 1, 8, generator=g).cuda()
+    t = torch.tensor([321]).cuda()
+    model = fresh(_model("no_cond")[2])
+    rep = model.replica()
+    y0, r0 = model(x, t, y={}), rep(x, t, y={})
+    assert torch.equal(y0, r0)
+    live = model.state_dict(keep_vars=True)
+    with torch.no_grad():
+        live["Unet.input_blocks.1.0.in_layers.2.weight"].mul_(1.5)
+        live["Unet.input_blocks.1.0.out_layers.0.weight"].add_(0.25)
+    y1, r1 = model(x, t, y={}), rep(x, t, y={})
+    assert not torch.equal(y1, y0)
+    want = fresh(model.state_dict())(x, t, y={})
+    assert torch.equal(y1, want) and torch.equal(r1, want)
