@@ -77,6 +77,10 @@ def parse(argv=None):
     ap.add_argument("--voxel_iou", type=int, default=0, metavar="R", help="--paired: also score volumetric IoU on an R^3 grid (0 = off)")
     ap.add_argument("--voxel_bounds", type=float, nargs=2, default=(-1.0, 1.0), metavar=("LO", "HI"))
     ap.add_argument("--voxel_mode", choices=("surface", "solid", "winding", "points"), default="surface")
+    ap.add_argument("--winding_accel", choices=("exact", "bvh"), default="exact",
+                    help="--voxel_mode winding: the exact sum over all faces, or the fast approximation (far parts of the mesh as dipoles)")
+    ap.add_argument("--winding_beta", type=float, default=2.0, metavar="B",
+                    help="--winding_accel bvh: a part of the mesh is approximated from B times its radius on (>= 1; larger is closer to exact)")
     ap.add_argument("--normal_consistency", action="store_true", help="--paired: also score the normal consistency of every pair")
     ap.add_argument("--normals_k", type=int, default=16, metavar="K", help="--normal_consistency: neighbours per estimated normal (3 .. 64)")
     ap.add_argument("--self_intersections", action="store_true", help="--paired: also report the self-intersections of every generated mesh")
@@ -177,7 +181,7 @@ def voxel_scores(gen_items, ref_items, a):
             elif a.voxel_mode == "surface":
                 grids.append(voxelize.voxelize_surface(v, f.cuda(), R, bounds))
             elif a.voxel_mode == "winding":
-                grids.append(voxelize.voxelize_winding(v, f.cuda(), R, bounds))
+                grids.append(voxelize.voxelize_winding(v, f.cuda(), R, bounds, accel=a.winding_accel, beta=a.winding_beta))
             else:
                 grid, odd = voxelize.voxelize_solid(v, f.cuda(), R, bounds)
                 grids.append(grid)
@@ -237,6 +241,10 @@ def run(a):
         raise SystemExit("--collisions scores pairs: it needs --paired")
     if a.voxel_iou and not a.paired:
         raise SystemExit("--voxel_iou scores pairs: it needs --paired")
+    if a.winding_accel != "exact" and not (a.voxel_iou and a.voxel_mode == "winding"):
+        raise SystemExit("--winding_accel chooses how the winding number is summed: it needs --voxel_iou R --voxel_mode winding")
+    if not a.winding_beta >= 1.0:
+        raise SystemExit(f"--winding_beta must be a number >= 1 (or inf), got {a.winding_beta}")
     if a.normal_consistency and not a.paired:
         raise SystemExit("--normal_consistency scores pairs: it needs --paired")
     if a.normal_consistency and not (cloudnormals.K_MIN <= a.normals_k <= min(cloudnormals.K_MAX, a.num_points)):
@@ -264,6 +272,8 @@ def run(a):
         out["mean"] = {k: float(np.mean(r[k], dtype=np.float64)) for k in keys}
         if a.voxel_iou:
             out["options"].update(voxel_iou=a.voxel_iou, voxel_bounds=list(a.voxel_bounds), voxel_mode=a.voxel_mode)
+            if a.winding_accel != "exact":
+                out["options"].update(winding_accel=a.winding_accel, winding_beta=a.winding_beta)
             scores, skipped = voxel_scores(gen_items, ref_items, a)
             for name, s in scores.items():
                 out["items"][name].update(s)

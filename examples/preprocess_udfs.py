@@ -62,7 +62,25 @@ def parse(argv=None):
     ap.add_argument("--num_queries_on_surface", type=int, default=10_000, help="with --signed: on-surface queries put in front")
     ap.add_argument("--accel", choices=("tiles", "bvh"), default="tiles",
                     help="how the mesh is searched: its tiles, or the box hierarchy (the same bytes; faster for the rays of --signed)")
+    ap.add_argument("--winding_accel", choices=("exact", "bvh"), default="exact",
+                    help="with --signed --sign winding: the exact sum over all faces, or the fast approximation (far parts of the mesh as dipoles)")
+    ap.add_argument("--winding_beta", type=float, default=2.0, metavar="B",
+                    help="--winding_accel bvh: a part of the mesh is approximated from B times its radius on (>= 1; larger is closer to exact)")
     return ap.parse_args(argv)
+
+
+def winding_sdf_from_mesh(vs, ts, a, orient):
+    """meshprep.compute_sdf_from_mesh(sign="winding") with the winding numbers of a WindingScene of the driver's own (the fast
+    path): the same steps and the same random numbers in the same order"""
+    from surfd_amd.winding import WindingScene
+    cloud = meshprep.sample_points_uniformly(vs, ts, a.num_surface_points)
+    queries = meshprep.sample_points_around_pcd(cloud, [0.003, 0.01, 0.1], list(a.num_queries_per_std), (-1.0, 1.0), vs.device)
+    scene = WindingScene(vs, ts, orient=orient, accel=a.winding_accel, beta=a.winding_beta)
+    sdf, gradients = meshprep.compute_sdf_and_gradients(scene, None, queries, sign="winding")
+    on_surface = meshprep.sample_points_uniformly(vs, ts, a.num_queries_on_surface)
+    n = a.num_queries_on_surface
+    return (torch.cat([on_surface, queries]), torch.cat([sdf.new_zeros(n), sdf.clamp(-a.max_dist, a.max_dist)]),
+            torch.cat([gradients.new_zeros(n, 3), gradients]))
 
 
 def list_inputs(inputs):
@@ -92,10 +110,13 @@ def prepare_one(path, a):
             if a.weld:                                         # the sign comes from the welded mesh: the same surface, shared indices
                 vs, ts, _ = meshtopo.weld_vertices(vd, td)
             extra["orient"] = "outward"
-        coords, labels, gradients = meshprep.compute_sdf_from_mesh(vs, ts, num_surface_points=a.num_surface_points,
-                                                                   num_queries_on_surface=a.num_queries_on_surface,
-                                                                   num_queries_per_std=list(a.num_queries_per_std), max_dist=a.max_dist,
-                                                                   sign=a.sign, **extra)
+        if a.winding_accel != "exact":
+            coords, labels, gradients = winding_sdf_from_mesh(vs, ts, a, extra.get("orient", False))
+        else:
+            coords, labels, gradients = meshprep.compute_sdf_from_mesh(vs, ts, num_surface_points=a.num_surface_points,
+                                                                       num_queries_on_surface=a.num_queries_on_surface,
+                                                                       num_queries_per_std=list(a.num_queries_per_std), max_dist=a.max_dist,
+                                                                       sign=a.sign, **extra)
     else:
         coords, labels, gradients = meshprep.compute_udf_from_mesh(vd, td, num_surface_points=a.num_surface_points,
                                                                    num_queries_per_std=list(a.num_queries_per_std), max_dist=a.max_dist,
@@ -115,6 +136,10 @@ def run(a):
         raise SystemExit("--sign chooses the sign of --signed items: it needs --signed")
     if a.orient and a.sign != "winding":
         raise SystemExit("--orient re-orients the faces for the winding number: it needs --signed --sign winding")
+    if a.winding_accel != "exact" and a.sign != "winding":
+        raise SystemExit("--winding_accel chooses how the winding number is summed: it needs --signed --sign winding")
+    if not a.winding_beta >= 1.0:
+        raise SystemExit(f"--winding_beta must be a number >= 1 (or inf), got {a.winding_beta}")
     if a.weld and not a.orient:
         raise SystemExit("--weld welds the mesh whose topology --orient uses: it needs --orient")
     if not torch.cuda.is_available():

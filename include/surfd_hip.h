@@ -624,6 +624,36 @@ int surfd_winding_num_triangles(const surfd_winding *m);
  * a no-op.  The handle keeps the call's partial sums in a workspace of its own (at most 256 MiB; the points are walked in slabs):
  * a handle serves one stream and one host thread at a time. */
 int surfd_winding_eval(surfd_winding *m, const float *points, int64_t Q, int flags, double *w, surfd_stream s);
+#define SURFD_WINDING_COUNT_VISITS 2   /* flags bit 1 of surfd_winding_eval_fast: count cluster and triangle terms (surfd_winding_visits) */
+/* no reference counterpart; the tree of Barill et al.'s fast winding numbers (libigl's fast_winding_number precomputation), dipole only:
+ * the box hierarchy of csrc/meshbvh.hip over the handle's triangles (as surfd_rayscene_build_bvh), and for every child slot
+ * of every node a record of seven doubles: the area-weighted centre p of what the child holds, its vector area N and the squared
+ * distance R2 from p to the farthest corner of the child's box.  The sums behind the records are hierarchical and fixed in the
+ * header of csrc/winding.hip; tests/winding_fast_ref.py gives the same bits.  The handle's triangle records and their order do
+ * not change.  Idempotent.  host-sync. */
+int surfd_winding_build_bvh(surfd_winding *m, surfd_stream s);
+/* no reference counterpart; libigl's fast_winding_number(..., beta) with expansion order 0 (the dipole):
+ * AN APPROXIMATION of surfd_winding_eval whose cost per point is logarithmic in F: points[Q,3] fp32 -> w[Q] fp64, both on the
+ * device.  Every point walks the tree on its own; a child whose centre is farther than beta times its radius (d2 > beta^2 R2)
+ * contributes ((N . r) / (d2 sqrt(d2))) / 2 with r = p - point and is not entered, every other leaf contributes the exact terms
+ * of its triangles; w = (the sum in walk order) / (2 pi).  beta: a finite number >= 1 or +inf (every triangle exactly, in the
+ * tree's order); anything else is SURFD_ERR_ARG.  The bits of w[n] depend on the point, the mesh and beta alone, and differ from
+ * the restatement only through the exact terms' atan2 (|w - w_ref| <= max(T, 1) 2^-50, T the point's number of terms).  Measured
+ * error against surfd_winding_eval: DESIGN.md section 8.16.  flags: SURFD_WINDING_COUNT_VISITS.  A point that holds a NaN or an
+ * Inf gets w = NaN.  0 <= Q < 2^31; Q = 0 is a no-op.  Without surfd_winding_build_bvh: SURFD_ERR_STATE, never a fallback.
+ * Does not sync and keeps nothing in the handle's workspace. */
+int surfd_winding_eval_fast(surfd_winding *m, const float *points, int64_t Q, double beta, int flags, double *w, surfd_stream s);
+/* no reference counterpart; a measurement of the fast path:
+ * the cluster terms and triangle terms, summed over the points, of the last surfd_winding_eval_fast with
+ * SURFD_WINDING_COUNT_VISITS, to host memory.  host-sync.  Measurement only. */
+int surfd_winding_visits(surfd_winding *m, int64_t *cluster_terms, int64_t *triangle_terms, surfd_stream s);
+/* no reference counterpart; the hierarchy's shape, for tests:
+ * as surfd_mesh_bvh_info */
+int surfd_winding_bvh_info(const surfd_winding *m, int *levels, int *leaves, int *nodes, int32_t *level_sizes, int capacity);
+/* no reference counterpart; the hierarchy's content, for tests:
+ * as surfd_mesh_bvh_read, and records[nodes,4,7] fp64 (nullable): (p.x, p.y, p.z, N.x, N.y, N.z, R2) of every child slot,
+ * (0, 0, 0, 0, 0, 0, -1) for a slot that holds nothing */
+int surfd_winding_bvh_read(const surfd_winding *m, float *boxes, int32_t *leaf_triangles, double *records, surfd_stream s);
 
 /* ------------------------------------------------------------------------------------ */
 /* Mesh topology: edges and their valences, face neighbours, connected components,        */

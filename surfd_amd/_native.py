@@ -159,6 +159,11 @@ _SIGS = {
     "surfd_winding_destroy": (None, [_P]),
     "surfd_winding_num_triangles": (C.c_int, [_P]),
     "surfd_winding_eval": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P]),
+    "surfd_winding_build_bvh": (C.c_int, [_P, _P]),
+    "surfd_winding_eval_fast": (C.c_int, [_P, _P, C.c_int64, C.c_double, C.c_int, _P, _P]),
+    "surfd_winding_visits": (C.c_int, [_P, c_i64p, c_i64p, _P]),
+    "surfd_winding_bvh_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int32), C.c_int]),
+    "surfd_winding_bvh_read": (C.c_int, [_P, _P, _P, _P, _P]),
     "surfd_meshtopo_create": (C.c_int, [_P, C.c_int, C.c_int, _P, C.POINTER(_P)]),
     "surfd_meshtopo_destroy": (None, [_P]),
     "surfd_meshtopo_counts": (C.c_int, [_P, c_i64p, c_i64p, c_i64p, c_i64p]),

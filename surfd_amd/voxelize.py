@@ -170,19 +170,23 @@ def voxelize_solid(vertices: Tensor, faces: Tensor, resolution: int = 32, bounds
     return grid, ({"odd_columns": c[0], "dropped": c[1]} if return_counts else c[0])
 
 
-def voxelize_winding(vertices: Tensor, faces: Tensor, resolution: int = 32, bounds=(-1.0, 1.0), threshold: float = 0.5) -> VoxelGrid:
+def voxelize_winding(vertices: Tensor, faces: Tensor, resolution: int = 32, bounds=(-1.0, 1.0), threshold: float = 0.5,
+                     accel: str = "exact", beta: float = 2.0) -> VoxelGrid:
     """The voxels whose centre lies inside the mesh by its generalized winding number: |w| >= ``threshold`` (csrc/winding.hip
     through surfd_amd/winding.py).  A hole costs only its own solid angle, so a mesh with small holes fills as the closed one
     does, where voxelize_solid leaks along every column through a hole.  The centres are
     lo + (arange(R, dtype=float32) + 0.5) * ((hi - lo) / R), built in torch on the device; R^3 x F terms, nothing is culled.  The
     faces must be consistently oriented (all outwards or all inwards); surface voxels are not OR-ed in.  Indices outside
-    [0, V) and vertices that are not finite are refused, not dropped."""
-    from .winding import WindingScene, _check_threshold
+    [0, V) and vertices that are not finite are refused, not dropped.  ``accel="bvh"`` takes the winding numbers from the fast
+    path with ``beta`` (an approximation whose cost is logarithmic in F; WindingScene)."""
+    from .winding import WindingScene, _check_beta, _check_threshold, _check_winding_accel
     R, bounds = _check_grid(resolution, bounds)
     threshold = _check_threshold(threshold)
+    _check_winding_accel(accel)
+    _check_beta(beta)
     if not isinstance(vertices, Tensor) or not isinstance(faces, Tensor):
         raise TypeError("vertices and faces must be tensors")
-    scene = WindingScene(vertices, faces)
+    scene = WindingScene(vertices, faces, accel=accel, beta=beta)
     lo, hi = bounds
     with torch.cuda.device(scene.device):
         c = lo + (torch.arange(R, dtype=torch.float32, device=scene.device) + 0.5) * ((hi - lo) / R)
