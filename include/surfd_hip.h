@@ -828,6 +828,13 @@ int surfd_cloud_nn(const float *a, const float *b, int B, int Na, int Nb, float 
  * The other direction is a second call with the roles swapped. */
 int surfd_cloud_nn_matrix(const float *a, int M, int Na, const float *b, int R, int Nb, float tau2,
                           float *mean, int32_t *below, surfd_stream s);
+/* no reference counterpart; the launch plan surfd_cloud_nn_matrix takes for M query clouds of Na points and R candidate clouds:
+ * P = 1, 2, 4, 8 query points per lane for Na <= 256, <= 512, <= 1024, above; query_tiles = ceil(Na / (256 P)) register tiles
+ * of the query cloud (above 1 they are reloaded per candidate cloud); want = min(R, max(1, ceil(2048 / M))), span = ceil(R / want)
+ * candidate clouds per workgroup, S = ceil(R / span) workgroups per query cloud (the last range may be shorter).  The same
+ * checks of M, Na, R and the same return codes as the launch; no device call; every out pointer may be NULL.  For tests and
+ * tools that must know which path a shape takes. */
+int surfd_cloud_nn_matrix_plan(int M, int Na, int R, int *P, int *S, int *span, int *query_tiles);
 
 /* ------------------------------------------------------------------------------------ */
 /* Farthest point sampling: K points of a cloud, each the one farthest from every pick    */

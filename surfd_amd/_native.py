@@ -184,6 +184,7 @@ _SIGS = {
     "surfd_meshclean_fill_small_holes": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, c_i64p, _P]),
     "surfd_cloud_nn": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "surfd_cloud_nn_matrix": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_float, _P, _P, _P]),
+    "surfd_cloud_nn_matrix_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "surfd_cloud_fps_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "surfd_cloud_fps": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P]),
     "surfd_cloud_normals": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P]),

@@ -191,22 +191,46 @@ int surfd_cloud_nn(const float *a, const float *b, int B, int Na, int Nb, float 
     return SURFD_OK;
 }
 
-int surfd_cloud_nn_matrix(const float *a, int M, int Na, const float *b, int R, int Nb, float tau2, float *mean, int32_t *below,
-                          surfd_stream s) {
+// the argument checks of surfd_cloud_nn_matrix and its launch plan, on the host alone: P query points per lane, S ranges of
+// `span` candidate clouds per query cloud (about CN_TARGET_WGS workgroups over the chip, whole clouds per range), nqt register
+// tiles of 256 P query points
+struct CnPlan { int P, S, span, nqt; };
+static int cn_matrix_plan(int M, int Na, int R, int Nb, CnPlan *plan) {
     if (M < 1 || R < 1 || Na < 1 || Nb < 1)
         SURFD_FAIL(SURFD_ERR_ARG, "surfd_cloud_nn_matrix: M = %d, Na = %d, R = %d, Nb = %d must be positive", M, Na, R, Nb);
-    if (!a || !b) SURFD_FAIL(SURFD_ERR_ARG, "surfd_cloud_nn_matrix: null a or b");
-    if (!mean) SURFD_FAIL(SURFD_ERR_ARG, "surfd_cloud_nn_matrix: null mean");
     if (M > (1 << 20) || R > (1 << 20) || Na > (1 << 24) || Nb > (1 << 28))
         SURFD_FAIL(SURFD_ERR_UNSUPPORTED, "surfd_cloud_nn_matrix: M = %d, Na = %d, R = %d, Nb = %d is beyond the supported size", M, Na, R, Nb);
-    // ranges of candidate clouds per query cloud: about CN_TARGET_WGS workgroups over the chip, whole clouds per range
     const int want = std::min<long>(R, std::max<long>(1, ceil_div<long>(CN_TARGET_WGS, M)));
-    const int span = ceil_div(R, want);
-    const int S = ceil_div(R, span);
+    plan->span = ceil_div(R, want);
+    plan->S = ceil_div(R, plan->span);
+    plan->P = Na <= 256 ? 1 : Na <= 512 ? 2 : Na <= 1024 ? 4 : CN_PMAX;
+    plan->nqt = ceil_div(Na, 256 * plan->P);
+    return SURFD_OK;
+}
+
+int surfd_cloud_nn_matrix_plan(int M, int Na, int R, int *P, int *S, int *span, int *query_tiles) {
+    CnPlan plan;
+    const int rc = cn_matrix_plan(M, Na, R, 1, &plan);
+    if (rc != SURFD_OK) return rc;
+    if (P) *P = plan.P;
+    if (S) *S = plan.S;
+    if (span) *span = plan.span;
+    if (query_tiles) *query_tiles = plan.nqt;
+    return SURFD_OK;
+}
+
+int surfd_cloud_nn_matrix(const float *a, int M, int Na, const float *b, int R, int Nb, float tau2, float *mean, int32_t *below,
+                          surfd_stream s) {
+    CnPlan plan;
+    const int rc = cn_matrix_plan(M, Na, R, Nb, &plan);
+    if (rc != SURFD_OK) return rc;
+    if (!a || !b) SURFD_FAIL(SURFD_ERR_ARG, "surfd_cloud_nn_matrix: null a or b");
+    if (!mean) SURFD_FAIL(SURFD_ERR_ARG, "surfd_cloud_nn_matrix: null mean");
+    const int S = plan.S, span = plan.span;
     hipStream_t st = as_stream(s);
-    if (Na <= 256) cn_matrix_launch<1>(a, M, Na, b, R, Nb, S, span, tau2, mean, below, st);
-    else if (Na <= 512) cn_matrix_launch<2>(a, M, Na, b, R, Nb, S, span, tau2, mean, below, st);
-    else if (Na <= 1024) cn_matrix_launch<4>(a, M, Na, b, R, Nb, S, span, tau2, mean, below, st);
+    if (plan.P == 1) cn_matrix_launch<1>(a, M, Na, b, R, Nb, S, span, tau2, mean, below, st);
+    else if (plan.P == 2) cn_matrix_launch<2>(a, M, Na, b, R, Nb, S, span, tau2, mean, below, st);
+    else if (plan.P == 4) cn_matrix_launch<4>(a, M, Na, b, R, Nb, S, span, tau2, mean, below, st);
     else cn_matrix_launch<CN_PMAX>(a, M, Na, b, R, Nb, S, span, tau2, mean, below, st);
     LAUNCH_CHECK();
     return SURFD_OK;

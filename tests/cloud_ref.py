@@ -5,6 +5,7 @@ output: numpy / torch-CPU restatements.
                     d2 = (dx dx + dy dy) + dz dz, one rounding per operation) with (d2, index) selection: lower index on ties
   nn_f64            the same mathematics in fp64 (the truth the derived bounds are about)
   mean_f32 / mean_f64, matrix_f32 / matrix_f64     the directed Chamfer means of a pair of clouds / of two sets
+  mean_kernel_order, matrix_kernel_order           the same means in the fp64 summation order the kernel documents: its bits
   mmd_cov_f64, one_nna_f64                         the set metrics, written as plain loops
   row_gaps          how clearly every arg-min of a matrix is decided
   shell_cloud, torus_cloud, family, lattice_cloud, random_cloud     deterministic test clouds
@@ -74,6 +75,43 @@ def matrix_f32(A, B, tau2=None):
     res = [[mean_f32(a, b, tau2) for b in B] for a in A]
     mean = np.array([[r[0] for r in row] for row in res], np.float32)
     return mean, (None if tau2 is None else np.array([[r[1] for r in row] for row in res], np.int64))
+
+
+def mean_kernel_order(d2):
+    """d2 [Na] float32 -> float32: the mean in the summation order csrc/cloudnn.hip documents.  Lane t of 256 adds d2[t::256] in
+    ascending order to an fp64 accumulator that starts at 0.0 (a lane whose point lies beyond Na adds 0.0, which changes no
+    accumulator: none is -0.0); each wave of 64 lanes reduces by the xor tree with offsets 32, 16, 8, 4, 2, 1, after which all
+    64 lanes hold one value (asserted); the four waves are added as ((w0 + w1) + w2) + w3; the sum is divided by float(Na) and
+    rounded once to fp32.  The order does not depend on P: for a fixed lane, ascending (tile, p) is ascending index, stride 256."""
+    d2 = np.ascontiguousarray(d2, dtype=np.float32)
+    assert d2.ndim == 1 and len(d2) >= 1
+    na = len(d2)
+    rows = -(-na // 256)
+    padded = np.zeros(rows * 256, np.float64)
+    padded[:na] = d2
+    acc = np.zeros(256, np.float64)
+    for row in padded.reshape(rows, 256):
+        acc = acc + row
+    w = acc.reshape(4, 64)
+    lanes = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        w = w + w[:, lanes ^ o]
+    assert (w == w[:, :1]).all()
+    total = ((w[0, 0] + w[1, 0]) + w[2, 0]) + w[3, 0]
+    return np.float32(total / float(na))
+
+
+def matrix_kernel_order(A, B, tau2=None):
+    """([M, R] float32 means in the kernel's summation order, [M, R] int64 counts of d2 < float32(tau2) or None), on nn_f32"""
+    mean = np.empty((len(A), len(B)), np.float32)
+    below = None if tau2 is None else np.empty((len(A), len(B)), np.int64)
+    for i, a in enumerate(A):
+        for j, b in enumerate(B):
+            d2, _ = nn_f32(a, b)
+            mean[i, j] = mean_kernel_order(d2)
+            if below is not None:
+                below[i, j] = int((d2 < np.float32(tau2)).sum())
+    return mean, below
 
 
 def ulp_distance(x, y):
@@ -188,6 +226,21 @@ def lattice_cloud(B, N, seed):
 def random_cloud(B, N, seed):
     g = torch.Generator().manual_seed(seed)
     return (torch.rand(B, N, 3, generator=g) * 2 - 1).numpy()
+
+
+def wave_order_case():
+    """(a [256, 3], b [1, 3], the mean in the kernel's order, the mean of the exact sum): a cloud on which the association of
+    the four wave sums decides the fp32 result.  b is the origin, so d2 = x^2 exactly: 4 and 2^-22 in wave 0 (lanes 0 and 1),
+    2^-52 twice in wave 2 (lanes 128, 129) and twice in wave 3 (lanes 192, 193).  w0 = 4 + 2^-22, the midpoint of two fp32
+    neighbours; w2 = w3 = 2^-51, half an fp64 ulp of w0.  ((w0 + w1) + w2) + w3 absorbs each half ulp in turn (ties to even:
+    w0 is an even multiple of 2^-50), the sum stays the midpoint and float32 rounds it to even: mean = 4 / 256.  Any order that
+    adds w2 and w3 first, and the exact sum, lie above the midpoint and round up."""
+    a = np.zeros((256, 3), np.float32)
+    a[0, 0], a[1, 0] = 2.0, 2.0 ** -11
+    a[[128, 129, 192, 193], 0] = 2.0 ** -26
+    b = np.zeros((1, 3), np.float32)
+    kernel_order = np.float32(2.0 ** -6)
+    return a, b, kernel_order, np.nextafter(kernel_order, np.float32(1))
 
 
 def self_check_clouds():

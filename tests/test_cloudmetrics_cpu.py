@@ -1,8 +1,10 @@
 """CPU-side checks of the point-cloud metrics (surfd_amd/cloudmetrics.py, csrc/cloudnn.hip): the two exports exist and are
 bound, argument errors are return codes, the kernels are in the code object without spills or scratch, the set metrics give the
 known answers on hand-built matrices (ties included), the normalisations are right on hand-checkable clouds, the module
-refuses what it cannot take, and the yardstick (tests/cloud_ref.py) agrees with itself.  Every test here fails on a tree without
-surfd_amd/cloudmetrics.py or without the surfd_cloud_* symbols."""
+refuses what it cannot take, and the yardstick (tests/cloud_ref.py) agrees with itself; the launch plan the library reports
+(surfd_cloud_nn_matrix_plan) against a table worked out by hand, and the yardstick's restatement of the kernel's summation order
+against its free-order one on every shape the GPU tests use.  Every test here fails on a tree without surfd_amd/cloudmetrics.py
+or without the surfd_cloud_* symbols."""
 import ctypes as C
 import importlib.util
 import os
@@ -18,7 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import cloud_ref as R  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLOUD_EXPORTS = ("surfd_cloud_nn", "surfd_cloud_nn_matrix")
+CLOUD_EXPORTS = ("surfd_cloud_nn", "surfd_cloud_nn_matrix", "surfd_cloud_nn_matrix_plan")
 
 
 @pytest.fixture(scope="module")
@@ -257,3 +259,92 @@ def test_input_checks_before_any_launch(CM):
     with pytest.raises(ValueError, match="f_threshold"):
         CM.chamfer_distance(ok, ok, f_threshold=0.0)
     assert CM._tau2(0.01) == float(np.float32(0.01 * 0.01))
+
+
+# ---- 5. the launch plan ------------------------------------------------------------------------------------------------------------
+def matrix_plan_of(lib, M, Na, Rr):
+    """(P, S, span, query_tiles) as the library reports them"""
+    out = [C.c_int(-1) for _ in range(4)]
+    rc = lib.surfd_cloud_nn_matrix_plan(M, Na, Rr, *[C.byref(v) for v in out])
+    assert rc == 0, (rc, lib.surfd_last_error())
+    return tuple(v.value for v in out)
+
+
+# worked out by hand from the header: P = 1, 2, 4, 8 for Na <= 256, <= 512, <= 1024, above; query_tiles = ceil(Na / (256 P))
+PLAN_OF_NA = {1: (1, 1), 256: (1, 1), 257: (2, 1), 512: (2, 1), 513: (4, 1), 1024: (4, 1), 1025: (8, 1), 2048: (8, 1), 2049: (8, 2),
+              4096: (8, 2), 4097: (8, 3)}
+# want = min(R, max(1, ceil(2048 / M))), span = ceil(R / want), S = ceil(R / span): (M, R) -> (S, span)
+PLAN_OF_SETS = {(5, 7): (7, 1), (2048, 2): (1, 2), (1025, 3): (2, 2), (700, 7): (3, 3), (2049, 5): (1, 5), (3, 2049): (683, 3),
+                (1, 2049): (1025, 2), (1, 4100): (1367, 3)}
+
+
+def test_launch_plan_against_the_table(lib):
+    for Na, (P, tiles) in PLAN_OF_NA.items():
+        for M, Rr in ((1, 1), (700, 7)):
+            got = matrix_plan_of(lib, M, Na, Rr)
+            assert (got[0], got[3]) == (P, tiles), (Na, M, Rr, got)
+    for (M, Rr), (S, span) in PLAN_OF_SETS.items():
+        for Na in (5, 2049):
+            got = matrix_plan_of(lib, M, Na, Rr)
+            assert got[1:3] == (S, span), (M, Rr, Na, got)
+            assert S * span >= Rr and (S - 1) * span < Rr, (M, Rr, S, span)   # the ranges cover every cloud and none is empty
+    # every out pointer may be NULL, on its own and all together
+    assert lib.surfd_cloud_nn_matrix_plan(700, 300, 7, None, None, None, None) == 0
+    for k in range(4):
+        out = [C.c_int(-1) for _ in range(4)]
+        args = [None if n == k else C.byref(v) for n, v in enumerate(out)]
+        assert lib.surfd_cloud_nn_matrix_plan(700, 300, 7, *args) == 0
+        assert [v.value for v in out] == [-1 if n == k else w for n, w in enumerate((2, 3, 3, 1))]
+
+
+def test_launch_plan_refuses_what_the_launch_refuses(lib):
+    p = C.c_void_p(16)                                         # never dereferenced: every launch below fails its checks first
+    prefix = lambda: lib.surfd_last_error().split(b", Nb")[0]
+    cases = [((0, 4, 1), -1), ((1, 0, 1), -1), ((1, 4, 0), -1), ((-2, 4, 1), -1), ((1, -1, 1), -1), ((1, 4, -5), -1),
+             (((1 << 20) + 1, 4, 1), -4), ((1, (1 << 24) + 1, 1), -4), ((1, 4, (1 << 20) + 1), -4)]
+    for (M, Na, Rr), code in cases:
+        out = [C.c_int(-1) for _ in range(4)]
+        assert lib.surfd_cloud_nn_matrix_plan(M, Na, Rr, *[C.byref(v) for v in out]) == code, (M, Na, Rr)
+        said = prefix()
+        assert said.startswith(b"surfd_cloud_nn_matrix: M = %d, Na = %d, R = %d" % (M, Na, Rr)), said
+        assert [v.value for v in out] == [-1] * 4                            # a refusal writes nothing
+        assert lib.surfd_cloud_nn_matrix(p, M, Na, p, Rr, 4, 0.0, p, None, None) == code, (M, Na, Rr)
+        assert prefix() == said
+    # the limits themselves are accepted: want = max(1, ceil(2048 / 2^20)) = 1, so one range of all 2^20 clouds
+    assert matrix_plan_of(lib, 1 << 20, 1 << 24, 1 << 20) == (8, 1, 1 << 20, 1 << 13)
+
+
+# ---- 6. the kernel's summation order, restated, against the free-order restatement -----------------------------------------------------
+GRID_NA = (1, 2, 63, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 2047, 2048, 2049, 4096, 4097)
+GRID_NB = (1, 3, 4, 5, 2047, 2048, 2049, 4097)
+
+
+def test_kernel_order_against_free_order_and_fp64():
+    """what tests/test_gpu_cloudmetrics.py holds the kernel to bit for bit is itself within 1 ulp of the free-order mean and
+    within MEAN_BOUND of the fp64 mathematics, on the whole shape grid of the GPU tests"""
+    worst_ulp, worst_rel = 0, 0.0
+    for Na in GRID_NA:
+        a = R.random_cloud(1, Na, Na)[0]
+        for Nb in GRID_NB:
+            b = R.random_cloud(1, Nb, 7 * Nb + 1)[0]
+            d2, _ = R.nn_f32(a, b)
+            got = R.mean_kernel_order(d2)
+            assert got.dtype == np.float32
+            ulp = int(R.ulp_distance(got, R.mean_f32(a, b)[0]).max())
+            m64 = R.mean_f64(a, b)
+            rel = abs(float(got) - m64) / m64
+            assert ulp <= 1, (Na, Nb, ulp)
+            assert rel <= R.MEAN_BOUND, (Na, Nb, rel / R.U)
+            worst_ulp, worst_rel = max(worst_ulp, ulp), max(worst_rel, rel)
+    print(f"kernel-order mean on {len(GRID_NA) * len(GRID_NB)} cloud pairs: at most {worst_ulp} ulp from the free-order mean, "
+          f"largest relative error against fp64 = {worst_rel / R.U:.3f} u (bound 7 u)")
+    # the order itself where it decides the bits: worked out by hand in wave_order_case's docstring
+    a, b, want, exact = R.wave_order_case()
+    d2, _ = R.nn_f32(a, b)
+    assert sorted(d2[d2 > 0].tolist()) == [2.0 ** -52] * 4 + [2.0 ** -22, 4.0]
+    assert R.mean_kernel_order(d2) == want == np.float32(4 / 256) and exact > want
+    w = [float(d2[k:k + 64].astype(np.float64).sum()) for k in range(0, 256, 64)]     # exact: at most two addends of one size
+    assert np.float32(((w[0] + w[1]) + (w[2] + w[3])) / 256.0) == exact             # another association, another result
+    matrix, below = R.matrix_kernel_order(R.random_cloud(2, 300, 1), R.random_cloud(3, 77, 2), 0.01)
+    assert matrix.shape == below.shape == (2, 3) and matrix.dtype == np.float32 and below.dtype == np.int64
+    assert R.matrix_kernel_order(R.random_cloud(2, 300, 1), R.random_cloud(3, 77, 2))[1] is None
