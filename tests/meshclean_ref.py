@@ -10,7 +10,9 @@ surfd_amd.meshproc in the ORDER-FREE form the device builds, one plain Python lo
     clean_until_stable     meshproc's sequence with the counts that steer it, and the stats the device reports
 
 tests/test_meshclean_cpu.py pins every function here to meshproc bit for bit; tests/test_gpu_meshclean.py pins the device to
-meshproc.  Also here: the meshes both share (shapes()), the smallest at which each rule can go wrong.
+meshproc.  Also here: the meshes both share (shapes()), the smallest at which each rule can go wrong; and, apart from them, the
+meshes at size (big_shapes(): merges across the whole index range, duplicates among thousands of faces) and the families padded(),
+relabelled(), side_by_side() and first_soups().  numpy only, every one seeded.
 """
 import math
 
@@ -244,3 +246,185 @@ def random_soup(rng):
     else:
         f = np.array([rng.choice(nv, size=3, replace=False) for _ in range(nf)])
     return v, f.astype(np.int64)
+
+
+def first_soups(n=400, seed=7):
+    """the first n soups of random_soup(default_rng(seed)): one generator stream, so a shorter list is a prefix of a longer one"""
+    rng = np.random.default_rng(seed)
+    return [random_soup(rng) for _ in range(n)]
+
+
+# ---- meshes at size (big_shapes) and families of small ones (padded, relabelled, side_by_side) -------------------------------------
+TORUS_VERTICES, TORUS_FACES = 96 * 88, 2 * 96 * 88           # raycast_ref.torus(96, 88): 8 448 and 16 896
+SOUP_SHIFT = (-0.25, 0.125, -0.5)
+JITTER = 4e-9                                                # 0.4 of a key: splits a class where a coordinate lies within 0.4 of a rounding edge
+
+
+def unwelded(mesh, seed, shift=(0.0, 0.0, 0.0), jitter=0.0):
+    """every face gets three vertices of its own (V = 3 F), faces and vertex labels shuffled, all coordinates shifted: the copies
+    of one vertex keep equal bits and lie anywhere in the index range.  jitter: each coordinate of each copy moves by 0, +jitter
+    or -jitter"""
+    v, f = _mesh(*mesh)
+    rng = np.random.default_rng(seed)
+    f = f[rng.permutation(len(f))]
+    pts = v[f.reshape(-1)] + np.asarray(shift, dtype=np.float64)
+    if jitter:
+        pts = pts + rng.choice([0.0, jitter, -jitter], size=pts.shape)
+    label = rng.permutation(len(pts))                        # corner c of face k is vertex label[3 k + c]
+    out = np.empty_like(pts)
+    out[label] = pts
+    return out, label.reshape(-1, 3).astype(np.int64)
+
+
+FAN_EXTRA, FAN_NAN, FAN_NAN_FACES = 3000, 500, 40
+FAN_APEX = (0.03125, -0.0625, 0.125)
+
+
+def fan(n=5000, seed=5):
+    """a disc of n triangles round one apex, unwelded (V = 3 n: the apex class has n members over the whole index range, every rim
+    class 2), then FAN_EXTRA finite vertices that no face names (copies of fan corners, so each coincides with a class it must not
+    join), FAN_NAN all-NaN vertices and FAN_NAN_FACES faces that each name one of them, all labels shuffled.  The x keys have both
+    signs, so the vertices that take no part sort between the classes of positive and of negative x; the highest label among them
+    goes to a copy of the rim vertex of the lowest x, the class that follows them in the device's order."""
+    ang = np.arange(n) * (2.0 * np.pi / n)
+    v = np.vstack([[FAN_APEX], np.stack([FAN_APEX[0] + np.cos(ang), FAN_APEX[1] + np.sin(ang), np.full(n, FAN_APEX[2])], axis=1)])
+    k = np.arange(n)
+    sv, sf = unwelded((v, np.stack([np.zeros(n, dtype=np.int64), 1 + k, 1 + (k + 1) % n], axis=1)), seed)
+    rng = np.random.default_rng(seed + 1)
+    extra = sv[rng.integers(0, len(sv), size=FAN_EXTRA)]
+    extra[0] = v[1 + int(np.argmin(v[1:, 0]))]               # the rim vertex of the lowest x
+    extra[1:64] = v[0]                                       # and copies of the apex
+    nan_f = np.stack([rng.integers(0, len(sv), FAN_NAN_FACES), rng.integers(0, len(sv), FAN_NAN_FACES),
+                      len(sv) + FAN_EXTRA + rng.choice(FAN_NAN, FAN_NAN_FACES, replace=False)], axis=1)
+    allv = np.vstack([sv, extra, np.full((FAN_NAN, 3), np.nan)])
+    allf = np.vstack([sf, nan_f])[rng.permutation(n + FAN_NAN_FACES)]
+    perm = rng.permutation(len(allv))                        # vertex i becomes perm[i]
+    top = len(sv) + int(np.argmax(perm[len(sv):]))           # the vertex with the highest label of those that take no part
+    perm[[len(sv), top]] = perm[[top, len(sv)]]
+    out = np.empty_like(allv)
+    out[perm] = allv
+    return out, perm[allf].astype(np.int64)
+
+
+def doubled_sheet(seed=3):
+    """sheet(64) with every face present two or three times (about 3 in 5 twice), each copy rotated by 0, 1 or 2 corners and about 2
+    in 5 reversed, all faces shuffled"""
+    v, f = sheet(64)
+    rng = np.random.default_rng(seed)
+    g = f[np.repeat(np.arange(len(f)), rng.choice([2, 3], size=len(f), p=[0.6, 0.4]))]
+    g = np.take_along_axis(g, (np.arange(3)[None, :] + rng.integers(0, 3, size=(len(g), 1))) % 3, axis=1)
+    rev = rng.random(len(g)) < 0.4
+    g[rev] = g[rev][:, ::-1]
+    return v, g[rng.permutation(len(g))].astype(np.int64)
+
+
+_big = {}
+
+
+def big_shapes():
+    """name -> (vertices, faces): the meshes at size, built once and read-only.  Not part of shapes(): the parametrised tests over
+    every function keep their run time"""
+    if not _big:
+        import raycast_ref
+        torus = raycast_ref.torus(96, 88)
+        assert torus[0].shape == (TORUS_VERTICES, 3) and torus[1].shape == (TORUS_FACES, 3)
+        _big.update(torus_soup=unwelded(torus, 1, SOUP_SHIFT), torus_soup_jitter=unwelded(torus, 1, SOUP_SHIFT, JITTER), fan=fan(),
+                    doubled_sheet=doubled_sheet())
+        for v, f in _big.values():
+            v.setflags(write=False); f.setflags(write=False)
+    return _big
+
+
+def loop_vertices(faces):
+    """the vertices that exactly one border half-edge leaves, ascending"""
+    out, _ = border_out_next(faces)
+    return sorted(u for u in out if out[u] == 1)
+
+
+PAD_SIZES = (255, 256, 257, 65535, 65536, 65537)
+PAD_NAMES = ("octahedron_minus_one", "cube_minus_quad")
+
+
+def padded(name, V, top=True, split=False):
+    """(vertices, faces, new): a toy solid of shapes() inside V vertices, vertex i of the solid as new[i], every other vertex an
+    unreferenced (0, 0, 0).  top: the solid takes the highest labels, the vertices of its border loop V - 1, V - 2, ... and the
+    others below them; not top: the lowest labels, the loop first.  The loop's vertices keep their order among themselves, so the
+    caps of the padded solid are the caps of the solid, re-indexed: same rows, same rotation, same order.
+    split (with top): the loop stays at the top and the other vertices go to 0, 1, ... except one, m, which lies HALF THE KEY RANGE
+    below a loop vertex L with which it shares a neighbour o among the others: at new[L] - 2^(b - 1), b the bits of an index
+    below V.  The edges (L, o) and (m, o) then differ in the highest bit of the hole pass's sort key alone, and the faces are
+    re-ordered so that a half-edge of (m, o) lies between the two of (L, o): a stable sort that left that bit out would part
+    them.  (V = 2^k + 1: only V - 1 has that bit and no such pair exists; m stays with the others.)"""
+    v, f = shapes()[name]
+    loop = loop_vertices(f)
+    rest = [i for i in range(len(v)) if i not in loop]
+    new = np.empty(len(v), dtype=np.int64)
+    if top and split:
+        bits = 1
+        while (1 << bits) < V:
+            bits += 1
+        edges = {frozenset(e) for t in f.tolist() for e in ((t[0], t[1]), (t[1], t[2]), (t[2], t[0]))}
+        L, m, o = next((L, m, o) for L in loop[::-1] for m in rest for o in rest if frozenset((L, o)) in edges and frozenset((m, o)) in edges)
+        with_L = [k for k, t in enumerate(f.tolist()) if L in t and o in t]
+        with_m = [k for k, t in enumerate(f.tolist()) if m in t and o in t]
+        first = ([k for k in with_L if k not in with_m] + with_L)[0]
+        second = [k for k in with_m if k != first][0]
+        f = f[[first, second] + [k for k in range(len(f)) if k not in (first, second)]]
+        new[loop] = np.arange(V - len(loop), V)
+        others = [i for i in rest if i != m]
+        new[others] = np.arange(len(others))
+        new[m] = max(new[L] - (1 << (bits - 1)), len(others))
+        assert new[m] < V - len(loop)
+    elif top:
+        new[rest] = np.arange(V - len(v), V - len(loop))
+        new[loop] = np.arange(V - len(loop), V)
+    else:
+        new[loop] = np.arange(len(loop))
+        new[rest] = np.arange(len(loop), len(v))
+    out = np.zeros((V, 3), dtype=np.float64)
+    out[new] = v
+    return out, new[f], new
+
+
+def relabelled(name, seed):
+    """a toy solid of shapes() under a seeded random permutation of its vertex labels"""
+    v, f = shapes()[name]
+    perm = np.random.default_rng(seed).permutation(len(v))
+    out = np.empty_like(v)
+    out[perm] = v
+    return out, perm[f]
+
+
+RELABEL_SEEDS = {"cube_minus_quad": 64, "octahedron_minus_one": 16}
+
+
+def relabellings():
+    """[(name, seed, vertices, faces)]: cube_minus_quad under 64 permutations and octahedron_minus_one under 16"""
+    return [(name, seed) + relabelled(name, seed) for name in sorted(RELABEL_SEEDS) for seed in range(RELABEL_SEEDS[name])]
+
+
+def loop_pattern(faces):
+    """the rank pattern of the one small loop of a toy solid: the ranks of its vertices among themselves, listed along the border
+    from the smallest (which has rank 0).  A 4-loop has 6 patterns, a 3-loop 2."""
+    out, nxt = border_out_next(faces)
+    loop = [min(u for u in out if out[u] == 1)]
+    while nxt[loop[-1]] != loop[0]:
+        loop.append(nxt[loop[-1]])
+    return tuple(sorted(loop).index(u) for u in loop)
+
+
+def side_by_side(meshes, seed=None, gap=4.0):
+    """the meshes as disjoint components of one, component k moved by k gap along x so that no two vertices coincide; with a seed
+    all vertex labels are shuffled, so the loops' vertices interleave"""
+    vs, fs, base = [], [], 0
+    for k, (v, f) in enumerate(meshes):
+        vs.append(np.asarray(v, dtype=np.float64) + np.array([k * gap, 0.0, 0.0]))
+        fs.append(np.asarray(f, dtype=np.int64) + base)
+        base += len(v)
+    v, f = np.vstack(vs), np.vstack(fs)
+    if seed is None:
+        return v, f
+    perm = np.random.default_rng(seed).permutation(len(v))
+    out = np.empty_like(v)
+    out[perm] = v
+    return out, perm[f]
