@@ -67,6 +67,10 @@ def parse(argv=None):
     ap.add_argument("--device_clean", action="store_true",
                     help="open meshes: the far-face filter and the cleaning (merge, duplicate and flat faces, small holes) on the GPU too "
                          "(surfd_amd.meshclean: the same mesh); implies --device_post")
+    ap.add_argument("--simplify_cells", type=int, default=None, metavar="K",
+                    help="make the mesh smaller on the GPU before it is written: vertex clustering on a grid of K cells along the largest extent, "
+                         "one quadric representative per occupied cell (surfd_amd.meshsimplify); needs --device_clean (open meshes) or "
+                         "--watertight --device_mc")
     ap.add_argument("--respacing", default="", help="e.g. ddim50 for a quick run (the reference always runs 1000 steps)")
     ap.add_argument("--seed", type=int, default=10)
     ap.add_argument("--synthetic", action="store_true", help="create synthetic checkpoints under --output_dir and use them")
@@ -77,7 +81,10 @@ def parse(argv=None):
     ap.add_argument("--sketch_path", default=None)
     ap.add_argument("--strict", action="store_true",
                     help="raise instead of re-running a stage in exact fp32 when the split-fp16 kernels had to clamp an operand")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.simplify_cells is not None and not (a.device_mc if a.watertight else a.device_clean):
+        ap.error("--simplify_cells works on the device mesh: add --device_clean (open meshes) or --device_mc (--watertight)")
+    return a
 
 
 def postprocess_open_mesh(mode: str) -> bool:
@@ -192,6 +199,9 @@ def run(a):
         def shape_mesh():
             if a.watertight and a.device_mc:
                 verts, faces = get_watertight_mesh(field, a.resolution, max_batch=2 ** 16, device=True, min_faces=5000)
+                if a.simplify_cells is not None and len(faces):
+                    from surfd_amd.meshsimplify import simplify_vertex_clustering
+                    verts, faces = simplify_vertex_clustering(verts, faces, cells=a.simplify_cells)
                 return verts.cpu().numpy(), faces.cpu().numpy()
             if a.watertight:
                 verts, faces = get_watertight_mesh(field, a.resolution, max_batch=2 ** 16)
@@ -199,7 +209,7 @@ def run(a):
             device_clean = bool(getattr(a, "device_clean", False))
             device_post = bool(getattr(a, "device_post", False)) or device_clean
             v, t = get_mesh_from_udf(field, coords_range=(-1, 1), max_dist=0.1, N=a.resolution, max_batch=2 ** 16, differentiable=False,
-                                     device_post=device_post, device_clean=device_clean)
+                                     device_post=device_post, device_clean=device_clean, simplify_cells=getattr(a, "simplify_cells", None))
             if device_post:                                   # the mesh goes to the host once, for write_obj
                 if postprocess_open_mesh(a.mode):
                     from surfd_amd import meshsmooth, meshtopo

@@ -43,6 +43,10 @@ def parse(argv=None):
     ap.add_argument("--resolution", type=int, default=512)
     ap.add_argument("--watertight", action="store_true")
     ap.add_argument("--device_mc", action="store_true", help="--watertight: mesh the grid on the GPU (same mesh; the grid is not copied to the host)")
+    ap.add_argument("--simplify_cells", type=int, default=None, metavar="K",
+                    help="make the mesh smaller on the GPU before it is written: vertex clustering on a grid of K cells along the largest extent, "
+                         "one quadric representative per occupied cell (surfd_amd.meshsimplify); with --watertight it needs --device_mc, open "
+                         "meshes are then cleaned on the GPU too (device_clean: the same mesh)")
     ap.add_argument("--batch", type=int, default=1, help="clouds per encoder call (export_meshes.py:75 uses 1)")
     ap.add_argument("--seed", type=int, default=10)
     ap.add_argument("--output_dir", default="outputs/reconstruct")
@@ -60,7 +64,10 @@ def parse(argv=None):
                     help="--metrics: also record the reconstruction's topology (surfd_amd.meshtopo): pieces, holes, manifoldness, orientation")
     ap.add_argument("--preview", type=int, default=0, metavar="N",
                     help="also write N orbit views (shaded / depth / normal PNGs, surfd_amd.render) of every mesh; 0 = none")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.simplify_cells is not None and a.watertight and not a.device_mc:
+        ap.error("--simplify_cells works on the device mesh: add --device_mc")
+    return a
 
 
 def synthetic_checkpoint(out_dir, size_latent):
@@ -219,10 +226,14 @@ def run(a):
         def shape_mesh():
             if a.watertight and a.device_mc:
                 v, t = get_watertight_mesh(field, a.resolution, max_batch=2 ** 16, device=True)
+                if a.simplify_cells is not None and len(t):
+                    from surfd_amd.meshsimplify import simplify_vertex_clustering
+                    v, t = simplify_vertex_clustering(v, t, cells=a.simplify_cells)
                 return v.cpu().numpy(), t.cpu().numpy()
             if a.watertight:
                 return get_watertight_mesh(field, a.resolution, max_batch=2 ** 16)
-            v, t = get_mesh_from_udf(field, coords_range=(-1, 1), max_dist=0.1, N=a.resolution, max_batch=2 ** 16, differentiable=False)
+            v, t = get_mesh_from_udf(field, coords_range=(-1, 1), max_dist=0.1, N=a.resolution, max_batch=2 ** 16, differentiable=False,
+                                     device_clean=a.simplify_cells is not None, simplify_cells=a.simplify_cells)
             return v.cpu().numpy(), t.cpu().numpy()
 
         (verts, faces), _ = run_guarded(f"{item} (decoder grids)", shape_mesh, decoder.saturation_count,

@@ -808,6 +808,32 @@ int surfd_meshclean_drop_degenerate_faces(const double *vertices, int V, const i
 int surfd_meshclean_fill_small_holes(const int32_t *faces, int F, int V, int32_t *caps, int64_t cap_rows, int64_t *counts, surfd_stream s);
 
 /* ------------------------------------------------------------------------------------ */
+/* Mesh simplification: vertex clustering on a uniform grid with one representative per  */
+/* occupied cell (no reference counterpart: the reference writes its meshes at the full   */
+/* resolution of the grid).  tests/meshsimplify_ref.py restates the contract sequentially */
+/* in numpy; every output equals it bit for bit and in the same order                     */
+/* (csrc/meshsimplify.hip states the contract and the passes).  Stateless; no float       */
+/* atomics: no result depends on launch geometry.                                         */
+/* ------------------------------------------------------------------------------------ */
+enum { SURFD_SIMPLIFY_MEAN = 0, SURFD_SIMPLIFY_QUADRIC = 1 };
+/* vertices fp64 [V,3] and faces int32 [F,3] on the device.  A face that names a non-finite vertex goes; the vertices the others
+ * name take part.  Cell index per axis k = floor((x - origin) / cell), origin (HOST, 3 doubles) or null = the minimum over the
+ * vertices that take part; each k must lie in [0, 2^21), anything else is SURFD_ERR_ARG (never a wrapped key).  One cluster per
+ * occupied cell, in ascending kx << 42 | ky << 21 | kz, members in ascending index.  representative: SURFD_SIMPLIFY_MEAN = the
+ * sum of the members in that order / count; SURFD_SIMPLIFY_QUADRIC = the minimiser of the cell's area-weighted plane quadric
+ * relative to the cell centre, eigenvalues below rank_tol times the largest truncated (six Jacobi sweeps), the mean where the point
+ * is not finite or leaves the mean by more than a cell on an axis (a fall-back).  Faces are renamed, those with two equal names
+ * (collapsed) go, the rest pass through surfd_meshclean_drop_duplicate_faces (its order); clusters no face names go.
+ * out_vertices[V,3], out_faces[F,3] must hold the whole input; vertex_map[V] (nullable): the output vertex of every input
+ * vertex, -1 without one; counts[6] (host): output vertices, output faces, clusters, collapsed faces, duplicate faces,
+ * fall-backs.  F = 0 or V = 0: empty outputs, the map all -1.  3 F >= 2^31: SURFD_ERR_UNSUPPORTED; cell and rank_tol must be
+ * positive and finite, the origin finite, an index outside [0, V) is found on the device before anything is indexed by it: all
+ * SURFD_ERR_ARG.  HOST-SYNCS 3 TIMES (2 where every face collapses, 1 where none is kept): clusters and kept faces; the duplicate
+ * pass's count; the output sizes. */
+int surfd_meshsimplify_cluster(const double *vertices, int V, const int32_t *faces, int F, const double *origin, double cell, int representative,
+                               double rank_tol, double *out_vertices, int32_t *out_faces, int32_t *vertex_map, int64_t *counts, surfd_stream s);
+
+/* ------------------------------------------------------------------------------------ */
 /* Point-cloud metrics: nearest neighbours between clouds and the matrix of directed      */
 /* Chamfer means between two sets of clouds.  No reference counterpart (the reference     */
 /* ships no evaluation code): stands for pytorch3d's knn_points(p1, p2, K=1) /            */

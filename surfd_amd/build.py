@@ -39,6 +39,7 @@ SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshtopo.hip")          # edges, co
 SOURCES.insert(SOURCES.index("mcubes.cpp"), "mcdevice.hip")          # level-set marching cubes on the device (surfd_amd/mcubes.py: marching_cubes_device)
 SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshsmooth.hip")        # Laplacian / Taubin / border smoothing, vertex normals (surfd_amd/meshsmooth.py)
 SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshclean.hip")         # merge / duplicate / degenerate faces, small holes (surfd_amd/meshclean.py)
+SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshsimplify.hip")      # vertex clustering with mean / quadric representatives (surfd_amd/meshsimplify.py)
 FILE_FLAGS = {"cloudnn.hip": ["-fno-slp-vectorize"], "cloudnormals.hip": ["-fno-slp-vectorize"]}
 
 

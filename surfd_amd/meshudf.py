@@ -355,7 +355,7 @@ def get_udf_and_grads(udf_func, coords_range: Tuple[float, float], max_dist: flo
 def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[float, float], max_dist: float,
                       N: int = 128, smooth_borders: bool = True, differentiable: bool = True,
                       max_batch: int = 2 ** 12, use_fast_grid_filler: bool = True, device_post: bool = False,
-                      device_clean: bool = False) -> Tuple[Tensor, Tensor]:
+                      device_clean: bool = False, simplify_cells: Optional[int] = None) -> Tuple[Tensor, Tensor]:
     """Triangulated mesh of the zero set of a UDF — same signature, defaults and return value as the reference
     (meshudf/meshudf.py:307-514): (vertices [V,3] float32, faces [F,3] int64) on the device.
 
@@ -369,9 +369,18 @@ def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[
     vertex normals from the device too; the cleaning stays on the host.  ``device_clean=True`` (no reference counterpart; implies
     the device smoothing): the mesher's output is uploaded once, the far-face filter runs on the device tensors (the same probes
     and the same rule) and the cleaning runs there too (surfd_amd.meshclean: meshproc's result bit for bit), so the mesh does not
-    come down between the probes and the smoothing; the returned tensors equal the default path's."""
+    come down between the probes and the smoothing; the returned tensors equal the default path's.  ``simplify_cells=K`` (no
+    reference counterpart; needs ``device_clean=True`` and ``differentiable=False``): between the cleaning and the border smoothing
+    the mesh is clustered on a grid of K cells along its largest extent, one quadric representative per occupied cell
+    (surfd_amd.meshsimplify.simplify_vertex_clustering); the simplified vertices are no longer tied to udf samples, so the
+    re-attached gradients have no meaning for them."""
     from . import meshproc as mp
     from .mcubes import udf_mc_lewiner
+    if simplify_cells is not None:
+        if not device_clean:
+            raise ValueError("simplify_cells runs on the device mesh: pass device_clean=True")
+        if differentiable:
+            raise ValueError("simplify_cells moves vertices off the udf samples: pass differentiable=False")
     if not use_fast_grid_filler:
         udf, gradients = get_udf_and_grads(udf_func, coords_range, max_dist, N, max_batch)
     else:
@@ -387,6 +396,9 @@ def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[
 
     if device_clean:
         v64, f64 = _clean_on_device(udf_func, vertices, faces, dev, N, max_batch)
+        if simplify_cells is not None and len(f64):
+            from .meshsimplify import simplify_vertex_clustering
+            v64, f64 = simplify_vertex_clustering(v64, f64, cells=int(simplify_cells))
         return _finish_mesh(udf_func, v64, f64, dev, N, smooth_borders, differentiable, max_batch, True)
     # faces whose corners or edge midpoints sit at large udf values are artefacts: drop them (meshudf.py:354-378)
     edges, edge_face = mp.edges_of_faces(faces)
@@ -456,7 +468,8 @@ def get_watertight_mesh(udf_func: Callable[[Tensor], Tensor], N: int, max_batch:
     ``min_faces=K`` here: components (by shared vertices) with fewer faces go.
     ``device=True``: the grid is meshed where it lies (mcubes.marching_cubes_device: the same mesh bit for bit, no copy of the
     grid to the host) and the result stays there — (vertices float64, faces int64) as device tensors, ``min_faces`` through
-    meshtopo.keep_components_with_at_least — ready for the device stages that follow (winding, voxelize, render, raycast)."""
+    meshtopo.keep_components_with_at_least — ready for the device stages that follow (winding, voxelize, render, raycast;
+    surfd_amd.meshsimplify.simplify_vertex_clustering(verts, faces, cells=K) makes it smaller there)."""
     from .mcubes import marching_cubes, marching_cubes_device
     udf, _ = GridFiller(N).fill_grid(udf_func, max_batch, with_grads=False)
     udf[udf < 0] = 0
