@@ -1,23 +1,39 @@
-// Host scaffold of the device-side builds (meshtopo.hip, meshsmooth.hip, meshbvh.hip), included after common.h: make keys,
-// radix-sort them with hipcub, scan flags, read a count back, size the result, fill it.  What a kernel computes is each file's own.
+// Host scaffold of the device-side builds (meshtopo.hip, meshsmooth.hip, meshbvh.hip, meshclean.hip, meshsimplify.hip), included
+// after common.h: make keys, radix-sort them with hipcub, scan flags, read a count back, size the result, fill it.  What a kernel
+// computes is each file's own; the device pieces two of the files share are in meshedit.h.
 //   DeviceScratch  the temporaries of one build.  get() allocates, the destructor frees: THE SCOPE ENDS ONLY AFTER THE STREAM HAS
 //                  DRAINED (a build synchronises before it returns; hipFree on an earlier return waits for the device itself).
+//   ScratchArena   (scratcharena.h) the temporaries of a call carved from ONE block of its DeviceScratch, dev_slot<T>(n) bytes each;
+//                  zeroed_words() carves the counter words of a call and zeroes them on the stream.
 //   CubWorkspace   hipcub's temporary storage behind the four operations the builds use: each call asks hipcub for the size, makes
 //                  the workspace large enough and runs.  Fed from a DeviceScratch it grows by taking a new block (the old one
 //                  is freed with the scope, so nothing in flight loses its buffer).  Without one it is a handle's own: sized by
 //                  its first call, fixed from then on (a larger need is SURFD_ERR_STATE), so later calls allocate nothing.
 //   dev_bytes, dev_grid, dev_tid, scan_total    sizes of max(n, 1) elements, 256-wide grids, the 64-bit thread index, and the
 //                  total of an exclusive sum.  SURFD_TRY passes a SURFD_* refusal on (the callee has set the message).
+//   DEV_LAUNCH     a kernel over n items on the stream `st` of the scope: one item per lane, 256 lanes per block, no LDS, then
+//                  LAUNCH_CHECK.  Launches of another block size, grid shape or LDS size are written out.
+//   read_words     THE host read of a call: a few counter words, then the stream is drained (the scratch may be freed after it).
+//   mesh_sizes     the refusal of F < 0, V < 0 and 3 F >= 2^31 that every entry point over faces starts with.
 // A build returns from wherever it is refused: besides the scratch it holds the handle it has not finished in a std::unique_ptr
 // with the handle's free function, declared before the scratch, and release()s it at the end.
 #pragma once
 #include <algorithm>
+#include <climits>
 #include <hipcub/hipcub.hpp>
 #include <memory>
+
+#include "scratcharena.h"
 
 #define SURFD_TRY(expr)                                             \
     do {                                                            \
         if (const int _rc = (expr); _rc != SURFD_OK) return _rc;    \
+    } while (0)
+
+#define DEV_LAUNCH(kernel, n, ...)                                                             \
+    do {                                                                                       \
+        hipLaunchKernelGGL(kernel, dim3(dev_grid(n)), dim3(256), 0, st, __VA_ARGS__);          \
+        LAUNCH_CHECK();                                                                        \
     } while (0)
 
 namespace surfd {
@@ -35,6 +51,20 @@ static __global__ void scan_total_kernel(const int *__restrict__ flag, const int
 static inline int scan_total(const int *flag, const int *excl, int n, int *out, hipStream_t st) {
     hipLaunchKernelGGL(scan_total_kernel, dim3(1), dim3(64), 0, st, flag, excl, n, out);
     LAUNCH_CHECK();
+    return SURFD_OK;
+}
+
+// the one host read of a call; the scratch may be freed after it
+static inline int read_words(const int *dev, int *host, int n, hipStream_t st) {
+    HIP_TRY(hipMemcpyAsync(host, dev, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return SURFD_OK;
+}
+
+// too_many: what 3 F >= 2^31 returns (V is an int: below 2^31)
+static inline int mesh_sizes(const char *who, int F, int V, int too_many = SURFD_ERR_ARG) {
+    if (F < 0 || V < 0) SURFD_FAIL(SURFD_ERR_ARG, "%s: F = %d, V = %d must not be negative", who, F, V);
+    if ((long)F * 3 > (long)INT_MAX) SURFD_FAIL(too_many, "%s: 3 F must stay below 2^31, F = %d", who, F);
     return SURFD_OK;
 }
 
@@ -56,6 +86,13 @@ class DeviceScratch {
         return SURFD_OK;
     }
 };
+
+// the counter words of a call, zeroed on the stream
+static inline int zeroed_words(ScratchArena &arena, int **words, int n, hipStream_t st) {
+    SURFD_TRY(arena.get(words, n));
+    HIP_TRY(hipMemsetAsync(*words, 0, (size_t)n * sizeof(int), st));
+    return SURFD_OK;
+}
 
 struct CubWorkspace {
     DeviceScratch *scratch = nullptr;        // null: the handle's own block (its owner frees ptr)

@@ -233,9 +233,7 @@ int bvh_build(MeshBvh *b, const float4 *rec, int rec4, bool relative, int F, hip
     HIP_TRY(hipMemcpyAsync(b->level_off, lay.off, BVH_MAX_LEVELS * sizeof(int), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(bvh_bounds_kernel, dim3(1), dim3(1024), 0, st, rec, rec4, (int)relative, F, bb);
     LAUNCH_CHECK();
-    hipLaunchKernelGGL(bvh_codes_kernel, dim3((unsigned)ceil_div(F, 256)), dim3(256), 0, st, rec, rec4, (int)relative, F, (const float *)bb,
-                       code_in, idx_in);
-    LAUNCH_CHECK();
+    DEV_LAUNCH(bvh_codes_kernel, F, rec, rec4, (int)relative, F, (const float *)bb, code_in, idx_in);      // F >= 1 (bvh_layout)
     SURFD_TRY(cub.sort_pairs(code_in, code_out, idx_in, idx_out, F, 64, st));
     hipLaunchKernelGGL(bvh_leaf_kernel, dim3((unsigned)ceil_div(lay.size[0], 64)), dim3(64), 0, st, rec, rec4, (int)relative, F, lay.nleaf,
                        lay.size[0], (const int *)idx_out, b->leaf_tri, b->boxes);

@@ -34,12 +34,13 @@
 //                    a scan over V, no sort and no count of the caps on the host.  Fewer than 3 faces: no caps (meshproc returns).
 //
 // Passes (256-wide grids, one item per lane; sorts and scans are hipcub's through CubWorkspace):
-//   cull    mc_vertex_flags (finite, range) -> mc_face_mark (keep flag per face, used flag per vertex: every writer stores the
+//   cull    mc_vertex_flags (finite, range) -> face_mark (keep flag per face, used flag per vertex: every writer stores the
 //           same 1) -> three stable 64-bit radix sorts of (key of one coordinate, vertex), z then y then x, the key re-read
 //           through the permutation before each; a vertex that takes no part gets the key 2^63, which no quantised coordinate has,
 //           so those gather in one run and split no class -> mc_heads (head of a run of equal keys) -> inclusive max of the head
-//           positions -> mc_rep (stable sorts of an ascending start: the head of a run is its lowest index) -> exclusive sums of the
-//           survivor and keep flags -> mc_out_vertices, mc_out_faces.
+//           positions -> group_rep (stable sorts of an ascending start: the head of a run is its lowest index) -> exclusive sums of the
+//           survivor and keep flags -> mc_out_vertices, mc_out_faces.  face_mark and everything from the inclusive max to the
+//           survivor count (group_representatives, shared with surfd_meshtopo_weld) are in meshedit.h.
 //   dup     mc_dup_key0 (smallest index, 31 bits) -> sort -> mc_dup_key1 (largest << 32 | middle, 63 bits) -> sort -> mc_dup_heads
 //           -> exclusive sum -> mc_dup_out (the head of every run, at its rank).
 //   degen   mc_degenerate_flags -> exclusive sum -> mc_compact_faces.
@@ -48,7 +49,8 @@
 //           is where one lane wrote it) -> mc_loops -> exclusive sum of the slot flags -> mc_caps_out.  The number of loops is a
 //           reduction of the start flags: 3-loops = 2 loops - caps, 4-loops = caps - loops.
 // Scratch (freed when the call returns): cull 52 V + 8 F bytes, dup 36 F, degen 8 F, holes 72 F + 32 V, carved from ONE
-// DeviceScratch block per call (McArena), plus hipcub's workspace in a block of its own.  Nothing is kept between calls.
+// DeviceScratch block per call (ScratchArena; it, the launch macro, the counter words and their one read-back are devscratch.h's),
+// plus hipcub's workspace in a block of its own.  Nothing is kept between calls.
 //
 // Limits, all return codes: F >= 0, V >= 0, 3 F < 2^31, V < 2^31 (F = 0 or V = 0 give empty outputs).  An index outside [0, V)
 // (negative, for the duplicate pass, which has no V) is SURFD_ERR_ARG.  The kernels that see caller indices compare them first
@@ -62,6 +64,7 @@
 // stay below the input's length; caps are also compared against the caller's row count.
 #include "common.h"
 #include "devscratch.h"
+#include "meshedit.h"
 #include "meshscene.h"
 #include <cmath>
 
@@ -87,21 +90,9 @@ __global__ void mc_vertex_flags_kernel(const double *__restrict__ vertices, int 
     if (dev_tid() >= V) return;
     const long v = dev_tid();
     const double x = vertices[3 * v], y = vertices[3 * v + 1], z = vertices[3 * v + 2];
-    const bool fin = isfinite(x) && isfinite(y) && isfinite(z);
-    nonfinite[v] = fin ? 0 : 1;
-    if (fin && !(fabs(x * scale) < 0x1p62 && fabs(y * scale) < 0x1p62 && fabs(z * scale) < 0x1p62)) cnt[MC_RANGE] = 1;      // every writer stores the same 1
-}
-
-// the only cull kernel that sees the caller's indices: a face with one out of range raises the flag and is not looked at further
-__global__ void mc_face_mark_kernel(const int32_t *__restrict__ faces, int F, int V, const int *__restrict__ nonfinite, int *__restrict__ keep,
-                                    int *__restrict__ used, int *__restrict__ cnt) {
-    if (dev_tid() >= F) return;
-    const long f = dev_tid();
-    const int t0 = faces[3 * f], t1 = faces[3 * f + 1], t2 = faces[3 * f + 2];
-    if (!mc_in(t0, V) || !mc_in(t1, V) || !mc_in(t2, V)) { cnt[MC_BAD] = 1; keep[f] = 0; return; }
-    const int k = (nonfinite[t0] | nonfinite[t1] | nonfinite[t2]) ? 0 : 1;
-    keep[f] = k;
-    if (k) { used[t0] = 1; used[t1] = 1; used[t2] = 1; }      // every writer stores the same 1
+    const int nf = vertex_nonfinite(vertices, v);
+    nonfinite[v] = nf;
+    if (!nf && !(fabs(x * scale) < 0x1p62 && fabs(y * scale) < 0x1p62 && fabs(z * scale) < 0x1p62)) cnt[MC_RANGE] = 1;      // every writer stores the same 1
 }
 
 // key[i] = the quantised coordinate c of vertex idx[i] (of vertex i without idx, which also starts the permutation in iota)
@@ -126,15 +117,6 @@ __global__ void mc_heads_kernel(const double *__restrict__ vertices, int V, doub
         for (int j = 0; j < 3; ++j) same = same && mc_quantise(vertices[3 * a + j], scale) == mc_quantise(vertices[3 * b + j], scale);
     }
     headpos[i] = same ? 0 : i;
-}
-
-__global__ void mc_rep_kernel(int V, const int *__restrict__ idx, const int *__restrict__ headpos, const int *__restrict__ used, int *__restrict__ rep,
-                              int *__restrict__ survives) {
-    if (dev_tid() >= V) return;
-    const int i = (int)dev_tid();
-    const int v = idx[i], r = idx[headpos[i]];
-    rep[v] = r;
-    survives[v] = (used[v] && v == r) ? 1 : 0;
 }
 
 __global__ void mc_out_vertices_kernel(const double *__restrict__ vertices, int V, const int *__restrict__ survives, const int *__restrict__ newidx,
@@ -285,69 +267,16 @@ __global__ void mc_caps_out_kernel(int V, const int *__restrict__ capflag, const
     for (int c = 0; c < 3; ++c) caps[3 * n + c] = captri[3 * m + c];
 }
 
-namespace {
-
-int mc_args(const char *who, int F, int V) {
-    if (F < 0 || V < 0) SURFD_FAIL(SURFD_ERR_ARG, "%s: F = %d, V = %d must not be negative", who, F, V);
-    if ((long)F * 3 > (long)INT_MAX) SURFD_FAIL(SURFD_ERR_ARG, "%s: 3 F must stay below 2^31, F = %d", who, F);
-    return SURFD_OK;
-}
-
-// The temporaries of a call, carved from ONE block of its DeviceScratch: a block per temporary is a hipMalloc / hipFree pair each,
-// and a call here has up to fourteen.  open() takes the sum of the slots the call is going to ask for; get() refuses to go past it.
-template <class T>
-size_t mc_slot(long n) { return (dev_bytes<T>(n) + 255) & ~(size_t)255; }
-
-class McArena {
-    char *base = nullptr;
-    size_t size = 0, used = 0;
-  public:
-    int open(DeviceScratch &scratch, size_t bytes) {
-        size = bytes;
-        return scratch.get(&base, (long)bytes);
-    }
-    template <class T>
-    int get(T **ptr, long n) {
-        const size_t b = mc_slot<T>(n);
-        if (used + b > size) SURFD_FAIL(SURFD_ERR_STATE, "meshclean: the arena of the call is too small (%zu + %zu > %zu bytes)", used, b, size);
-        *ptr = (T *)(base + used);
-        used += b;
-        return SURFD_OK;
-    }
-};
-
-// the counter words of a call, zeroed on the stream
-int mc_counters(McArena &arena, int **cnt, hipStream_t st) {
-    SURFD_TRY(arena.get(cnt, MC_WORDS));
-    HIP_TRY(hipMemsetAsync(*cnt, 0, MC_WORDS * sizeof(int), st));
-    return SURFD_OK;
-}
-
-// the one host read of a call; the scratch may be freed after it
-int mc_read(const int *cnt, int *host, hipStream_t st) {
-    HIP_TRY(hipMemcpyAsync(host, cnt, MC_WORDS * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return SURFD_OK;
-}
-
-}  // namespace
-
 }  // namespace surfd
 
 using namespace surfd;
-
-#define MC_LAUNCH(kernel, n, ...)                                                              \
-    do {                                                                                       \
-        hipLaunchKernelGGL(kernel, dim3(dev_grid(n)), dim3(256), 0, st, __VA_ARGS__);          \
-        LAUNCH_CHECK();                                                                        \
-    } while (0)
 
 extern "C" int surfd_meshclean_cull_and_merge(const double *vertices, int V, const int32_t *faces, int F, double scale, double *out_vertices,
                                               int32_t *out_faces, int64_t *counts, surfd_stream s) {
     const char *who = "surfd_meshclean_cull_and_merge";
     if (!counts) SURFD_FAIL(SURFD_ERR_ARG, "%s: null argument", who);
     for (int i = 0; i < 5; ++i) counts[i] = 0;
-    SURFD_TRY(mc_args(who, F, V));
+    SURFD_TRY(mesh_sizes(who, F, V));
     if (!(scale > 0.0) || !std::isfinite(scale)) SURFD_FAIL(SURFD_ERR_ARG, "%s: scale = %g must be positive and finite", who, scale);
     if (F == 0 || V == 0) return SURFD_OK;
     if (!vertices || !faces || !out_vertices || !out_faces) SURFD_FAIL(SURFD_ERR_ARG, "%s: null argument", who);
@@ -356,36 +285,33 @@ extern "C" int surfd_meshclean_cull_and_merge(const double *vertices, int V, con
     CubWorkspace cub{&scratch};
     int *cnt, *nonfinite, *used, *idxa, *idxb, *headpos, *hp, *rep, *survives, *newidx, *keep, *fpos;
     mc_u64 *key, *key2;
-    McArena arena;
-    SURFD_TRY(arena.open(scratch, mc_slot<int>(MC_WORDS) + 9 * mc_slot<int>(V) + 2 * mc_slot<mc_u64>(V) + 2 * mc_slot<int>(F)));
-    SURFD_TRY(mc_counters(arena, &cnt, st));
+    ScratchArena arena("meshclean");
+    SURFD_TRY(arena.open(scratch, dev_slot<int>(MC_WORDS) + 9 * dev_slot<int>(V) + 2 * dev_slot<mc_u64>(V) + 2 * dev_slot<int>(F)));
+    SURFD_TRY(zeroed_words(arena, &cnt, MC_WORDS, st));
     SURFD_TRY(arena.get(&nonfinite, V)); SURFD_TRY(arena.get(&used, V)); SURFD_TRY(arena.get(&idxa, V)); SURFD_TRY(arena.get(&idxb, V));
     SURFD_TRY(arena.get(&headpos, V)); SURFD_TRY(arena.get(&hp, V)); SURFD_TRY(arena.get(&rep, V)); SURFD_TRY(arena.get(&survives, V));
     SURFD_TRY(arena.get(&newidx, V)); SURFD_TRY(arena.get(&key, V)); SURFD_TRY(arena.get(&key2, V));
     SURFD_TRY(arena.get(&keep, F)); SURFD_TRY(arena.get(&fpos, F));
     HIP_TRY(hipMemsetAsync(used, 0, dev_bytes<int>(V), st));
-    MC_LAUNCH(mc_vertex_flags_kernel, V, vertices, V, scale, nonfinite, cnt);
-    MC_LAUNCH(mc_face_mark_kernel, F, faces, F, V, (const int *)nonfinite, keep, used, cnt);
+    DEV_LAUNCH(mc_vertex_flags_kernel, V, vertices, V, scale, nonfinite, cnt);
+    DEV_LAUNCH(face_mark_kernel, F, faces, F, V, (const int *)nonfinite, keep, used, cnt + MC_BAD);
     // least significant coordinate first; the sorts are stable, so equal keys end up adjacent and ascending in the vertex index
-    MC_LAUNCH(mc_coord_key_kernel, V, vertices, V, scale, (const int *)used, (const int *)nullptr, 2, key, idxa);
+    DEV_LAUNCH(mc_coord_key_kernel, V, vertices, V, scale, (const int *)used, (const int *)nullptr, 2, key, idxa);
     SURFD_TRY(cub.sort_pairs(key, key2, idxa, idxb, V, 64, st));
-    MC_LAUNCH(mc_coord_key_kernel, V, vertices, V, scale, (const int *)used, (const int *)idxb, 1, key, (int *)nullptr);
+    DEV_LAUNCH(mc_coord_key_kernel, V, vertices, V, scale, (const int *)used, (const int *)idxb, 1, key, (int *)nullptr);
     SURFD_TRY(cub.sort_pairs(key, key2, idxb, idxa, V, 64, st));
-    MC_LAUNCH(mc_coord_key_kernel, V, vertices, V, scale, (const int *)used, (const int *)idxa, 0, key, (int *)nullptr);
+    DEV_LAUNCH(mc_coord_key_kernel, V, vertices, V, scale, (const int *)used, (const int *)idxa, 0, key, (int *)nullptr);
     SURFD_TRY(cub.sort_pairs(key, key2, idxa, idxb, V, 64, st));
-    MC_LAUNCH(mc_heads_kernel, V, vertices, V, scale, (const int *)used, (const int *)idxb, headpos);
-    SURFD_TRY(cub.inclusive_max(headpos, hp, V, st));
-    MC_LAUNCH(mc_rep_kernel, V, V, (const int *)idxb, (const int *)hp, (const int *)used, rep, survives);
-    SURFD_TRY(cub.exclusive_sum(survives, newidx, V, st));
-    SURFD_TRY(scan_total(survives, newidx, V, cnt + MC_N0, st));
+    DEV_LAUNCH(mc_heads_kernel, V, vertices, V, scale, (const int *)used, (const int *)idxb, headpos);
+    SURFD_TRY(group_representatives(cub, V, idxb, headpos, hp, used, rep, survives, newidx, cnt + MC_N0, st));
     SURFD_TRY(cub.exclusive_sum(keep, fpos, F, st));
     SURFD_TRY(scan_total(keep, fpos, F, cnt + MC_N1, st));
     SURFD_TRY(cub.reduce_sum(nonfinite, cnt + MC_N2, V, st));
     SURFD_TRY(cub.reduce_sum(used, cnt + MC_N3, V, st));
-    MC_LAUNCH(mc_out_vertices_kernel, V, vertices, V, (const int *)survives, (const int *)newidx, out_vertices);
-    MC_LAUNCH(mc_out_faces_kernel, F, faces, F, (const int *)keep, (const int *)fpos, (const int *)rep, (const int *)newidx, out_faces);
+    DEV_LAUNCH(mc_out_vertices_kernel, V, vertices, V, (const int *)survives, (const int *)newidx, out_vertices);
+    DEV_LAUNCH(mc_out_faces_kernel, F, faces, F, (const int *)keep, (const int *)fpos, (const int *)rep, (const int *)newidx, out_faces);
     int hc[MC_WORDS];
-    SURFD_TRY(mc_read(cnt, hc, st));
+    SURFD_TRY(read_words(cnt, hc, MC_WORDS, st));
     if (hc[MC_BAD]) return mesh_bad_index(who, V);
     if (hc[MC_RANGE]) SURFD_FAIL(SURFD_ERR_ARG, "%s: a finite coordinate times the scale %g reaches 2^62: beyond the range of the 64-bit keys", who, scale);
     counts[0] = hc[MC_N0];                                   // vertices that stay
@@ -400,7 +326,7 @@ extern "C" int surfd_meshclean_drop_duplicate_faces(const int32_t *faces, int F,
     const char *who = "surfd_meshclean_drop_duplicate_faces";
     if (!count) SURFD_FAIL(SURFD_ERR_ARG, "%s: null argument", who);
     *count = 0;
-    SURFD_TRY(mc_args(who, F, 0));
+    SURFD_TRY(mesh_sizes(who, F, 0));
     if (F == 0) return SURFD_OK;
     if (!faces || !out_faces) SURFD_FAIL(SURFD_ERR_ARG, "%s: null argument", who);
     hipStream_t st = as_stream(s);
@@ -409,23 +335,23 @@ extern "C" int surfd_meshclean_drop_duplicate_faces(const int32_t *faces, int F,
     int *cnt, *idxa, *idxb, *head, *rank;
     unsigned *k0, *k0s;
     mc_u64 *k1, *k1s;
-    McArena arena;
-    SURFD_TRY(arena.open(scratch, mc_slot<int>(MC_WORDS) + 4 * mc_slot<int>(F) + mc_slot<unsigned>(F) + 2 * mc_slot<mc_u64>(F)));
-    SURFD_TRY(mc_counters(arena, &cnt, st));
+    ScratchArena arena("meshclean");
+    SURFD_TRY(arena.open(scratch, dev_slot<int>(MC_WORDS) + 4 * dev_slot<int>(F) + dev_slot<unsigned>(F) + 2 * dev_slot<mc_u64>(F)));
+    SURFD_TRY(zeroed_words(arena, &cnt, MC_WORDS, st));
     SURFD_TRY(arena.get(&idxa, F)); SURFD_TRY(arena.get(&idxb, F)); SURFD_TRY(arena.get(&head, F)); SURFD_TRY(arena.get(&rank, F));
     SURFD_TRY(arena.get(&k0, F)); SURFD_TRY(arena.get(&k1, F)); SURFD_TRY(arena.get(&k1s, F));
     k0s = (unsigned *)k1;                                    // 4 F of the 8 F bytes that the second sort's keys overwrite after the first sort is done
     SURFD_TRY(cub.sort_pairs(k1, k1s, idxb, idxa, F, 63, st, true));        // the second sort is the larger: one workspace allocation
-    MC_LAUNCH(mc_dup_key0_kernel, F, faces, F, k0, idxa, cnt);
+    DEV_LAUNCH(mc_dup_key0_kernel, F, faces, F, k0, idxa, cnt);
     SURFD_TRY(cub.sort_pairs(k0, k0s, idxa, idxb, F, 31, st));
-    MC_LAUNCH(mc_dup_key1_kernel, F, faces, F, (const int *)idxb, k1);
+    DEV_LAUNCH(mc_dup_key1_kernel, F, faces, F, (const int *)idxb, k1);
     SURFD_TRY(cub.sort_pairs(k1, k1s, idxb, idxa, F, 63, st));
-    MC_LAUNCH(mc_dup_heads_kernel, F, faces, F, (const int *)idxa, head);
+    DEV_LAUNCH(mc_dup_heads_kernel, F, faces, F, (const int *)idxa, head);
     SURFD_TRY(cub.exclusive_sum(head, rank, F, st));
     SURFD_TRY(scan_total(head, rank, F, cnt + MC_N0, st));
-    MC_LAUNCH(mc_dup_out_kernel, F, faces, F, (const int *)idxa, (const int *)head, (const int *)rank, out_faces);
+    DEV_LAUNCH(mc_dup_out_kernel, F, faces, F, (const int *)idxa, (const int *)head, (const int *)rank, out_faces);
     int hc[MC_WORDS];
-    SURFD_TRY(mc_read(cnt, hc, st));
+    SURFD_TRY(read_words(cnt, hc, MC_WORDS, st));
     if (hc[MC_BAD]) SURFD_FAIL(SURFD_ERR_ARG, "%s: a face names a negative vertex index", who);
     *count = hc[MC_N0];
     return SURFD_OK;
@@ -436,23 +362,23 @@ extern "C" int surfd_meshclean_drop_degenerate_faces(const double *vertices, int
     const char *who = "surfd_meshclean_drop_degenerate_faces";
     if (!count) SURFD_FAIL(SURFD_ERR_ARG, "%s: null argument", who);
     *count = 0;
-    SURFD_TRY(mc_args(who, F, V));
+    SURFD_TRY(mesh_sizes(who, F, V));
     if (F == 0) return SURFD_OK;
     if (!faces || !out_faces || (V > 0 && !vertices)) SURFD_FAIL(SURFD_ERR_ARG, "%s: null argument", who);
     hipStream_t st = as_stream(s);
     DeviceScratch scratch;
     CubWorkspace cub{&scratch};
     int *cnt, *keep, *pos;
-    McArena arena;
-    SURFD_TRY(arena.open(scratch, mc_slot<int>(MC_WORDS) + 2 * mc_slot<int>(F)));
-    SURFD_TRY(mc_counters(arena, &cnt, st));
+    ScratchArena arena("meshclean");
+    SURFD_TRY(arena.open(scratch, dev_slot<int>(MC_WORDS) + 2 * dev_slot<int>(F)));
+    SURFD_TRY(zeroed_words(arena, &cnt, MC_WORDS, st));
     SURFD_TRY(arena.get(&keep, F)); SURFD_TRY(arena.get(&pos, F));
-    MC_LAUNCH(mc_degenerate_flags_kernel, F, vertices, V, faces, F, height, keep, cnt);
+    DEV_LAUNCH(mc_degenerate_flags_kernel, F, vertices, V, faces, F, height, keep, cnt);
     SURFD_TRY(cub.exclusive_sum(keep, pos, F, st));
     SURFD_TRY(scan_total(keep, pos, F, cnt + MC_N0, st));
-    MC_LAUNCH(mc_compact_faces_kernel, F, faces, F, (const int *)keep, (const int *)pos, out_faces);
+    DEV_LAUNCH(mc_compact_faces_kernel, F, faces, F, (const int *)keep, (const int *)pos, out_faces);
     int hc[MC_WORDS];
-    SURFD_TRY(mc_read(cnt, hc, st));
+    SURFD_TRY(read_words(cnt, hc, MC_WORDS, st));
     if (hc[MC_BAD]) return mesh_bad_index(who, V);
     *count = hc[MC_N0];
     return SURFD_OK;
@@ -462,7 +388,7 @@ extern "C" int surfd_meshclean_fill_small_holes(const int32_t *faces, int F, int
     const char *who = "surfd_meshclean_fill_small_holes";
     if (!counts) SURFD_FAIL(SURFD_ERR_ARG, "%s: null argument", who);
     counts[0] = counts[1] = counts[2] = 0;
-    SURFD_TRY(mc_args(who, F, V));
+    SURFD_TRY(mesh_sizes(who, F, V));
     if (F < 3) return SURFD_OK;                              // meshproc returns its input
     const int64_t most = std::min<int64_t>(V, 3L * F / 2);   // a cap has its own smallest vertex, and uses up at least two border half-edges
     if (!faces || cap_rows < most || (most > 0 && !caps))
@@ -474,27 +400,27 @@ extern "C" int surfd_meshclean_fill_small_holes(const int32_t *faces, int F, int
     int *cnt, *eh, *sh, *outcnt, *nxt, *start, *capflag, *cpos;
     int32_t *captri;
     mc_u64 *key, *skey;
-    McArena arena;
-    SURFD_TRY(arena.open(scratch, mc_slot<int>(MC_WORDS) + 2 * mc_slot<mc_u64>(H) + 2 * mc_slot<int>(H) + 5 * mc_slot<int>(V) + mc_slot<int32_t>(3L * V)));
-    SURFD_TRY(mc_counters(arena, &cnt, st));
+    ScratchArena arena("meshclean");
+    SURFD_TRY(arena.open(scratch, dev_slot<int>(MC_WORDS) + 2 * dev_slot<mc_u64>(H) + 2 * dev_slot<int>(H) + 5 * dev_slot<int>(V) + dev_slot<int32_t>(3L * V)));
+    SURFD_TRY(zeroed_words(arena, &cnt, MC_WORDS, st));
     SURFD_TRY(arena.get(&key, H)); SURFD_TRY(arena.get(&skey, H)); SURFD_TRY(arena.get(&eh, H)); SURFD_TRY(arena.get(&sh, H));
     SURFD_TRY(arena.get(&outcnt, V)); SURFD_TRY(arena.get(&start, V)); SURFD_TRY(arena.get(&capflag, V)); SURFD_TRY(arena.get(&nxt, V));
     SURFD_TRY(arena.get(&cpos, V)); SURFD_TRY(arena.get(&captri, 3L * V));
-    HIP_TRY(hipMemsetAsync(outcnt, 0, 3 * mc_slot<int>(V), st));      // outcnt, start, capflag: three slots in a row
+    HIP_TRY(hipMemsetAsync(outcnt, 0, 3 * dev_slot<int>(V), st));      // outcnt, start, capflag: three slots in a row
     int bits = 1;                                            // of an index below V: the keys take 2 bits of the radix sort, not 64
     while (bits < 31 && (1L << bits) < V) ++bits;
-    MC_LAUNCH(mc_edge_keys_kernel, F, faces, F, V, bits, key, eh, cnt);
+    DEV_LAUNCH(mc_edge_keys_kernel, F, faces, F, V, bits, key, eh, cnt);
     SURFD_TRY(cub.sort_pairs(key, skey, eh, sh, H, 2 * bits, st));
-    MC_LAUNCH(mc_border_next_kernel, H, (const mc_u64 *)skey, (const int *)sh, faces, H, V, outcnt, nxt);
+    DEV_LAUNCH(mc_border_next_kernel, H, (const mc_u64 *)skey, (const int *)sh, faces, H, V, outcnt, nxt);
     if (V > 0) {
-        MC_LAUNCH(mc_loops_kernel, V, V, (const int *)outcnt, (const int *)nxt, start, capflag, captri);
+        DEV_LAUNCH(mc_loops_kernel, V, V, (const int *)outcnt, (const int *)nxt, start, capflag, captri);
         SURFD_TRY(cub.exclusive_sum(capflag, cpos, V, st));
         SURFD_TRY(scan_total(capflag, cpos, V, cnt + MC_N0, st));
         SURFD_TRY(cub.reduce_sum(start, cnt + MC_N1, V, st));
-        MC_LAUNCH(mc_caps_out_kernel, V, V, (const int *)capflag, (const int *)cpos, (const int32_t *)captri, (long)cap_rows, caps);
+        DEV_LAUNCH(mc_caps_out_kernel, V, V, (const int *)capflag, (const int *)cpos, (const int32_t *)captri, (long)cap_rows, caps);
     }
     int hc[MC_WORDS];
-    SURFD_TRY(mc_read(cnt, hc, st));
+    SURFD_TRY(read_words(cnt, hc, MC_WORDS, st));
     if (hc[MC_BAD]) return mesh_bad_index(who, V);
     const int64_t n_caps = hc[MC_N0], n_loops = hc[MC_N1];
     counts[0] = n_caps;                                      // a 3-loop gives one cap, a 4-loop two

@@ -32,82 +32,70 @@
 //   counts       output vertices, output faces, clusters, collapsed faces, duplicate faces, fall-backs (over all clusters).
 //
 // Passes (256-wide grids, one item per lane unless said; sorts and scans are hipcub's through CubWorkspace):
-//   ms_vertex_flags -> ms_face_mark (keep per face, used per vertex; the only kernel that sees caller indices unchecked) ->
-//   ms_origin_min (block minimum of an order-preserving integer image of the doubles, then one integer atomicMin per block and
-//   axis: a minimum has no order) -> ms_origin_set -> ms_keys (range check; a vertex that takes no part gets 2^63, which no key
-//   has) -> stable 64-bit radix sort of (key, vertex) -> ms_heads -> exclusive sum -> ms_cluster_of (cluster of every vertex, start
-//   of every run) -> ms_face_live (renamed, not collapsed) -> exclusive sums of keep and live -> ms_compact_live -> HOST READ 1:
+//   vc_vertex_flags -> face_mark (keep per face, used per vertex; the only kernel that sees caller indices unchecked) ->
+//   vc_origin_min (block minimum of an order-preserving integer image of the doubles, then one integer atomicMin per block and
+//   axis: a minimum has no order) -> vc_origin_set -> vc_keys (range check; a vertex that takes no part gets 2^63, which no key
+//   has) -> stable 64-bit radix sort of (key, vertex) -> run_heads -> exclusive sum -> vc_cluster_of (cluster of every vertex, start
+//   of every run) -> vc_face_live (renamed, not collapsed) -> exclusive sums of keep and live -> vc_compact_live -> HOST READ 1:
 //   flags, clusters C, kept faces, live faces.
-//   ms_mean (one lane per cluster walks its run) -> for quadric: ms_corner_records (3 per kept face, compacted, in ascending
+//   vc_mean (one lane per cluster walks its run) -> for quadric: vc_corner_records (3 per kept face, compacted, in ascending
 //   3 f + corner) -> stable sort by cluster over ceil(log2 C) bits (C == 1: ZERO bits, no sort is issued: rocPRIM's onesweep writes
-//   nothing to its output for an empty bit range, and the records are in order already) -> ms_record_heads -> ms_quadric (one lane
+//   nothing to its output for an empty bit range, and the records are in order already) -> vc_record_heads -> vc_quadric (one lane
 //   per cluster walks its records, then the Jacobi and the point) -> surfd_meshclean_drop_duplicate_faces on the live faces (HOST
-//   READ 2, its own) -> ms_mark_named -> exclusive sum -> ms_out_vertices, ms_out_faces, ms_vertex_map -> HOST READ 3: output
-//   vertices, fall-backs.
+//   READ 2, its own) -> vc_mark_named -> exclusive sum -> vc_out_vertices, vc_out_faces, vc_vertex_map -> HOST READ 3: output
+//   vertices, fall-backs.  face_mark, run_heads and the non-finite flag are in meshedit.h.
 // No float atomics: every sum is one lane's loop in a fixed order.  The one-lane walks cost what their longest run costs: a
 // cluster of n members and r records is n + r dependent iterations on one lane (each record gathers 3 indices and 9 doubles)
 // while the other 63 lanes of its wave wait; nothing balances lanes of unequal length.
 // Scratch (freed when the call returns): 48 V + 28 F bytes before the first read, then 36 C + 12 F_live + (quadric) 48 F_kept,
-// each stage in ONE DeviceScratch block, plus hipcub's workspace and the duplicate pass's own 36 F_live.
+// each stage in ONE DeviceScratch block (the ScratchArena of devscratch.h, opened once per stage), plus hipcub's workspace and the
+// duplicate pass's own 36 F_live.
 // Limits: F >= 0, V >= 0 (F = 0 or V = 0: empty outputs, the map all -1); 3 F < 2^31 and V < 2^31, beyond: SURFD_ERR_UNSUPPORTED.
 // Bounds: every kernel guards its thread index; arrays of V entries are indexed by caller indices only behind the comparison in
-// ms_face_mark (a face that fails it is not kept, and only kept faces are read again) or by library-made values (permutations of
+// face_mark (a face that fails it is not kept, and only kept faces are read again) or by library-made values (permutations of
 // [0, V), cluster numbers below C <= V, record values 3 f + corner of kept faces); output rows come from exclusive sums of flags.
 #include "common.h"
 #include "devscratch.h"
+#include "meshedit.h"
 #include "meshscene.h"
 #include <cmath>
 
 namespace surfd {
 
-typedef unsigned long long ms_u64;
-constexpr ms_u64 MS_KEY_NONE = 0x8000000000000000ull;        // every key of a vertex that takes part is below 2^63
-constexpr int MS_KBITS = 21;
-enum { MS_BAD = 0, MS_RANGE = 1, MS_C = 2, MS_KEPT = 3, MS_LIVE = 4, MS_VOUT = 5, MS_FALLBACK = 6, MS_WORDS = 8 };
-
-__device__ __forceinline__ bool ms_in(int t, int V) { return t >= 0 && t < V; }
+typedef unsigned long long vc_u64;
+constexpr vc_u64 VC_KEY_NONE = 0x8000000000000000ull;        // every key of a vertex that takes part is below 2^63
+constexpr int VC_KBITS = 21;
+enum { VC_BAD = 0, VC_RANGE = 1, VC_C = 2, VC_KEPT = 3, VC_LIVE = 4, VC_VOUT = 5, VC_FALLBACK = 6, VC_WORDS = 8 };
 
 // an image of the doubles in which unsigned order is numeric order (-0.0 below 0.0; no NaN comes here)
-__device__ __forceinline__ ms_u64 ms_ordered(double x) {
-    const ms_u64 b = (ms_u64)__double_as_longlong(x);
-    return (b >> 63) ? ~b : (b | MS_KEY_NONE);
+__device__ __forceinline__ vc_u64 vc_ordered(double x) {
+    const vc_u64 b = (vc_u64)__double_as_longlong(x);
+    return (b >> 63) ? ~b : (b | VC_KEY_NONE);
 }
-__device__ __forceinline__ double ms_unordered(ms_u64 o) {
-    const ms_u64 b = (o >> 63) ? (o & ~MS_KEY_NONE) : ~o;
+__device__ __forceinline__ double vc_unordered(vc_u64 o) {
+    const vc_u64 b = (o >> 63) ? (o & ~VC_KEY_NONE) : ~o;
     return __longlong_as_double((long long)b);
 }
 
-__global__ void ms_vertex_flags_kernel(const double *__restrict__ vertices, int V, int *__restrict__ nonfinite) {
+__global__ void vc_vertex_flags_kernel(const double *__restrict__ vertices, int V, int *__restrict__ nonfinite) {
     if (dev_tid() >= V) return;
     const long v = dev_tid();
-    nonfinite[v] = (isfinite(vertices[3 * v]) && isfinite(vertices[3 * v + 1]) && isfinite(vertices[3 * v + 2])) ? 0 : 1;
-}
-
-// a face with an index out of range raises the flag and is not looked at further
-__global__ void ms_face_mark_kernel(const int32_t *__restrict__ faces, int F, int V, const int *__restrict__ nonfinite, int *__restrict__ keep,
-                                    int *__restrict__ used, int *__restrict__ cnt) {
-    if (dev_tid() >= F) return;
-    const long f = dev_tid();
-    const int t0 = faces[3 * f], t1 = faces[3 * f + 1], t2 = faces[3 * f + 2];
-    if (!ms_in(t0, V) || !ms_in(t1, V) || !ms_in(t2, V)) { cnt[MS_BAD] = 1; keep[f] = 0; return; }
-    const int k = (nonfinite[t0] | nonfinite[t1] | nonfinite[t2]) ? 0 : 1;
-    keep[f] = k;
-    if (k) { used[t0] = 1; used[t1] = 1; used[t2] = 1; }      // every writer stores the same 1
+    nonfinite[v] = vertex_nonfinite(vertices, v);
 }
 
 // omin[3], preset to all ones: the smallest image per axis over the referenced vertices
-__global__ void __launch_bounds__(256) ms_origin_min_kernel(const double *__restrict__ vertices, int V, const int *__restrict__ used, ms_u64 *omin) {
-    __shared__ ms_u64 sm[3][256];
+__global__ void __launch_bounds__(256) vc_origin_min_kernel(const double *__restrict__ vertices, int V, const int *__restrict__ used, vc_u64 *omin) {
+    __shared__ vc_u64 sm[3][256];
     const long v = dev_tid();
     const bool on = v < V && used[v];
 #pragma unroll
-    for (int j = 0; j < 3; ++j) sm[j][threadIdx.x] = on ? ms_ordered(vertices[3 * v + j]) : ~0ull;
+    for (int j = 0; j < 3; ++j) sm[j][threadIdx.x] = on ? vc_ordered(vertices[3 * v + j]) : ~0ull;
     __syncthreads();
     for (int w = 128; w > 0; w >>= 1) {
         if ((int)threadIdx.x < w) {
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
-                const ms_u64 a = sm[j][threadIdx.x], b = sm[j][threadIdx.x + w];
+                const vc_u64 a = sm[j][threadIdx.x], b = sm[j][threadIdx.x + w];
                 sm[j][threadIdx.x] = b < a ? b : a;
             }
         }
@@ -116,51 +104,44 @@ __global__ void __launch_bounds__(256) ms_origin_min_kernel(const double *__rest
     if (threadIdx.x < 3 && sm[threadIdx.x][0] != ~0ull) atomicMin(omin + threadIdx.x, sm[threadIdx.x][0]);
 }
 
-__global__ void ms_origin_set_kernel(const ms_u64 *__restrict__ omin, int given, double ox, double oy, double oz, double *__restrict__ org) {
+__global__ void vc_origin_set_kernel(const vc_u64 *__restrict__ omin, int given, double ox, double oy, double oz, double *__restrict__ org) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     if (given) { org[0] = ox; org[1] = oy; org[2] = oz; return; }
 #pragma unroll
-    for (int j = 0; j < 3; ++j) org[j] = omin[j] == ~0ull ? 0.0 : ms_unordered(omin[j]) + 0.0;      // no referenced vertex: no key is made
+    for (int j = 0; j < 3; ++j) org[j] = omin[j] == ~0ull ? 0.0 : vc_unordered(omin[j]) + 0.0;      // no referenced vertex: no key is made
 }
 
-__global__ void ms_keys_kernel(const double *__restrict__ vertices, int V, const int *__restrict__ used, const double *__restrict__ org, double cell,
-                               ms_u64 *__restrict__ key, int *__restrict__ iota, int *__restrict__ cnt) {
+__global__ void vc_keys_kernel(const double *__restrict__ vertices, int V, const int *__restrict__ used, const double *__restrict__ org, double cell,
+                               vc_u64 *__restrict__ key, int *__restrict__ iota, int *__restrict__ cnt) {
     if (dev_tid() >= V) return;
     const long v = dev_tid();
     iota[v] = (int)v;
-    ms_u64 k = MS_KEY_NONE;
+    vc_u64 k = VC_KEY_NONE;
     if (used[v]) {
         const double kx = floor((vertices[3 * v] - org[0]) / cell), ky = floor((vertices[3 * v + 1] - org[1]) / cell),
                      kz = floor((vertices[3 * v + 2] - org[2]) / cell);
-        const double top = (double)(1 << MS_KBITS);
+        const double top = (double)(1 << VC_KBITS);
         if (kx >= 0.0 && kx < top && ky >= 0.0 && ky < top && kz >= 0.0 && kz < top)
-            k = ((ms_u64)kx << (2 * MS_KBITS)) | ((ms_u64)ky << MS_KBITS) | (ms_u64)kz;
+            k = ((vc_u64)kx << (2 * VC_KBITS)) | ((vc_u64)ky << VC_KBITS) | (vc_u64)kz;
         else
-            cnt[MS_RANGE] = 1;                                  // every writer stores the same 1; the vertex keeps the key of no cell
+            cnt[VC_RANGE] = 1;                                  // every writer stores the same 1; the vertex keeps the key of no cell
     }
     key[v] = k;
 }
 
-__global__ void ms_heads_kernel(const ms_u64 *__restrict__ skey, int V, int *__restrict__ head) {
-    if (dev_tid() >= V) return;
-    const long i = dev_tid();
-    const ms_u64 k = skey[i];
-    head[i] = (k != MS_KEY_NONE && (i == 0 || skey[i - 1] != k)) ? 1 : 0;
-}
-
-__global__ void ms_cluster_of_kernel(const ms_u64 *__restrict__ skey, const int *__restrict__ sidx, const int *__restrict__ head, const int *__restrict__ hpos,
+__global__ void vc_cluster_of_kernel(const vc_u64 *__restrict__ skey, const int *__restrict__ sidx, const int *__restrict__ head, const int *__restrict__ hpos,
                                      int V, int *__restrict__ cluster_of, int *__restrict__ cstart) {
     if (dev_tid() >= V) return;
     const long i = dev_tid();
     const int v = sidx[i];
-    if (skey[i] == MS_KEY_NONE) { cluster_of[v] = -1; return; }
+    if (skey[i] == VC_KEY_NONE) { cluster_of[v] = -1; return; }
     const int c = hpos[i] + head[i] - 1;                       // the heads up to and including this position, less one
     cluster_of[v] = c;
     if (head[i]) cstart[c] = (int)i;
 }
 
 // a kept face names validated, finite, referenced vertices: each has a cluster
-__global__ void ms_face_live_kernel(const int32_t *__restrict__ faces, int F, const int *__restrict__ keep, const int *__restrict__ cluster_of,
+__global__ void vc_face_live_kernel(const int32_t *__restrict__ faces, int F, const int *__restrict__ keep, const int *__restrict__ cluster_of,
                                     int *__restrict__ live) {
     if (dev_tid() >= F) return;
     const long f = dev_tid();
@@ -172,7 +153,7 @@ __global__ void ms_face_live_kernel(const int32_t *__restrict__ faces, int F, co
     live[f] = l;
 }
 
-__global__ void ms_compact_live_kernel(const int32_t *__restrict__ faces, int F, const int *__restrict__ live, const int *__restrict__ lpos,
+__global__ void vc_compact_live_kernel(const int32_t *__restrict__ faces, int F, const int *__restrict__ live, const int *__restrict__ lpos,
                                        const int *__restrict__ cluster_of, int32_t *__restrict__ out) {
     if (dev_tid() >= F || !live[dev_tid()]) return;
     const long f = dev_tid(), n = lpos[f];                     // n <= f
@@ -181,12 +162,12 @@ __global__ void ms_compact_live_kernel(const int32_t *__restrict__ faces, int F,
 }
 
 // one lane per cluster: the sum of its members in ascending vertex index
-__global__ void ms_mean_kernel(const double *__restrict__ vertices, const ms_u64 *__restrict__ skey, const int *__restrict__ sidx, int V,
+__global__ void vc_mean_kernel(const double *__restrict__ vertices, const vc_u64 *__restrict__ skey, const int *__restrict__ sidx, int V,
                                const int *__restrict__ cstart, int C, double *__restrict__ mean) {
     if (dev_tid() >= C) return;
     const long c = dev_tid();
     long i = cstart[c];
-    const ms_u64 k = skey[i];
+    const vc_u64 k = skey[i];
     double sx = 0.0, sy = 0.0, sz = 0.0, n = 0.0;
     for (; i < V && skey[i] == k; ++i) {
         const long v = sidx[i];
@@ -196,7 +177,7 @@ __global__ void ms_mean_kernel(const double *__restrict__ vertices, const ms_u64
     mean[3 * c] = sx / n; mean[3 * c + 1] = sy / n; mean[3 * c + 2] = sz / n;
 }
 
-__global__ void ms_corner_records_kernel(const int32_t *__restrict__ faces, int F, const int *__restrict__ keep, const int *__restrict__ kpos,
+__global__ void vc_corner_records_kernel(const int32_t *__restrict__ faces, int F, const int *__restrict__ keep, const int *__restrict__ kpos,
                                          const int *__restrict__ cluster_of, unsigned *__restrict__ rkey, int *__restrict__ rval) {
     if (dev_tid() >= F || !keep[dev_tid()]) return;
     const long f = dev_tid(), n = kpos[f];
@@ -207,7 +188,7 @@ __global__ void ms_corner_records_kernel(const int32_t *__restrict__ faces, int 
     }
 }
 
-__global__ void ms_record_heads_kernel(const unsigned *__restrict__ rkey, int n, int C, int *__restrict__ rstart) {
+__global__ void vc_record_heads_kernel(const unsigned *__restrict__ rkey, int n, int C, int *__restrict__ rstart) {
     if (dev_tid() >= n) return;
     const long i = dev_tid();
     const unsigned k = rkey[i];
@@ -216,7 +197,7 @@ __global__ void ms_record_heads_kernel(const unsigned *__restrict__ rkey, int n,
 
 // one Jacobi rotation of the pair (p, q); r is the third index (csrc/cloudnormals.hip: cnrm_rotate, kept as a copy so that file's
 // code stays as its tests pinned it)
-__device__ __forceinline__ void ms_rotate(double &app, double &aqq, double &apq, double &arp, double &arq, double &v0p, double &v0q, double &v1p,
+__device__ __forceinline__ void vc_rotate(double &app, double &aqq, double &apq, double &arp, double &arq, double &v0p, double &v0q, double &v1p,
                                           double &v1q, double &v2p, double &v2q) {
     if (apq == 0.0) return;
     const double theta = (aqq - app) / (2.0 * apq);
@@ -238,15 +219,15 @@ __device__ __forceinline__ void ms_rotate(double &app, double &aqq, double &apq,
 
 // one lane per cluster: its records in ascending 3 f + corner, then the solve.  rep holds the mean on entry and the representative
 // on return.
-__global__ void __launch_bounds__(256) ms_quadric_kernel(const double *__restrict__ vertices, const int32_t *__restrict__ faces, const ms_u64 *__restrict__ skey,
+__global__ void __launch_bounds__(256) vc_quadric_kernel(const double *__restrict__ vertices, const int32_t *__restrict__ faces, const vc_u64 *__restrict__ skey,
                                                          const int *__restrict__ cstart, const unsigned *__restrict__ rkey, const int *__restrict__ rval, int n,
                                                          const int *__restrict__ rstart, int C, const double *__restrict__ org, double cell, double rank_tol,
                                                          double *__restrict__ rep, int *cnt) {
     if (dev_tid() >= C) return;
     const long c = dev_tid();
-    const ms_u64 key = skey[cstart[c]];
-    const ms_u64 mask = (1ull << MS_KBITS) - 1;
-    const double cx = org[0] + ((double)(key >> (2 * MS_KBITS)) + 0.5) * cell, cy = org[1] + ((double)((key >> MS_KBITS) & mask) + 0.5) * cell,
+    const vc_u64 key = skey[cstart[c]];
+    const vc_u64 mask = (1ull << VC_KBITS) - 1;
+    const double cx = org[0] + ((double)(key >> (2 * VC_KBITS)) + 0.5) * cell, cy = org[1] + ((double)((key >> VC_KBITS) & mask) + 0.5) * cell,
                  cz = org[2] + ((double)(key & mask) + 0.5) * cell;
     double a00 = 0.0, a01 = 0.0, a02 = 0.0, a11 = 0.0, a12 = 0.0, a22 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0;
     long i = rstart[c];
@@ -274,9 +255,9 @@ __global__ void __launch_bounds__(256) ms_quadric_kernel(const double *__restric
     double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;   // v[row][column]
 #pragma unroll 1
     for (int sweep = 0; sweep < 6; ++sweep) {
-        ms_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);      // (p, q) = (0, 1), r = 2
-        ms_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);      // (0, 2), r = 1
-        ms_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);      // (1, 2), r = 0
+        vc_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);      // (p, q) = (0, 1), r = 2
+        vc_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);      // (0, 2), r = 1
+        vc_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);      // (1, 2), r = 0
     }
     double lmax = a00;
     if (a11 > lmax) lmax = a11;
@@ -290,17 +271,17 @@ __global__ void __launch_bounds__(256) ms_quadric_kernel(const double *__restric
     }
     const double x0 = m0 + e0, x1 = m1 + e1, x2 = m2 + e2;
     const bool ok = isfinite(x0) && isfinite(x1) && isfinite(x2) && fabs(x0 - m0) <= cell && fabs(x1 - m1) <= cell && fabs(x2 - m2) <= cell;
-    if (!ok) { atomicAdd(cnt + MS_FALLBACK, 1); return; }      // an integer count has no order; rep keeps the mean
+    if (!ok) { atomicAdd(cnt + VC_FALLBACK, 1); return; }      // an integer count has no order; rep keeps the mean
     rep[3 * c] = cx + x0; rep[3 * c + 1] = cy + x1; rep[3 * c + 2] = cz + x2;
 }
 
 // names are cluster numbers the library made, below C
-__global__ void ms_mark_named_kernel(const int32_t *__restrict__ names, long n, int *__restrict__ named) {
+__global__ void vc_mark_named_kernel(const int32_t *__restrict__ names, long n, int *__restrict__ named) {
     if (dev_tid() >= n) return;
     named[names[dev_tid()]] = 1;                               // every writer stores the same 1
 }
 
-__global__ void ms_out_vertices_kernel(const double *__restrict__ rep, int C, const int *__restrict__ named, const int *__restrict__ newid,
+__global__ void vc_out_vertices_kernel(const double *__restrict__ rep, int C, const int *__restrict__ named, const int *__restrict__ newid,
                                        double *__restrict__ out) {
     if (dev_tid() >= C || !named[dev_tid()]) return;
     const long c = dev_tid(), n = newid[c];                    // n <= c < C <= V
@@ -308,67 +289,28 @@ __global__ void ms_out_vertices_kernel(const double *__restrict__ rep, int C, co
     for (int j = 0; j < 3; ++j) out[3 * n + j] = rep[3 * c + j];
 }
 
-__global__ void ms_out_faces_kernel(const int32_t *__restrict__ names, long n, const int *__restrict__ newid, int32_t *__restrict__ out) {
+__global__ void vc_out_faces_kernel(const int32_t *__restrict__ names, long n, const int *__restrict__ newid, int32_t *__restrict__ out) {
     if (dev_tid() >= n) return;
     out[dev_tid()] = newid[names[dev_tid()]];
 }
 
-__global__ void ms_vertex_map_kernel(const int *__restrict__ cluster_of, int V, const int *__restrict__ named, const int *__restrict__ newid,
+__global__ void vc_vertex_map_kernel(const int *__restrict__ cluster_of, int V, const int *__restrict__ named, const int *__restrict__ newid,
                                      int32_t *__restrict__ map) {
     if (dev_tid() >= V) return;
     const int c = cluster_of[dev_tid()];
     map[dev_tid()] = (c >= 0 && named[c]) ? newid[c] : -1;
 }
 
-namespace {
-
-template <class T>
-size_t ms_slot(long n) { return (dev_bytes<T>(n) + 255) & ~(size_t)255; }
-
-// the temporaries of one stage, carved from one block of the call's DeviceScratch (csrc/meshclean.hip: McArena)
-class MsArena {
-    char *base = nullptr;
-    size_t size = 0, used = 0;
-  public:
-    int open(DeviceScratch &scratch, size_t bytes) {
-        size = bytes; used = 0;
-        return scratch.get(&base, (long)bytes);
-    }
-    template <class T>
-    int get(T **ptr, long n) {
-        const size_t b = ms_slot<T>(n);
-        if (used + b > size) SURFD_FAIL(SURFD_ERR_STATE, "meshsimplify: the arena of the call is too small (%zu + %zu > %zu bytes)", used, b, size);
-        *ptr = (T *)(base + used);
-        used += b;
-        return SURFD_OK;
-    }
-};
-
-int ms_read(const int *cnt, int *host, hipStream_t st) {
-    HIP_TRY(hipMemcpyAsync(host, cnt, MS_WORDS * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return SURFD_OK;
-}
-
-}  // namespace
-
 }  // namespace surfd
 
 using namespace surfd;
-
-#define MS_LAUNCH(kernel, n, ...)                                                              \
-    do {                                                                                       \
-        hipLaunchKernelGGL(kernel, dim3(dev_grid(n)), dim3(256), 0, st, __VA_ARGS__);          \
-        LAUNCH_CHECK();                                                                        \
-    } while (0)
 
 extern "C" int surfd_meshsimplify_cluster(const double *vertices, int V, const int32_t *faces, int F, const double *origin, double cell, int representative,
                                           double rank_tol, double *out_vertices, int32_t *out_faces, int32_t *vertex_map, int64_t *counts, surfd_stream s) {
     const char *who = "surfd_meshsimplify_cluster";
     if (!counts) SURFD_FAIL(SURFD_ERR_ARG, "%s: null argument", who);
     for (int i = 0; i < 6; ++i) counts[i] = 0;
-    if (F < 0 || V < 0) SURFD_FAIL(SURFD_ERR_ARG, "%s: F = %d, V = %d must not be negative", who, F, V);
-    if ((long)F * 3 > (long)INT_MAX) SURFD_FAIL(SURFD_ERR_UNSUPPORTED, "%s: 3 F must stay below 2^31, F = %d", who, F);      // V is an int: below 2^31
+    SURFD_TRY(mesh_sizes(who, F, V, SURFD_ERR_UNSUPPORTED));
     if (!(cell > 0.0) || !std::isfinite(cell)) SURFD_FAIL(SURFD_ERR_ARG, "%s: cell = %g must be positive and finite", who, cell);
     if (!(rank_tol > 0.0) || !std::isfinite(rank_tol)) SURFD_FAIL(SURFD_ERR_ARG, "%s: rank_tol = %g must be positive and finite", who, rank_tol);
     if (representative != SURFD_SIMPLIFY_MEAN && representative != SURFD_SIMPLIFY_QUADRIC)
@@ -384,45 +326,44 @@ extern "C" int surfd_meshsimplify_cluster(const double *vertices, int V, const i
     DeviceScratch scratch;
     CubWorkspace cub{&scratch};
     int *cnt, *nonfinite, *used, *idxa, *sidx, *head, *hpos, *cluster_of, *cstart, *keep, *kpos, *live, *lpos;
-    ms_u64 *key, *skey, *omin;
+    vc_u64 *key, *skey, *omin;
     double *org;
     int32_t *fbuf;
-    MsArena arena;
-    SURFD_TRY(arena.open(scratch, ms_slot<int>(MS_WORDS) + ms_slot<ms_u64>(3) + ms_slot<double>(3) + 8 * ms_slot<int>(V) + 2 * ms_slot<ms_u64>(V) +
-                                      4 * ms_slot<int>(F) + ms_slot<int32_t>(3L * F)));
-    SURFD_TRY(arena.get(&cnt, MS_WORDS)); SURFD_TRY(arena.get(&omin, 3)); SURFD_TRY(arena.get(&org, 3));
+    ScratchArena arena("meshsimplify");
+    SURFD_TRY(arena.open(scratch, dev_slot<int>(VC_WORDS) + dev_slot<vc_u64>(3) + dev_slot<double>(3) + 8 * dev_slot<int>(V) + 2 * dev_slot<vc_u64>(V) +
+                                      4 * dev_slot<int>(F) + dev_slot<int32_t>(3L * F)));
+    SURFD_TRY(zeroed_words(arena, &cnt, VC_WORDS, st)); SURFD_TRY(arena.get(&omin, 3)); SURFD_TRY(arena.get(&org, 3));
     SURFD_TRY(arena.get(&nonfinite, V)); SURFD_TRY(arena.get(&used, V)); SURFD_TRY(arena.get(&idxa, V)); SURFD_TRY(arena.get(&sidx, V));
     SURFD_TRY(arena.get(&head, V)); SURFD_TRY(arena.get(&hpos, V)); SURFD_TRY(arena.get(&cluster_of, V)); SURFD_TRY(arena.get(&cstart, V));
     SURFD_TRY(arena.get(&key, V)); SURFD_TRY(arena.get(&skey, V));
     SURFD_TRY(arena.get(&keep, F)); SURFD_TRY(arena.get(&kpos, F)); SURFD_TRY(arena.get(&live, F)); SURFD_TRY(arena.get(&lpos, F));
     SURFD_TRY(arena.get(&fbuf, 3L * F));
-    HIP_TRY(hipMemsetAsync(cnt, 0, MS_WORDS * sizeof(int), st));
-    HIP_TRY(hipMemsetAsync(omin, 0xFF, 3 * sizeof(ms_u64), st));
+    HIP_TRY(hipMemsetAsync(omin, 0xFF, 3 * sizeof(vc_u64), st));
     HIP_TRY(hipMemsetAsync(used, 0, dev_bytes<int>(V), st));
-    MS_LAUNCH(ms_vertex_flags_kernel, V, vertices, V, nonfinite);
-    MS_LAUNCH(ms_face_mark_kernel, F, faces, F, V, (const int *)nonfinite, keep, used, cnt);
-    if (!origin) MS_LAUNCH(ms_origin_min_kernel, V, vertices, V, (const int *)used, omin);
-    hipLaunchKernelGGL(ms_origin_set_kernel, dim3(1), dim3(64), 0, st, (const ms_u64 *)omin, origin ? 1 : 0, origin ? origin[0] : 0.0, origin ? origin[1] : 0.0,
+    DEV_LAUNCH(vc_vertex_flags_kernel, V, vertices, V, nonfinite);
+    DEV_LAUNCH(face_mark_kernel, F, faces, F, V, (const int *)nonfinite, keep, used, cnt + VC_BAD);
+    if (!origin) DEV_LAUNCH(vc_origin_min_kernel, V, vertices, V, (const int *)used, omin);
+    hipLaunchKernelGGL(vc_origin_set_kernel, dim3(1), dim3(64), 0, st, (const vc_u64 *)omin, origin ? 1 : 0, origin ? origin[0] : 0.0, origin ? origin[1] : 0.0,
                        origin ? origin[2] : 0.0, org);
     LAUNCH_CHECK();
-    MS_LAUNCH(ms_keys_kernel, V, vertices, V, (const int *)used, (const double *)org, cell, key, idxa, cnt);
+    DEV_LAUNCH(vc_keys_kernel, V, vertices, V, (const int *)used, (const double *)org, cell, key, idxa, cnt);
     SURFD_TRY(cub.sort_pairs(key, skey, idxa, sidx, V, 64, st));
-    MS_LAUNCH(ms_heads_kernel, V, (const ms_u64 *)skey, V, head);
+    DEV_LAUNCH(run_heads_kernel<VC_KEY_NONE>, V, (const vc_u64 *)skey, V, head);
     SURFD_TRY(cub.exclusive_sum(head, hpos, V, st));
-    SURFD_TRY(scan_total(head, hpos, V, cnt + MS_C, st));
-    MS_LAUNCH(ms_cluster_of_kernel, V, (const ms_u64 *)skey, (const int *)sidx, (const int *)head, (const int *)hpos, V, cluster_of, cstart);
-    MS_LAUNCH(ms_face_live_kernel, F, faces, F, (const int *)keep, (const int *)cluster_of, live);
+    SURFD_TRY(scan_total(head, hpos, V, cnt + VC_C, st));
+    DEV_LAUNCH(vc_cluster_of_kernel, V, (const vc_u64 *)skey, (const int *)sidx, (const int *)head, (const int *)hpos, V, cluster_of, cstart);
+    DEV_LAUNCH(vc_face_live_kernel, F, faces, F, (const int *)keep, (const int *)cluster_of, live);
     SURFD_TRY(cub.exclusive_sum(keep, kpos, F, st));
-    SURFD_TRY(scan_total(keep, kpos, F, cnt + MS_KEPT, st));
+    SURFD_TRY(scan_total(keep, kpos, F, cnt + VC_KEPT, st));
     SURFD_TRY(cub.exclusive_sum(live, lpos, F, st));
-    SURFD_TRY(scan_total(live, lpos, F, cnt + MS_LIVE, st));
-    MS_LAUNCH(ms_compact_live_kernel, F, faces, F, (const int *)live, (const int *)lpos, (const int *)cluster_of, fbuf);
-    int hc[MS_WORDS];
-    SURFD_TRY(ms_read(cnt, hc, st));                         // host read 1
-    if (hc[MS_BAD]) return mesh_bad_index(who, V);
-    if (hc[MS_RANGE])
+    SURFD_TRY(scan_total(live, lpos, F, cnt + VC_LIVE, st));
+    DEV_LAUNCH(vc_compact_live_kernel, F, faces, F, (const int *)live, (const int *)lpos, (const int *)cluster_of, fbuf);
+    int hc[VC_WORDS];
+    SURFD_TRY(read_words(cnt, hc, VC_WORDS, st));                         // host read 1
+    if (hc[VC_BAD]) return mesh_bad_index(who, V);
+    if (hc[VC_RANGE])
         SURFD_FAIL(SURFD_ERR_ARG, "%s: a cell index floor((x - origin) / %g) falls outside [0, 2^21): beyond the range of the keys", who, cell);
-    const int Cn = hc[MS_C], kept = hc[MS_KEPT], F1 = hc[MS_LIVE];
+    const int Cn = hc[VC_C], kept = hc[VC_KEPT], F1 = hc[VC_LIVE];
     counts[2] = Cn;
     counts[3] = (int64_t)kept - F1;
     if (Cn == 0) return SURFD_OK;                            // every face named a non-finite vertex
@@ -432,36 +373,36 @@ extern "C" int surfd_meshsimplify_cluster(const double *vertices, int V, const i
     int *named, *newid, *rstart, *rval, *rvals;
     unsigned *rkey, *rkeys;
     int32_t *dbuf;
-    MsArena stage;
-    SURFD_TRY(stage.open(scratch, ms_slot<double>(3L * Cn) + 3 * ms_slot<int>(Cn) + ms_slot<int32_t>(3L * F1) + 2 * ms_slot<int>(R) + 2 * ms_slot<unsigned>(R)));
+    ScratchArena stage("meshsimplify");
+    SURFD_TRY(stage.open(scratch, dev_slot<double>(3L * Cn) + 3 * dev_slot<int>(Cn) + dev_slot<int32_t>(3L * F1) + 2 * dev_slot<int>(R) + 2 * dev_slot<unsigned>(R)));
     SURFD_TRY(stage.get(&rep, 3L * Cn)); SURFD_TRY(stage.get(&named, Cn)); SURFD_TRY(stage.get(&newid, Cn)); SURFD_TRY(stage.get(&rstart, Cn));
     SURFD_TRY(stage.get(&dbuf, 3L * F1));
     SURFD_TRY(stage.get(&rval, R)); SURFD_TRY(stage.get(&rvals, R)); SURFD_TRY(stage.get(&rkey, R)); SURFD_TRY(stage.get(&rkeys, R));
-    MS_LAUNCH(ms_mean_kernel, Cn, vertices, (const ms_u64 *)skey, (const int *)sidx, V, (const int *)cstart, Cn, rep);
+    DEV_LAUNCH(vc_mean_kernel, Cn, vertices, (const vc_u64 *)skey, (const int *)sidx, V, (const int *)cstart, Cn, rep);
     if (representative == SURFD_SIMPLIFY_QUADRIC) {
-        MS_LAUNCH(ms_corner_records_kernel, F, faces, F, (const int *)keep, (const int *)kpos, (const int *)cluster_of, rkey, rval);
+        DEV_LAUNCH(vc_corner_records_kernel, F, faces, F, (const int *)keep, (const int *)kpos, (const int *)cluster_of, rkey, rval);
         int bits = 0;                                        // of a cluster number below C
         while ((1L << bits) < Cn) ++bits;
         if (bits > 0) SURFD_TRY(cub.sort_pairs(rkey, rkeys, rval, rvals, R, bits, st));
         else { rkeys = rkey; rvals = rval; }                 // one cluster: the records are in order, and a sort over no bits writes nothing
         HIP_TRY(hipMemsetAsync(rstart, 0xFF, dev_bytes<int>(Cn), st));
-        MS_LAUNCH(ms_record_heads_kernel, R, (const unsigned *)rkeys, R, Cn, rstart);
-        MS_LAUNCH(ms_quadric_kernel, Cn, vertices, faces, (const ms_u64 *)skey, (const int *)cstart, (const unsigned *)rkeys, (const int *)rvals, R,
+        DEV_LAUNCH(vc_record_heads_kernel, R, (const unsigned *)rkeys, R, Cn, rstart);
+        DEV_LAUNCH(vc_quadric_kernel, Cn, vertices, faces, (const vc_u64 *)skey, (const int *)cstart, (const unsigned *)rkeys, (const int *)rvals, R,
                   (const int *)rstart, Cn, (const double *)org, cell, rank_tol, rep, cnt);
     }
     int64_t F2 = 0;
     if (F1 > 0) SURFD_TRY(surfd_meshclean_drop_duplicate_faces(fbuf, F1, dbuf, &F2, s));      // host read 2 (its own)
     HIP_TRY(hipMemsetAsync(named, 0, dev_bytes<int>(Cn), st));
-    if (F2 > 0) MS_LAUNCH(ms_mark_named_kernel, 3 * F2, (const int32_t *)dbuf, 3L * F2, named);
+    if (F2 > 0) DEV_LAUNCH(vc_mark_named_kernel, 3 * F2, (const int32_t *)dbuf, 3L * F2, named);
     SURFD_TRY(cub.exclusive_sum(named, newid, Cn, st));
-    SURFD_TRY(scan_total(named, newid, Cn, cnt + MS_VOUT, st));
-    MS_LAUNCH(ms_out_vertices_kernel, Cn, (const double *)rep, Cn, (const int *)named, (const int *)newid, out_vertices);
-    if (F2 > 0) MS_LAUNCH(ms_out_faces_kernel, 3 * F2, (const int32_t *)dbuf, 3L * F2, (const int *)newid, out_faces);
-    if (vertex_map) MS_LAUNCH(ms_vertex_map_kernel, V, (const int *)cluster_of, V, (const int *)named, (const int *)newid, vertex_map);
-    SURFD_TRY(ms_read(cnt, hc, st));                         // host read 3
-    counts[0] = hc[MS_VOUT];
+    SURFD_TRY(scan_total(named, newid, Cn, cnt + VC_VOUT, st));
+    DEV_LAUNCH(vc_out_vertices_kernel, Cn, (const double *)rep, Cn, (const int *)named, (const int *)newid, out_vertices);
+    if (F2 > 0) DEV_LAUNCH(vc_out_faces_kernel, 3 * F2, (const int32_t *)dbuf, 3L * F2, (const int *)newid, out_faces);
+    if (vertex_map) DEV_LAUNCH(vc_vertex_map_kernel, V, (const int *)cluster_of, V, (const int *)named, (const int *)newid, vertex_map);
+    SURFD_TRY(read_words(cnt, hc, VC_WORDS, st));                         // host read 3
+    counts[0] = hc[VC_VOUT];
     counts[1] = F2;
     counts[4] = (int64_t)F1 - F2;
-    counts[5] = hc[MS_FALLBACK];
+    counts[5] = hc[VC_FALLBACK];
     return SURFD_OK;
 }

@@ -292,9 +292,8 @@ static void ms_free(surfd_meshsmooth *m) {
 extern "C" int surfd_meshsmooth_create(const int32_t *triangles, int F, int V, surfd_stream s, surfd_meshsmooth **out) {
     if (!out) SURFD_FAIL(SURFD_ERR_ARG, "surfd_meshsmooth_create: null argument");
     *out = nullptr;
-    if (F < 0 || V < 0) SURFD_FAIL(SURFD_ERR_ARG, "surfd_meshsmooth_create: F = %d, V = %d must not be negative", F, V);
+    SURFD_TRY(mesh_sizes("surfd_meshsmooth_create", F, V));
     if (F > 0 && !triangles) SURFD_FAIL(SURFD_ERR_ARG, "surfd_meshsmooth_create: null argument");
-    if ((long)F * 3 > (long)INT_MAX) SURFD_FAIL(SURFD_ERR_ARG, "surfd_meshsmooth_create: 3 F must stay below 2^31, F = %d", F);
     hipStream_t st = as_stream(s);
     std::unique_ptr<surfd_meshsmooth, void (*)(surfd_meshsmooth *)> owner(new surfd_meshsmooth(), ms_free);      // freed on every early return
     surfd_meshsmooth *m = owner.get();
@@ -322,49 +321,36 @@ extern "C" int surfd_meshsmooth_create(const int32_t *triangles, int F, int V, s
     SURFD_TRY(scratch.get(&hborder, H)); SURFD_TRY(scratch.get(&vflag, V)); SURFD_TRY(scratch.get(&scal, 4));
     HIP_TRY(hipMemsetAsync(scal, 0, 4 * sizeof(int), st));
     HIP_TRY(hipMemcpyAsync(m->tri, triangles, (size_t)H * sizeof(int32_t), hipMemcpyDefault, st));
-    hipLaunchKernelGGL(ms_keys_kernel, dim3(dev_grid(F)), dim3(256), 0, st, (const int32_t *)m->tri, F, V, ekey, eh, okey, ikey, ckey, cpay, scal);
-    LAUNCH_CHECK();
+    DEV_LAUNCH(ms_keys_kernel, F, (const int32_t *)m->tri, F, V, ekey, eh, okey, ikey, ckey, cpay, scal);
     SURFD_TRY(cub.sort_pairs(ekey, ekey2, eh, eh2, H, 64, st));
-    hipLaunchKernelGGL(ms_border_flags_kernel, dim3(dev_grid(H)), dim3(256), 0, st, (const ms_u64 *)ekey2, H, flag);
-    LAUNCH_CHECK();
+    DEV_LAUNCH(ms_border_flags_kernel, H, (const ms_u64 *)ekey2, H, flag);
     SURFD_TRY(cub.exclusive_sum(flag, rank, H, st));
     SURFD_TRY(scan_total(flag, rank, H, scal + 1, st));
     int hs[4];
-    HIP_TRY(hipMemcpyAsync(hs, scal, sizeof(hs), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    SURFD_TRY(read_words(scal, hs, 4, st));
     if (hs[0]) return mesh_bad_index("surfd_meshsmooth_create", V);        // nothing below this line sees an unvalidated index
     const int B = m->B = hs[1];
     HIP_TRY(hipMalloc(&m->bnbr, dev_bytes<int>(2L * B)));
     SURFD_TRY(scratch.get(&bsrc, 2L * B));
     SURFD_TRY(scratch.get(&bdst, 2L * B));
-    hipLaunchKernelGGL(ms_border_records_kernel, dim3(dev_grid(H)), dim3(256), 0, st, (const ms_u64 *)ekey2, (const int *)eh2, (const int *)flag,
-                       (const int *)rank, H, B, hborder, bsrc, bdst);
-    LAUNCH_CHECK();
+    DEV_LAUNCH(ms_border_records_kernel, H, (const ms_u64 *)ekey2, (const int *)eh2, (const int *)flag, (const int *)rank, H, B, hborder, bsrc, bdst);
     // BN: the sorted keys (2 B <= 2 H words) go to ekey (8 H bytes), which the first sort has read and nothing needs any more
     unsigned *bsorted = (unsigned *)ekey;
     if (B > 0) SURFD_TRY(cub.sort_pairs(bsrc, bsorted, bdst, m->bnbr, 2 * B, 32, st));
-    hipLaunchKernelGGL(ms_offsets_kernel, dim3(dev_grid(V + 1L)), dim3(256), 0, st, (const unsigned *)bsorted, 2u * (unsigned)B, V, 0u, m->boff);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(ms_vertex_border_kernel, dim3(dev_grid(V)), dim3(256), 0, st, (const unsigned *)m->boff, V, m->vborder, vflag);
-    LAUNCH_CHECK();
+    DEV_LAUNCH(ms_offsets_kernel, V + 1L, (const unsigned *)bsorted, 2u * (unsigned)B, V, 0u, m->boff);
+    DEV_LAUNCH(ms_vertex_border_kernel, V, (const unsigned *)m->boff, V, m->vborder, vflag);
     if (V > 0) SURFD_TRY(cub.reduce_sum(vflag, scal + 2, V, st));
     // OUT, IN
     for (int arriving = 0; arriving < 2; ++arriving) {
         SURFD_TRY(cub.sort_pairs(arriving ? ikey : okey, skey, eh, sh, H, 32, st));
         const long base = arriving ? H : 0;
-        hipLaunchKernelGGL(ms_offsets_kernel, dim3(dev_grid(V + 1L)), dim3(256), 0, st, (const unsigned *)skey, (unsigned)H, V, (unsigned)base,
-                           arriving ? m->ioff : m->ooff);
-        LAUNCH_CHECK();
-        hipLaunchKernelGGL(ms_adjacency_kernel, dim3(dev_grid(H)), dim3(256), 0, st, (const int32_t *)m->tri, (const int *)sh, (const unsigned char *)hborder, H,
-                           arriving, m->nbr + base, m->opp + base);
-        LAUNCH_CHECK();
+        DEV_LAUNCH(ms_offsets_kernel, V + 1L, (const unsigned *)skey, (unsigned)H, V, (unsigned)base, arriving ? m->ioff : m->ooff);
+        DEV_LAUNCH(ms_adjacency_kernel, H, (const int32_t *)m->tri, (const int *)sh, (const unsigned char *)hborder, H, arriving, m->nbr + base, m->opp + base);
     }
     // corners, ascending in (c, f) inside a vertex
     SURFD_TRY(cub.sort_pairs(ckey, skey, cpay, m->ch, H, 32, st));
-    hipLaunchKernelGGL(ms_offsets_kernel, dim3(dev_grid(V + 1L)), dim3(256), 0, st, (const unsigned *)skey, (unsigned)H, V, 0u, m->coff);
-    LAUNCH_CHECK();
-    HIP_TRY(hipMemcpyAsync(hs, scal, sizeof(hs), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));                        // the scratch is freed next
+    DEV_LAUNCH(ms_offsets_kernel, V + 1L, (const unsigned *)skey, (unsigned)H, V, 0u, m->coff);
+    SURFD_TRY(read_words(scal, hs, 4, st));                   // the scratch is freed next
     m->n_border_vertices = hs[2];
     *out = owner.release();
     return SURFD_OK;
@@ -403,8 +389,7 @@ int ms_import(const void *vertices, int dtype, long n, double *dst, hipStream_t 
     if (dtype == SURFD_MESHSMOOTH_F64) {
         if (vertices != (const void *)dst) HIP_TRY(hipMemcpyAsync(dst, vertices, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
     } else {
-        hipLaunchKernelGGL(ms_convert_kernel<float>, dim3(dev_grid(n)), dim3(256), 0, st, (const float *)vertices, n, dst);
-        LAUNCH_CHECK();
+        DEV_LAUNCH(ms_convert_kernel<float>, n, (const float *)vertices, n, dst);
     }
     return SURFD_OK;
 }
@@ -435,9 +420,7 @@ extern "C" int surfd_meshsmooth_laplacian(surfd_meshsmooth *m, const void *verti
     for (int i = 0; i < steps; ++i) {
         double *dst = i == steps - 1 ? out : (src == buf.a ? buf.b : buf.a);
         auto kernel = cotangent ? ms_laplacian_kernel<1> : ms_laplacian_kernel<0>;
-        hipLaunchKernelGGL(kernel, dim3(dev_grid(V)), dim3(256), 0, st, src, dst, V, (const unsigned *)m->ooff, (const unsigned *)m->ioff, (const int *)m->nbr,
-                           (const int *)m->opp, vb);
-        LAUNCH_CHECK();
+        DEV_LAUNCH(kernel, V, src, dst, V, (const unsigned *)m->ooff, (const unsigned *)m->ioff, (const int *)m->nbr, (const int *)m->opp, vb);
         src = dst;
     }
     return SURFD_OK;
@@ -460,9 +443,8 @@ extern "C" int surfd_meshsmooth_umbrella(surfd_meshsmooth *m, const void *vertic
     const double *src = buf.a;
     for (int i = 0; i < sweeps; ++i) {
         double *dst = i == sweeps - 1 ? out : (src == buf.a ? buf.b : buf.a);
-        hipLaunchKernelGGL(ms_umbrella_kernel, dim3(dev_grid(V)), dim3(256), 0, st, src, dst, V, (const unsigned *)(border ? m->boff : m->ooff),
-                           (const unsigned *)(border ? nullptr : m->ioff), (const int *)(border ? m->bnbr : m->nbr), (i & 1) ? k1 : k0);
-        LAUNCH_CHECK();
+        DEV_LAUNCH(ms_umbrella_kernel, V, src, dst, V, (const unsigned *)(border ? m->boff : m->ooff), (const unsigned *)(border ? nullptr : m->ioff),
+                   (const int *)(border ? m->bnbr : m->nbr), (i & 1) ? k1 : k0);
         src = dst;
     }
     return SURFD_OK;
@@ -483,17 +465,15 @@ extern "C" int surfd_meshsmooth_vertex_normals(surfd_meshsmooth *m, const void *
         if (raw) HIP_TRY(hipMemsetAsync(raw, 0, (size_t)V * 3 * sizeof(double), st));
         return SURFD_OK;
     }
-    const dim3 grid(dev_grid(V)), block(256);
     const unsigned *coff = m->coff;
     const int *ch = m->ch;
     const int32_t *tri = m->tri;
     if (dtype == SURFD_MESHSMOOTH_F32) {
-        if (weight == SURFD_MESHSMOOTH_ANGLE) hipLaunchKernelGGL((ms_normals_kernel<float, 1>), grid, block, 0, st, (const float *)vertices, tri, V, coff, ch, unit, raw);
-        else hipLaunchKernelGGL((ms_normals_kernel<float, 0>), grid, block, 0, st, (const float *)vertices, tri, V, coff, ch, unit, raw);
+        if (weight == SURFD_MESHSMOOTH_ANGLE) DEV_LAUNCH((ms_normals_kernel<float, 1>), V, (const float *)vertices, tri, V, coff, ch, unit, raw);
+        else DEV_LAUNCH((ms_normals_kernel<float, 0>), V, (const float *)vertices, tri, V, coff, ch, unit, raw);
     } else {
-        if (weight == SURFD_MESHSMOOTH_ANGLE) hipLaunchKernelGGL((ms_normals_kernel<double, 1>), grid, block, 0, st, (const double *)vertices, tri, V, coff, ch, unit, raw);
-        else hipLaunchKernelGGL((ms_normals_kernel<double, 0>), grid, block, 0, st, (const double *)vertices, tri, V, coff, ch, unit, raw);
+        if (weight == SURFD_MESHSMOOTH_ANGLE) DEV_LAUNCH((ms_normals_kernel<double, 1>), V, (const double *)vertices, tri, V, coff, ch, unit, raw);
+        else DEV_LAUNCH((ms_normals_kernel<double, 0>), V, (const double *)vertices, tri, V, coff, ch, unit, raw);
     }
-    LAUNCH_CHECK();
     return SURFD_OK;
 }

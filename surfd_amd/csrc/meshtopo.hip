@@ -81,6 +81,7 @@
 // by indices that create validated; edge ids come from the exclusive sum and lie in [0, E); pair nodes lie in [0, n).
 #include "common.h"
 #include "devscratch.h"
+#include "meshedit.h"
 #include <climits>
 #include <cmath>
 
@@ -139,14 +140,9 @@ __global__ void cc_compress_kernel(int *parent, int n) {
 
 static int cc_run(int *parent, int n, const int2 *pairs, int n_pairs, hipStream_t st) {
     if (n <= 0) return SURFD_OK;
-    hipLaunchKernelGGL(mt_iota_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, parent, n);
-    LAUNCH_CHECK();
-    if (n_pairs > 0) {
-        hipLaunchKernelGGL(cc_hook_kernel, dim3((unsigned)ceil_div(n_pairs, 256)), dim3(256), 0, st, parent, pairs, n_pairs);
-        LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(cc_compress_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, parent, n);
-    LAUNCH_CHECK();
+    DEV_LAUNCH(mt_iota_kernel, n, parent, n);
+    if (n_pairs > 0) DEV_LAUNCH(cc_hook_kernel, n_pairs, parent, pairs, n_pairs);
+    DEV_LAUNCH(cc_compress_kernel, n, parent, n);
     return SURFD_OK;
 }
 
@@ -170,13 +166,6 @@ __global__ void mt_keys_kernel(const int32_t *__restrict__ tri, int F, int V, u6
         hidx[h] = (int)h;
         if (!bad && !deg && atomicExch(used + a, 1) == 0) atomicAdd(cnt + MT_CNT_REFERENCED, 1);
     }
-}
-
-__global__ void mt_heads_kernel(const u64 *__restrict__ skeys, int n, int *__restrict__ head) {
-    if (dev_tid() >= n) return;
-    const int i = (int)dev_tid();
-    const u64 k = skeys[i];
-    head[i] = (k != MT_KEY_NONE && (i == 0 || skeys[i - 1] != k)) ? 1 : 0;
 }
 
 __global__ void mt_fill_kernel(const u64 *__restrict__ skeys, const int *__restrict__ shidx, const int *__restrict__ head,
@@ -419,14 +408,6 @@ __global__ void mt_weld_heads_kernel(const float *__restrict__ vertices, int V, 
     headpos[i] = same ? 0 : i;
 }
 
-__global__ void mt_weld_rep_kernel(int V, const int *__restrict__ idx, const int *__restrict__ headpos, int *__restrict__ rep, int *__restrict__ survives) {
-    if (dev_tid() >= V) return;
-    const int i = (int)dev_tid();
-    const int v = idx[i], r = idx[headpos[i]];
-    rep[v] = r;
-    survives[v] = v == r ? 1 : 0;
-}
-
 __global__ void mt_weld_map_kernel(int V, const int *__restrict__ rep, const int *__restrict__ survives, const int *__restrict__ newidx,
                                    int32_t *__restrict__ vertex_map, unsigned char *__restrict__ survivor) {
     if (dev_tid() >= V) return;
@@ -469,9 +450,8 @@ static void mt_free(surfd_meshtopo *m) {
 extern "C" int surfd_meshtopo_create(const int32_t *triangles, int F, int V, surfd_stream s, surfd_meshtopo **out) {
     if (!out) SURFD_FAIL(SURFD_ERR_ARG, "surfd_meshtopo_create: null argument");
     *out = nullptr;
-    if (F < 0 || V < 0) SURFD_FAIL(SURFD_ERR_ARG, "surfd_meshtopo_create: F = %d, V = %d must not be negative", F, V);
+    SURFD_TRY(mesh_sizes("surfd_meshtopo_create", F, V));
     if (F > 0 && !triangles) SURFD_FAIL(SURFD_ERR_ARG, "surfd_meshtopo_create: null argument");
-    if ((long)F * 3 > (long)INT_MAX) SURFD_FAIL(SURFD_ERR_ARG, "surfd_meshtopo_create: 3 F must stay below 2^31, F = %d", F);
     hipStream_t st = as_stream(s);
     std::unique_ptr<surfd_meshtopo, void (*)(surfd_meshtopo *)> owner(new surfd_meshtopo(), mt_free);      // freed on every early return
     surfd_meshtopo *m = owner.get();
@@ -501,16 +481,13 @@ extern "C" int surfd_meshtopo_create(const int32_t *triangles, int F, int V, sur
     HIP_TRY(hipMemcpyAsync(cnt, cnt0, sizeof(cnt0), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(m->face_edges, 0xFF, dev_bytes<int32_t>(n3), st));
     HIP_TRY(hipMemsetAsync(m->face_neighbors, 0xFF, dev_bytes<int32_t>(n3), st));
-    hipLaunchKernelGGL(mt_keys_kernel, dim3(dev_grid(F)), dim3(256), 0, st, (const int32_t *)m->tri, F, V, keys, hidx, m->degenerate, used, cnt);
-    LAUNCH_CHECK();
+    DEV_LAUNCH(mt_keys_kernel, F, (const int32_t *)m->tri, F, V, keys, hidx, m->degenerate, used, cnt);
     SURFD_TRY(cub.sort_pairs(keys, skeys, hidx, shidx, n3, 64, st));
-    hipLaunchKernelGGL(mt_heads_kernel, dim3(dev_grid(n3)), dim3(256), 0, st, (const u64 *)skeys, n3, head);
-    LAUNCH_CHECK();
+    DEV_LAUNCH(run_heads_kernel<MT_KEY_NONE>, n3, (const u64 *)skeys, n3, head);
     SURFD_TRY(m->scan.exclusive_sum(head, excl, n3, st));     // sizes the handle's workspace: every later scan is shorter
     SURFD_TRY(scan_total(head, excl, n3, cnt + MT_CNT_E, st));
     int hc[MT_CNT_WORDS];
-    HIP_TRY(hipMemcpyAsync(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    SURFD_TRY(read_words(cnt, hc, MT_CNT_WORDS, st));
     if (hc[MT_CNT_BAD] > 0)
         SURFD_FAIL(SURFD_ERR_ARG, "surfd_meshtopo_create: %d faces name vertices outside [0, %d), the first is face %d", hc[MT_CNT_BAD], V, hc[MT_CNT_FIRST_BAD]);
     m->n_degenerate = hc[MT_CNT_DEGENERATE];
@@ -524,12 +501,10 @@ extern "C" int surfd_meshtopo_create(const int32_t *triangles, int F, int V, sur
     HIP_TRY(hipMalloc(&m->edge_halfedges, dev_bytes<int32_t>(H)));
     HIP_TRY(hipMemsetAsync(m->edge_offsets, 0, dev_bytes<int32_t>(E + 1L), st));
     if (H > 0) {
-        hipLaunchKernelGGL(mt_fill_kernel, dim3(dev_grid(H)), dim3(256), 0, st, (const u64 *)skeys, (const int *)shidx, (const int *)head, (const int *)excl,
-                           H, E, m->edges, m->edge_offsets, m->edge_halfedges, m->face_edges);
-        LAUNCH_CHECK();
-        hipLaunchKernelGGL(mt_neighbors_kernel, dim3(dev_grid(H)), dim3(256), 0, st, H, E, (const int32_t *)m->edge_offsets,
-                           (const int32_t *)m->edge_halfedges, (const int32_t *)m->face_edges, m->valence, m->face_neighbors);
-        LAUNCH_CHECK();
+        DEV_LAUNCH(mt_fill_kernel, H, (const u64 *)skeys, (const int *)shidx, (const int *)head, (const int *)excl, H, E, m->edges, m->edge_offsets,
+                   m->edge_halfedges, m->face_edges);
+        DEV_LAUNCH(mt_neighbors_kernel, H, H, E, (const int32_t *)m->edge_offsets, (const int32_t *)m->edge_halfedges, (const int32_t *)m->face_edges, m->valence,
+                   m->face_neighbors);
     }
     const long n_nodes = std::max(std::max(2L * F, (long)V), (long)E), n_pairs = std::max(3L * F, 2L * E), n_fe = std::max(F, E);
     HIP_TRY(hipMalloc(&m->parent, dev_bytes<int>(n_nodes)));
@@ -577,15 +552,12 @@ extern "C" int surfd_meshtopo_read(const surfd_meshtopo *m, int32_t *edges, int3
 
 // rootface[0 .. n) -> labels and the number of components (read back: the one sync of the call)
 static int mt_number(surfd_meshtopo *m, int n, int32_t *labels, int64_t *count, hipStream_t st) {
-    hipLaunchKernelGGL(mt_isroot_kernel, dim3(dev_grid(n)), dim3(256), 0, st, (const int *)m->rootface, n, m->isroot);
-    LAUNCH_CHECK();
+    DEV_LAUNCH(mt_isroot_kernel, n, (const int *)m->rootface, n, m->isroot);
     SURFD_TRY(m->scan.exclusive_sum(m->isroot, m->rank, n, st));      // allocates nothing: SURFD_ERR_STATE if create's size did not do
-    hipLaunchKernelGGL(mt_labels_kernel, dim3(dev_grid(n)), dim3(256), 0, st, (const int *)m->rootface, (const int *)m->rank, n, labels);
-    LAUNCH_CHECK();
+    DEV_LAUNCH(mt_labels_kernel, n, (const int *)m->rootface, (const int *)m->rank, n, labels);
     SURFD_TRY(scan_total(m->isroot, m->rank, n, m->scalars, st));
     int c = 0;
-    HIP_TRY(hipMemcpyAsync(&c, m->scalars, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    SURFD_TRY(read_words(m->scalars, &c, 1, st));
     *count = c;
     return SURFD_OK;
 }
@@ -601,25 +573,18 @@ extern "C" int surfd_meshtopo_components(surfd_meshtopo *m, int connectivity, in
     hipStream_t st = as_stream(s);
     int rc;
     if (connectivity == SURFD_MESHTOPO_VERTEX) {
-        hipLaunchKernelGGL(mt_pairs_vertex_kernel, dim3(dev_grid(F)), dim3(256), 0, st, (const int32_t *)m->tri, (const unsigned char *)m->degenerate, F, m->pairs);
-        LAUNCH_CHECK();
+        DEV_LAUNCH(mt_pairs_vertex_kernel, F, (const int32_t *)m->tri, (const unsigned char *)m->degenerate, F, m->pairs);
         if ((rc = cc_run(m->parent, V, m->pairs, 2 * F, st)) != SURFD_OK) return rc;
         HIP_TRY(hipMemsetAsync(m->vaux, 0x7F, dev_bytes<int>(V), st));         // 0x7F7F7F7F: above every face index
-        hipLaunchKernelGGL(mt_minface_kernel, dim3(dev_grid(F)), dim3(256), 0, st, (const int32_t *)m->tri, (const unsigned char *)m->degenerate, F,
-                           (const int *)m->parent, m->vaux);
-        LAUNCH_CHECK();
-        hipLaunchKernelGGL(mt_rootface_vertex_kernel, dim3(dev_grid(F)), dim3(256), 0, st, (const int32_t *)m->tri, (const unsigned char *)m->degenerate, F,
-                           (const int *)m->parent, (const int *)m->vaux, m->rootface);
-        LAUNCH_CHECK();
+        DEV_LAUNCH(mt_minface_kernel, F, (const int32_t *)m->tri, (const unsigned char *)m->degenerate, F, (const int *)m->parent, m->vaux);
+        DEV_LAUNCH(mt_rootface_vertex_kernel, F, (const int32_t *)m->tri, (const unsigned char *)m->degenerate, F, (const int *)m->parent, (const int *)m->vaux, m->rootface);
     } else {
         if (H > 0) {
-            hipLaunchKernelGGL(mt_pairs_faces_kernel, dim3(dev_grid(H)), dim3(256), 0, st, H, (const int32_t *)m->edge_offsets, (const int32_t *)m->edge_halfedges,
-                               (const int32_t *)m->face_edges, connectivity == SURFD_MESHTOPO_MANIFOLD ? 1 : 0, m->pairs);
-            LAUNCH_CHECK();
+            DEV_LAUNCH(mt_pairs_faces_kernel, H, H, (const int32_t *)m->edge_offsets, (const int32_t *)m->edge_halfedges, (const int32_t *)m->face_edges,
+                       connectivity == SURFD_MESHTOPO_MANIFOLD ? 1 : 0, m->pairs);
         }
         if ((rc = cc_run(m->parent, F, m->pairs, H, st)) != SURFD_OK) return rc;
-        hipLaunchKernelGGL(mt_rootface_faces_kernel, dim3(dev_grid(F)), dim3(256), 0, st, (const unsigned char *)m->degenerate, F, (const int *)m->parent, m->rootface);
-        LAUNCH_CHECK();
+        DEV_LAUNCH(mt_rootface_faces_kernel, F, (const unsigned char *)m->degenerate, F, (const int *)m->parent, m->rootface);
     }
     return mt_number(m, F, labels, count, st);
 }
@@ -634,15 +599,11 @@ extern "C" int surfd_meshtopo_border_loops(surfd_meshtopo *m, int32_t *labels, u
     int *vfirst = m->vaux, *vdeg = m->vaux + V;
     HIP_TRY(hipMemsetAsync(vfirst, 0x7F, dev_bytes<int>(V), st));
     HIP_TRY(hipMemsetAsync(vdeg, 0, dev_bytes<int>(V), st));
-    hipLaunchKernelGGL(mt_border_vertices_kernel, dim3(dev_grid(E)), dim3(256), 0, st, E, (const int32_t *)m->edges, (const int32_t *)m->valence, vfirst, vdeg);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(mt_pairs_border_kernel, dim3(dev_grid(E)), dim3(256), 0, st, E, (const int32_t *)m->edges, (const int32_t *)m->valence, (const int *)vfirst,
-                       (const int *)vdeg, m->pairs, irregular);
-    LAUNCH_CHECK();
+    DEV_LAUNCH(mt_border_vertices_kernel, E, E, (const int32_t *)m->edges, (const int32_t *)m->valence, vfirst, vdeg);
+    DEV_LAUNCH(mt_pairs_border_kernel, E, E, (const int32_t *)m->edges, (const int32_t *)m->valence, (const int *)vfirst, (const int *)vdeg, m->pairs, irregular);
     int rc;
     if ((rc = cc_run(m->parent, E, m->pairs, 2 * E, st)) != SURFD_OK) return rc;
-    hipLaunchKernelGGL(mt_rootface_border_kernel, dim3(dev_grid(E)), dim3(256), 0, st, (const int32_t *)m->valence, E, (const int *)m->parent, m->rootface);
-    LAUNCH_CHECK();
+    DEV_LAUNCH(mt_rootface_border_kernel, E, (const int32_t *)m->valence, E, (const int *)m->parent, m->rootface);
     return mt_number(m, E, labels, count, st);
 }
 
@@ -654,29 +615,21 @@ extern "C" int surfd_meshtopo_orient(surfd_meshtopo *m, const float *vertices, u
     if (!flip) SURFD_FAIL(SURFD_ERR_ARG, "surfd_meshtopo_orient: null argument");
     hipStream_t st = as_stream(s);
     if (E > 0) {
-        hipLaunchKernelGGL(mt_pairs_orient_kernel, dim3(dev_grid(E)), dim3(256), 0, st, E, (const int32_t *)m->edges, (const int32_t *)m->edge_offsets,
-                           (const int32_t *)m->edge_halfedges, (const int32_t *)m->tri, m->pairs);
-        LAUNCH_CHECK();
+        DEV_LAUNCH(mt_pairs_orient_kernel, E, E, (const int32_t *)m->edges, (const int32_t *)m->edge_offsets, (const int32_t *)m->edge_halfedges,
+                   (const int32_t *)m->tri, m->pairs);
     }
     int rc;
     if ((rc = cc_run(m->parent, 2 * F, m->pairs, 2 * E, st)) != SURFD_OK) return rc;
-    hipLaunchKernelGGL(mt_flip_kernel, dim3(dev_grid(F)), dim3(256), 0, st, (const unsigned char *)m->degenerate, F, (const int *)m->parent, flip, m->orientable,
-                       m->patch_face);
-    LAUNCH_CHECK();
+    DEV_LAUNCH(mt_flip_kernel, F, (const unsigned char *)m->degenerate, F, (const int *)m->parent, flip, m->orientable, m->patch_face);
     if (vertices && m->V > 0) {
         unsigned *maxbits = (unsigned *)(m->scalars + 1);
         HIP_TRY(hipMemsetAsync(maxbits, 0, sizeof(unsigned), st));
         HIP_TRY(hipMemsetAsync(m->volume, 0, dev_bytes<u64>(F), st));
         HIP_TRY(hipMemsetAsync(m->open_patch, 0, dev_bytes<int>(F), st));
-        hipLaunchKernelGGL(mt_maxabs_kernel, dim3(dev_grid(3L * m->V)), dim3(256), 0, st, vertices, 3L * m->V, maxbits);
-        LAUNCH_CHECK();
-        hipLaunchKernelGGL(mt_volume_kernel, dim3(dev_grid(F)), dim3(256), 0, st, (const int32_t *)m->tri, vertices, F, (const int32_t *)m->face_edges,
-                           (const int32_t *)m->valence, (const unsigned char *)flip, (const int32_t *)m->patch_face, (const unsigned *)maxbits, m->volume,
-                           m->open_patch);
-        LAUNCH_CHECK();
-        hipLaunchKernelGGL(mt_turn_kernel, dim3(dev_grid(F)), dim3(256), 0, st, F, (const int32_t *)m->patch_face, (const unsigned char *)m->orientable,
-                           (const u64 *)m->volume, (const int *)m->open_patch, flip);
-        LAUNCH_CHECK();
+        DEV_LAUNCH(mt_maxabs_kernel, 3L * m->V, vertices, 3L * m->V, maxbits);
+        DEV_LAUNCH(mt_volume_kernel, F, (const int32_t *)m->tri, vertices, F, (const int32_t *)m->face_edges, (const int32_t *)m->valence,
+                   (const unsigned char *)flip, (const int32_t *)m->patch_face, (const unsigned *)maxbits, m->volume, m->open_patch);
+        DEV_LAUNCH(mt_turn_kernel, F, F, (const int32_t *)m->patch_face, (const unsigned char *)m->orientable, (const u64 *)m->volume, (const int *)m->open_patch, flip);
     }
     if (orientable) HIP_TRY(hipMemcpyAsync(orientable, m->orientable, (size_t)F, hipMemcpyDeviceToDevice, st));
     if (patch_face) HIP_TRY(hipMemcpyAsync(patch_face, m->patch_face, (size_t)F * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
@@ -702,24 +655,15 @@ extern "C" int surfd_meshtopo_weld(const float *vertices, int V, int32_t *vertex
     SURFD_TRY(scratch.get(&total, 1));
     SURFD_TRY(cub.sort_pairs(kxy, kxy2, idx1, idx2, V, 64, st, true));      // the second sort is the larger: one workspace allocation
     // least significant key first; both sorts are stable, so equal vertices end up adjacent and ascending in index
-    hipLaunchKernelGGL(mt_weld_key_z_kernel, dim3(dev_grid(V)), dim3(256), 0, st, vertices, V, kz, idx0);
-    LAUNCH_CHECK();
+    DEV_LAUNCH(mt_weld_key_z_kernel, V, vertices, V, kz, idx0);
     SURFD_TRY(cub.sort_pairs(kz, kz2, idx0, idx1, V, 32, st));
-    hipLaunchKernelGGL(mt_weld_key_xy_kernel, dim3(dev_grid(V)), dim3(256), 0, st, vertices, V, (const int *)idx1, kxy);
-    LAUNCH_CHECK();
+    DEV_LAUNCH(mt_weld_key_xy_kernel, V, vertices, V, (const int *)idx1, kxy);
     SURFD_TRY(cub.sort_pairs(kxy, kxy2, idx1, idx2, V, 64, st));
-    hipLaunchKernelGGL(mt_weld_heads_kernel, dim3(dev_grid(V)), dim3(256), 0, st, vertices, V, (const int *)idx2, headpos);
-    LAUNCH_CHECK();
-    SURFD_TRY(cub.inclusive_max(headpos, hp, V, st));
-    hipLaunchKernelGGL(mt_weld_rep_kernel, dim3(dev_grid(V)), dim3(256), 0, st, V, (const int *)idx2, (const int *)hp, rep, survives);
-    LAUNCH_CHECK();
-    SURFD_TRY(cub.exclusive_sum(survives, newidx, V, st));
-    hipLaunchKernelGGL(mt_weld_map_kernel, dim3(dev_grid(V)), dim3(256), 0, st, V, (const int *)rep, (const int *)survives, (const int *)newidx, vertex_map, survivor);
-    LAUNCH_CHECK();
-    SURFD_TRY(scan_total(survives, newidx, V, total, st));
+    DEV_LAUNCH(mt_weld_heads_kernel, V, vertices, V, (const int *)idx2, headpos);
+    SURFD_TRY(group_representatives(cub, V, idx2, headpos, hp, nullptr, rep, survives, newidx, total, st));      // every vertex takes part
+    DEV_LAUNCH(mt_weld_map_kernel, V, V, (const int *)rep, (const int *)survives, (const int *)newidx, vertex_map, survivor);
     int c = 0;
-    HIP_TRY(hipMemcpyAsync(&c, total, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));                        // the scratch is freed next
+    SURFD_TRY(read_words(total, &c, 1, st));                  // the scratch is freed next
     *count = c;
     return SURFD_OK;
 }
