@@ -71,6 +71,9 @@ def parse(argv=None):
                     help="make the mesh smaller on the GPU before it is written: vertex clustering on a grid of K cells along the largest extent, "
                          "one quadric representative per occupied cell (surfd_amd.meshsimplify); needs --device_clean (open meshes) or "
                          "--watertight --device_mc")
+    ap.add_argument("--simplify_faces", type=int, default=None, metavar="N",
+                    help="make the mesh smaller on the GPU before it is written: edge collapses down to N faces, borders kept, sheets not glued "
+                         "(surfd_amd.meshsimplify.simplify_quadric_decimation); the same rules as --simplify_cells, and not together with it")
     ap.add_argument("--respacing", default="", help="e.g. ddim50 for a quick run (the reference always runs 1000 steps)")
     ap.add_argument("--seed", type=int, default=10)
     ap.add_argument("--synthetic", action="store_true", help="create synthetic checkpoints under --output_dir and use them")
@@ -84,6 +87,12 @@ def parse(argv=None):
     a = ap.parse_args(argv)
     if a.simplify_cells is not None and not (a.device_mc if a.watertight else a.device_clean):
         ap.error("--simplify_cells works on the device mesh: add --device_clean (open meshes) or --device_mc (--watertight)")
+    if a.simplify_faces is not None and a.simplify_cells is not None:
+        ap.error("--simplify_faces and --simplify_cells exclude each other")
+    if a.simplify_faces is not None and not (a.device_mc if a.watertight else a.device_clean):
+        ap.error("--simplify_faces works on the device mesh: add --device_clean (open meshes) or --device_mc (--watertight)")
+    if a.simplify_faces is not None and a.simplify_faces < 0:
+        ap.error("--simplify_faces must not be negative")
     return a
 
 
@@ -202,6 +211,9 @@ def run(a):
                 if a.simplify_cells is not None and len(faces):
                     from surfd_amd.meshsimplify import simplify_vertex_clustering
                     verts, faces = simplify_vertex_clustering(verts, faces, cells=a.simplify_cells)
+                if a.simplify_faces is not None and len(faces):
+                    from surfd_amd.meshsimplify import simplify_quadric_decimation
+                    verts, faces = simplify_quadric_decimation(verts, faces, a.simplify_faces)
                 return verts.cpu().numpy(), faces.cpu().numpy()
             if a.watertight:
                 verts, faces = get_watertight_mesh(field, a.resolution, max_batch=2 ** 16)
@@ -209,7 +221,8 @@ def run(a):
             device_clean = bool(getattr(a, "device_clean", False))
             device_post = bool(getattr(a, "device_post", False)) or device_clean
             v, t = get_mesh_from_udf(field, coords_range=(-1, 1), max_dist=0.1, N=a.resolution, max_batch=2 ** 16, differentiable=False,
-                                     device_post=device_post, device_clean=device_clean, simplify_cells=getattr(a, "simplify_cells", None))
+                                     device_post=device_post, device_clean=device_clean, simplify_cells=getattr(a, "simplify_cells", None),
+                                     simplify_faces=getattr(a, "simplify_faces", None))
             if device_post:                                   # the mesh goes to the host once, for write_obj
                 if postprocess_open_mesh(a.mode):
                     from surfd_amd import meshsmooth, meshtopo

@@ -47,6 +47,9 @@ def parse(argv=None):
                     help="make the mesh smaller on the GPU before it is written: vertex clustering on a grid of K cells along the largest extent, "
                          "one quadric representative per occupied cell (surfd_amd.meshsimplify); with --watertight it needs --device_mc, open "
                          "meshes are then cleaned on the GPU too (device_clean: the same mesh)")
+    ap.add_argument("--simplify_faces", type=int, default=None, metavar="N",
+                    help="make the mesh smaller on the GPU before it is written: edge collapses down to N faces, borders kept, sheets not glued "
+                         "(surfd_amd.meshsimplify.simplify_quadric_decimation); the same rules as --simplify_cells, and not together with it")
     ap.add_argument("--batch", type=int, default=1, help="clouds per encoder call (export_meshes.py:75 uses 1)")
     ap.add_argument("--seed", type=int, default=10)
     ap.add_argument("--output_dir", default="outputs/reconstruct")
@@ -67,6 +70,12 @@ def parse(argv=None):
     a = ap.parse_args(argv)
     if a.simplify_cells is not None and a.watertight and not a.device_mc:
         ap.error("--simplify_cells works on the device mesh: add --device_mc")
+    if a.simplify_faces is not None and a.simplify_cells is not None:
+        ap.error("--simplify_faces and --simplify_cells exclude each other")
+    if a.simplify_faces is not None and a.watertight and not a.device_mc:
+        ap.error("--simplify_faces works on the device mesh: add --device_mc")
+    if a.simplify_faces is not None and a.simplify_faces < 0:
+        ap.error("--simplify_faces must not be negative")
     return a
 
 
@@ -229,11 +238,15 @@ def run(a):
                 if a.simplify_cells is not None and len(t):
                     from surfd_amd.meshsimplify import simplify_vertex_clustering
                     v, t = simplify_vertex_clustering(v, t, cells=a.simplify_cells)
+                if a.simplify_faces is not None and len(t):
+                    from surfd_amd.meshsimplify import simplify_quadric_decimation
+                    v, t = simplify_quadric_decimation(v, t, a.simplify_faces)
                 return v.cpu().numpy(), t.cpu().numpy()
             if a.watertight:
                 return get_watertight_mesh(field, a.resolution, max_batch=2 ** 16)
             v, t = get_mesh_from_udf(field, coords_range=(-1, 1), max_dist=0.1, N=a.resolution, max_batch=2 ** 16, differentiable=False,
-                                     device_clean=a.simplify_cells is not None, simplify_cells=a.simplify_cells)
+                                     device_clean=a.simplify_cells is not None or a.simplify_faces is not None, simplify_cells=a.simplify_cells,
+                                     simplify_faces=a.simplify_faces)
             return v.cpu().numpy(), t.cpu().numpy()
 
         (verts, faces), _ = run_guarded(f"{item} (decoder grids)", shape_mesh, decoder.saturation_count,

@@ -832,6 +832,28 @@ enum { SURFD_SIMPLIFY_MEAN = 0, SURFD_SIMPLIFY_QUADRIC = 1 };
  * pass's count; the output sizes. */
 int surfd_meshsimplify_cluster(const double *vertices, int V, const int32_t *faces, int F, const double *origin, double cell, int representative,
                                double rank_tol, double *out_vertices, int32_t *out_faces, int32_t *vertex_map, int64_t *counts, surfd_stream s);
+/* no reference counterpart; open3d's simplify_quadric_decimation(target_number_of_triangles) as rounds of independent collapses:
+ * edge-collapse decimation to a target face count with quadric error metrics (no priority
+ * queue; tests/meshdecimate_ref.py restates the contract sequentially in numpy, csrc/meshdecimate.hip carries its text and the
+ * passes; every output equals the restatement bit for bit).  vertices fp64 [V,3] and faces int32 [F,3] on the device.  A face that
+ * names a non-finite vertex or one vertex twice goes.  Every round: the unique edges, a point (the truncated minimiser of
+ * Q_lo + Q_hi around the midpoint, eigenvalues below rank_tol times the largest dropped; the cheapest of midpoint, lo, hi where
+ * that leaves the edge's enlarged box) and a cost per edge; an edge is valid when its valence is 1 or 2, the link condition
+ * holds, it is no interior edge between border vertices, its opposite vertices keep three edges and no face of its two fans
+ * turns by more than flip_cos allows; the first spread * ceil((F_now - target_faces) / 2) valid edges in ascending
+ * (fp32 cost, hash of seed, round and edge) are candidates; one is selected iff its hashed priority is the least at both end
+ * points and all their neighbours, so selected edges touch no common face; at most ceil((F_now - target_faces) / 2) collapse
+ * (hi into lo, at the point, Q summed).  Border edges add border_weight times the quadric of the plane through the edge
+ * perpendicular to their face.  Stops when F_now <= target_faces (0), when a round selects nothing (1) or after max_rounds (2).
+ * out_vertices[V,3], out_faces[F,3] must hold the whole input; vertex_map[V] (nullable): the output vertex every input vertex
+ * ended in, -1 where it took no part; counts[12] (host): output vertices, output faces, rounds, collapses, border collapses, stop
+ * reason, edges refused in the last round by valence, link, border, opposite vertex, flip, NaN cost.  F = 0 or V = 0: empty
+ * outputs, the map all -1.  3 F >= 2^31: SURFD_ERR_UNSUPPORTED; target_faces >= 0, border_weight >= 0, flip_cos in [0, 1),
+ * rank_tol > 0, all finite, spread >= 1, max_rounds >= 1, and an index outside [0, V) (found on the device before anything is
+ * indexed by it): all SURFD_ERR_ARG.  HOST-SYNCS 2 + 2 PER ROUND. */
+int surfd_meshsimplify_decimate(const double *vertices, int V, const int32_t *faces, int F, int64_t target_faces, double border_weight, double flip_cos,
+                                double rank_tol, int spread, int max_rounds, uint64_t seed, double *out_vertices, int32_t *out_faces,
+                                int32_t *vertex_map, int64_t *counts, surfd_stream s);
 
 /* ------------------------------------------------------------------------------------ */
 /* Point-cloud metrics: nearest neighbours between clouds and the matrix of directed      */

@@ -183,6 +183,8 @@ _SIGS = {
     "surfd_meshclean_drop_degenerate_faces": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_double, _P, c_i64p, _P]),
     "surfd_meshclean_fill_small_holes": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, c_i64p, _P]),
     "surfd_meshsimplify_cluster": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int, C.c_double, _P, _P, _P, c_i64p, _P]),
+    "surfd_meshsimplify_decimate": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_uint64,
+                                              _P, _P, _P, c_i64p, _P]),
     "surfd_cloud_nn": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "surfd_cloud_nn_matrix": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_float, _P, _P, _P]),
     "surfd_cloud_nn_matrix_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),

@@ -3,6 +3,9 @@ occupied cell, the mean of the cell's vertices or the minimiser of the cell's pl
 corners where the mean rounds them.  A mesh that lies on the device is made smaller there:
 
   simplify_vertex_clustering     (vertices, faces[, vertex_map][, stats])
+  simplify_quadric_decimation    (vertices, faces[, vertex_map][, stats]): edge collapses down to a target face count
+                                 (csrc/meshdecimate.hip, restated in tests/meshdecimate_ref.py); borders stay where they were,
+                                 manifold input stays manifold, sheets are not glued together
 
 tests/meshsimplify_ref.py restates the contract sequentially in numpy: every result equals it bit for bit and in the same order
 (vertex order, face order, every double).  The work runs in csrc/meshsimplify.hip and nowhere else: device tensors in, device
@@ -11,11 +14,12 @@ tensors out, CPU tensors are refused (no CPU fallback).  Vertices are float64 [V
 V < 2^31; an index outside [0, V) and a cell index outside [0, 2^21) are the library's SURFD_ERR_ARG (a RuntimeError), found on the
 device and never a fault.  Nothing is kept between calls; a call works on the current stream.
 
-Out of scope: edge-collapse decimation; any guarantee that the output is manifold or free of flipped or folded faces (clustering
-pinches two sheets that pass through one cell); attributes beyond ``vertex_map``; batches of meshes in one launch.
+Out of scope: for clustering, any guarantee that the output is manifold or free of flipped or folded faces (it pinches two sheets
+that pass through one cell); for decimation, any guarantee on non-manifold input (it comes out clean, no more) and the detection
+of fans (faces that fold within the flip bound); for both, attributes beyond ``vertex_map`` and batches of meshes in one launch.
 
 Host syncs: 3 per call (the cluster and face counts, the duplicate pass's count, the output sizes), 2 where every face collapses;
-``cells=K`` adds the read of the extent.
+``cells=K`` adds the read of the extent.  Decimation: 2 per call and 2 per round.
 """
 from __future__ import annotations
 
@@ -93,4 +97,60 @@ def simplify_vertex_clustering(vertices: Tensor, faces: Tensor, cell: Optional[f
         out.append(vmap.long())
     if return_stats:
         out.append(dict(zip(STAT_NAMES, (int(x) for x in c))))
+    return tuple(out)
+
+
+DECIMATE_STAT_NAMES = ("vertices", "faces", "rounds", "collapses", "border_collapses", "stop", "refused_valence", "refused_link",
+                       "refused_border", "refused_opposite", "refused_flip", "refused_nan")
+DECIMATE_STOPS = ("target", "stalled", "max_rounds")
+
+
+def simplify_quadric_decimation(vertices: Tensor, faces: Tensor, target_faces: Optional[int] = None, *, ratio: Optional[float] = None,
+                                border_weight: float = 1000.0, flip_cos: float = 0.2, rank_tol: float = 1e-3, spread: int = 4,
+                                max_rounds: int = 512, seed: int = 0, return_map: bool = False, return_stats: bool = False):
+    """(vertices float64 [V', 3], faces int64 [F', 3]) of the mesh after edge collapses down to ``target_faces`` faces (or
+    ``ratio`` times the faces given, rounded down; pass exactly one), by quadric error metrics in rounds of independent collapses:
+    every round ranks the valid edges by cost, takes the first ``spread`` times as many as are still to go as candidates, and
+    collapses those whose hashed priority (``seed``) is the least around both end points.  An edge is valid when the collapse keeps
+    the surface what it is (valence, link condition, borders, no vertex left with two edges) and turns no face by more than
+    ``flip_cos`` (the cosine between its old and new normal) allows.  A border edge adds the plane through it perpendicular to its
+    face, ``border_weight`` times: borders stay where they were.  The point of a collapse minimises the summed quadric, directions
+    whose eigenvalue is below ``rank_tol`` times the largest left at the midpoint.  The call stops at the target, when a round
+    finds nothing to collapse ("stalled": the output then has more faces than asked for) or after ``max_rounds``.
+    The defaults are knobs, not tuned values: ``border_weight`` and ``flip_cos`` are the customary ones of quadric decimation,
+    ``rank_tol`` is simplify_vertex_clustering's, ``spread`` and ``max_rounds`` bound the work of a round and of a call.
+    On a closed manifold mesh F' is target_faces or one less; on any mesh F' <= target_faces unless the call stalled.
+    ``return_map``: also int64 [V], the output vertex every input vertex ended in, -1 where it took no part; ``return_stats``:
+    also a dict of DECIMATE_STAT_NAMES, ``stop`` as one of DECIMATE_STOPS, the refusals those of the last round."""
+    v, f = _mesh(vertices, faces)
+    if (target_faces is None) == (ratio is None):
+        raise ValueError("pass exactly one of target_faces and ratio")
+    V, F = int(v.shape[0]), int(f.shape[0])
+    if ratio is not None:
+        if not 0 <= ratio <= 1:
+            raise ValueError(f"ratio must lie in [0, 1], got {ratio}")
+        target_faces = int(F * float(ratio))
+    if int(target_faces) != target_faces or target_faces < 0:
+        raise ValueError(f"target_faces must be an integer that is not negative, got {target_faces}")
+    if not (0 <= border_weight < float("inf")):
+        raise ValueError(f"border_weight must be finite and not negative, got {border_weight}")
+    if not (0 <= flip_cos < 1):
+        raise ValueError(f"flip_cos must lie in [0, 1), got {flip_cos}")
+    if not (rank_tol > 0 and rank_tol < float("inf")):
+        raise ValueError(f"rank_tol must be positive and finite, got {rank_tol}")
+    if int(spread) != spread or spread < 1 or int(max_rounds) != max_rounds or max_rounds < 1:
+        raise ValueError(f"spread and max_rounds must be integers of at least 1, got {spread} and {max_rounds}")
+    ov, of, c = torch.empty_like(v), torch.empty_like(f), _counts(12)
+    vmap = torch.empty(V, device=v.device, dtype=torch.int32) if return_map else None
+    with torch.cuda.device(v.device):
+        N.check(N.lib().surfd_meshsimplify_decimate(N.ptr(v), V, N.ptr(f), F, int(target_faces), float(border_weight), float(flip_cos), float(rank_tol),
+                                                    int(spread), int(max_rounds), int(seed) & (2 ** 64 - 1), N.ptr(ov), N.ptr(of),
+                                                    N.ptr(vmap) if return_map else None, c, N.stream()))
+    out = [ov[:c[0]], of[:c[1]].long()]
+    if return_map:
+        out.append(vmap.long())
+    if return_stats:
+        stats = dict(zip(DECIMATE_STAT_NAMES, (int(x) for x in c)))
+        stats["stop"] = DECIMATE_STOPS[stats["stop"]]
+        out.append(stats)
     return tuple(out)

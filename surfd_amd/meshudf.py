@@ -355,7 +355,8 @@ def get_udf_and_grads(udf_func, coords_range: Tuple[float, float], max_dist: flo
 def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[float, float], max_dist: float,
                       N: int = 128, smooth_borders: bool = True, differentiable: bool = True,
                       max_batch: int = 2 ** 12, use_fast_grid_filler: bool = True, device_post: bool = False,
-                      device_clean: bool = False, simplify_cells: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+                      device_clean: bool = False, simplify_cells: Optional[int] = None,
+                      simplify_faces: Optional[int] = None) -> Tuple[Tensor, Tensor]:
     """Triangulated mesh of the zero set of a UDF — same signature, defaults and return value as the reference
     (meshudf/meshudf.py:307-514): (vertices [V,3] float32, faces [F,3] int64) on the device.
 
@@ -373,7 +374,9 @@ def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[
     reference counterpart; needs ``device_clean=True`` and ``differentiable=False``): between the cleaning and the border smoothing
     the mesh is clustered on a grid of K cells along its largest extent, one quadric representative per occupied cell
     (surfd_amd.meshsimplify.simplify_vertex_clustering); the simplified vertices are no longer tied to udf samples, so the
-    re-attached gradients have no meaning for them."""
+    re-attached gradients have no meaning for them.  ``simplify_faces=N`` (no reference counterpart; the same two preconditions,
+    not together with ``simplify_cells``): at the same place the mesh is decimated by edge collapses to at most N faces
+    (surfd_amd.meshsimplify.simplify_quadric_decimation): borders stay where they were and sheets are not glued together."""
     from . import meshproc as mp
     from .mcubes import udf_mc_lewiner
     if simplify_cells is not None:
@@ -381,6 +384,15 @@ def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[
             raise ValueError("simplify_cells runs on the device mesh: pass device_clean=True")
         if differentiable:
             raise ValueError("simplify_cells moves vertices off the udf samples: pass differentiable=False")
+    if simplify_faces is not None:
+        if simplify_cells is not None:
+            raise ValueError("simplify_faces and simplify_cells exclude each other: pass one")
+        if not device_clean:
+            raise ValueError("simplify_faces runs on the device mesh: pass device_clean=True")
+        if differentiable:
+            raise ValueError("simplify_faces moves vertices off the udf samples: pass differentiable=False")
+        if int(simplify_faces) != simplify_faces or simplify_faces < 0:
+            raise ValueError(f"simplify_faces must be an integer that is not negative, got {simplify_faces}")
     if not use_fast_grid_filler:
         udf, gradients = get_udf_and_grads(udf_func, coords_range, max_dist, N, max_batch)
     else:
@@ -399,6 +411,9 @@ def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[
         if simplify_cells is not None and len(f64):
             from .meshsimplify import simplify_vertex_clustering
             v64, f64 = simplify_vertex_clustering(v64, f64, cells=int(simplify_cells))
+        if simplify_faces is not None and len(f64):
+            from .meshsimplify import simplify_quadric_decimation
+            v64, f64 = simplify_quadric_decimation(v64, f64, int(simplify_faces))
         return _finish_mesh(udf_func, v64, f64, dev, N, smooth_borders, differentiable, max_batch, True)
     # faces whose corners or edge midpoints sit at large udf values are artefacts: drop them (meshudf.py:354-378)
     edges, edge_face = mp.edges_of_faces(faces)
