@@ -74,6 +74,16 @@ def parse(argv=None):
     ap.add_argument("--simplify_faces", type=int, default=None, metavar="N",
                     help="make the mesh smaller on the GPU before it is written: edge collapses down to N faces, borders kept, sheets not glued "
                          "(surfd_amd.meshsimplify.simplify_quadric_decimation); the same rules as --simplify_cells, and not together with it")
+    ap.add_argument("--remesh_edge", type=float, default=None, metavar="L",
+                    help="remesh on the GPU before the mesh is written: triangles of roughly one size, edges of length L, vertices of valence 6 "
+                         "(surfd_amd.meshremesh.remesh_isotropic); after --simplify_cells / --simplify_faces where given, the same rules as they")
+    ap.add_argument("--remesh_edge_mean", type=float, default=None, metavar="K",
+                    help="the same with L = K times the mean edge length of the mesh; not together with --remesh_edge (open meshes: the mesh is "
+                         "remeshed as get_mesh_from_udf returns it, after the border smoothing, where --remesh_edge alone remeshes before it)")
+    ap.add_argument("--remesh_iterations", type=int, default=5, metavar="N", help="--remesh_edge / --remesh_edge_mean: iterations (default 5)")
+    ap.add_argument("--remesh_project", action="store_true",
+                    help="--remesh_edge / --remesh_edge_mean: put the moved vertices back onto the mesh as it was before, after every iteration "
+                         "(open meshes: remeshed as get_mesh_from_udf returns them, as with --remesh_edge_mean)")
     ap.add_argument("--respacing", default="", help="e.g. ddim50 for a quick run (the reference always runs 1000 steps)")
     ap.add_argument("--seed", type=int, default=10)
     ap.add_argument("--synthetic", action="store_true", help="create synthetic checkpoints under --output_dir and use them")
@@ -93,7 +103,35 @@ def parse(argv=None):
         ap.error("--simplify_faces works on the device mesh: add --device_clean (open meshes) or --device_mc (--watertight)")
     if a.simplify_faces is not None and a.simplify_faces < 0:
         ap.error("--simplify_faces must not be negative")
+    remesh = a.remesh_edge is not None or a.remesh_edge_mean is not None
+    if a.remesh_edge is not None and a.remesh_edge_mean is not None:
+        ap.error("--remesh_edge and --remesh_edge_mean exclude each other")
+    if remesh and not (a.device_mc if a.watertight else a.device_clean):
+        ap.error("--remesh_edge works on the device mesh: add --device_clean (open meshes) or --device_mc (--watertight)")
+    asked = a.remesh_edge if a.remesh_edge is not None else a.remesh_edge_mean
+    if (remesh and not 0 < asked < float("inf")) or a.remesh_iterations < 0:
+        ap.error("--remesh_edge / --remesh_edge_mean must be positive and finite, --remesh_iterations not negative")
+    if (a.remesh_project or a.remesh_iterations != 5) and not remesh:
+        ap.error("--remesh_iterations and --remesh_project go with --remesh_edge or --remesh_edge_mean")
     return a
+
+
+def remesh_in_call(a):
+    """the arguments of get_mesh_from_udf for --remesh_edge L alone: the call remeshes before it smooths the borders.  K times the
+    mean edge length and the projection need the mesh itself: the driver remeshes what the call returns (remesh_on_device)"""
+    if getattr(a, "remesh_edge", None) is None or getattr(a, "remesh_project", False):
+        return {}
+    return {"remesh_edge": a.remesh_edge, "remesh_iterations": a.remesh_iterations}
+
+
+def remesh_on_device(a, verts, faces):
+    """--remesh_edge / --remesh_edge_mean on a device mesh (float64 or float32 vertices, int64 faces); the mesh itself without them"""
+    if (getattr(a, "remesh_edge", None) is None and getattr(a, "remesh_edge_mean", None) is None) or not len(faces):
+        return verts, faces
+    from surfd_amd.meshremesh import mean_edge_length, remesh_isotropic
+    L = a.remesh_edge if a.remesh_edge is not None else a.remesh_edge_mean * mean_edge_length(verts, faces)
+    ov, of = remesh_isotropic(verts, faces, L, iterations=a.remesh_iterations, project=a.remesh_project)
+    return ov.to(verts.dtype), of
 
 
 def postprocess_open_mesh(mode: str) -> bool:
@@ -214,6 +252,7 @@ def run(a):
                 if a.simplify_faces is not None and len(faces):
                     from surfd_amd.meshsimplify import simplify_quadric_decimation
                     verts, faces = simplify_quadric_decimation(verts, faces, a.simplify_faces)
+                verts, faces = remesh_on_device(a, verts, faces)
                 return verts.cpu().numpy(), faces.cpu().numpy()
             if a.watertight:
                 verts, faces = get_watertight_mesh(field, a.resolution, max_batch=2 ** 16)
@@ -222,7 +261,9 @@ def run(a):
             device_post = bool(getattr(a, "device_post", False)) or device_clean
             v, t = get_mesh_from_udf(field, coords_range=(-1, 1), max_dist=0.1, N=a.resolution, max_batch=2 ** 16, differentiable=False,
                                      device_post=device_post, device_clean=device_clean, simplify_cells=getattr(a, "simplify_cells", None),
-                                     simplify_faces=getattr(a, "simplify_faces", None))
+                                     simplify_faces=getattr(a, "simplify_faces", None), **remesh_in_call(a))
+            if not remesh_in_call(a):
+                v, t = remesh_on_device(a, v, t)
             if device_post:                                   # the mesh goes to the host once, for write_obj
                 if postprocess_open_mesh(a.mode):
                     from surfd_amd import meshsmooth, meshtopo

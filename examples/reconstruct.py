@@ -50,6 +50,16 @@ def parse(argv=None):
     ap.add_argument("--simplify_faces", type=int, default=None, metavar="N",
                     help="make the mesh smaller on the GPU before it is written: edge collapses down to N faces, borders kept, sheets not glued "
                          "(surfd_amd.meshsimplify.simplify_quadric_decimation); the same rules as --simplify_cells, and not together with it")
+    ap.add_argument("--remesh_edge", type=float, default=None, metavar="L",
+                    help="remesh on the GPU before the mesh is written: triangles of roughly one size, edges of length L, vertices of valence 6 "
+                         "(surfd_amd.meshremesh.remesh_isotropic); after --simplify_cells / --simplify_faces where given, the same rules as they")
+    ap.add_argument("--remesh_edge_mean", type=float, default=None, metavar="K",
+                    help="the same with L = K times the mean edge length of the mesh; not together with --remesh_edge (open meshes: the mesh is "
+                         "remeshed as get_mesh_from_udf returns it, after the border smoothing, where --remesh_edge alone remeshes before it)")
+    ap.add_argument("--remesh_iterations", type=int, default=5, metavar="N", help="--remesh_edge / --remesh_edge_mean: iterations (default 5)")
+    ap.add_argument("--remesh_project", action="store_true",
+                    help="--remesh_edge / --remesh_edge_mean: put the moved vertices back onto the mesh as it was before, after every iteration "
+                         "(open meshes: remeshed as get_mesh_from_udf returns them, as with --remesh_edge_mean)")
     ap.add_argument("--batch", type=int, default=1, help="clouds per encoder call (export_meshes.py:75 uses 1)")
     ap.add_argument("--seed", type=int, default=10)
     ap.add_argument("--output_dir", default="outputs/reconstruct")
@@ -62,7 +72,8 @@ def parse(argv=None):
                     help="--metrics: how mesh_distance searches the meshes: their tiles, or the box hierarchy of csrc/meshbvh.hip "
                          "(the same numbers; not faster yet for closest points: DESIGN.md section 8.11)")
     ap.add_argument("--mesh_quality", action="store_true",
-                    help="--metrics: also record self_intersecting_faces, the share of the reconstruction's faces that pass through another")
+                    help="--metrics: also record self_intersecting_faces, the share of the reconstruction's faces that pass through another, and "
+                         "triangle_quality (edge lengths, smallest angles, valences; with --remesh_edge / --remesh_edge_mean before and after)")
     ap.add_argument("--topology", action="store_true",
                     help="--metrics: also record the reconstruction's topology (surfd_amd.meshtopo): pieces, holes, manifoldness, orientation")
     ap.add_argument("--preview", type=int, default=0, metavar="N",
@@ -76,7 +87,35 @@ def parse(argv=None):
         ap.error("--simplify_faces works on the device mesh: add --device_mc")
     if a.simplify_faces is not None and a.simplify_faces < 0:
         ap.error("--simplify_faces must not be negative")
+    remesh = a.remesh_edge is not None or a.remesh_edge_mean is not None
+    if a.remesh_edge is not None and a.remesh_edge_mean is not None:
+        ap.error("--remesh_edge and --remesh_edge_mean exclude each other")
+    if remesh and a.watertight and not a.device_mc:
+        ap.error("--remesh_edge works on the device mesh: add --device_mc")
+    asked = a.remesh_edge if a.remesh_edge is not None else a.remesh_edge_mean
+    if (remesh and not 0 < asked < float("inf")) or a.remesh_iterations < 0:
+        ap.error("--remesh_edge / --remesh_edge_mean must be positive and finite, --remesh_iterations not negative")
+    if (a.remesh_project or a.remesh_iterations != 5) and not remesh:
+        ap.error("--remesh_iterations and --remesh_project go with --remesh_edge or --remesh_edge_mean")
     return a
+
+
+def remesh_in_call(a):
+    """the arguments of get_mesh_from_udf for --remesh_edge L alone: the call remeshes before it smooths the borders.  K times the
+    mean edge length and the projection need the mesh itself: the driver remeshes what the call returns (remesh_on_device)"""
+    if getattr(a, "remesh_edge", None) is None or getattr(a, "remesh_project", False):
+        return {}
+    return {"remesh_edge": a.remesh_edge, "remesh_iterations": a.remesh_iterations}
+
+
+def remesh_on_device(a, verts, faces):
+    """--remesh_edge / --remesh_edge_mean on a device mesh (float64 or float32 vertices, int64 faces); the mesh itself without them"""
+    if (getattr(a, "remesh_edge", None) is None and getattr(a, "remesh_edge_mean", None) is None) or not len(faces):
+        return verts, faces
+    from surfd_amd.meshremesh import mean_edge_length, remesh_isotropic
+    L = a.remesh_edge if a.remesh_edge is not None else a.remesh_edge_mean * mean_edge_length(verts, faces)
+    ov, of = remesh_isotropic(verts, faces, L, iterations=a.remesh_iterations, project=a.remesh_project)
+    return ov.to(verts.dtype), of
 
 
 def synthetic_checkpoint(out_dir, size_latent):
@@ -141,6 +180,24 @@ def load_models(ae_dir):
     decoder = CbnDecoder(CoordsEncoder().out_dim, size_latent, 512, 5)
     decoder.load_state_dict(ckpt["decoder"], strict=True)
     return encoder, decoder.cuda().eval(), size_latent
+
+
+def triangle_quality_of(a, verts, faces, shape_mesh):
+    """--metrics --mesh_quality: surfd_amd.meshremesh.triangle_quality of the mesh written, and with --remesh_edge /
+    --remesh_edge_mean also of the mesh the same call gives without them (it is meshed once more for that), both against the
+    edge length the remeshing aimed at"""
+    import argparse
+    from surfd_amd.meshremesh import mean_edge_length, triangle_quality
+
+    def on_device(v, t):
+        return (torch.as_tensor(np.ascontiguousarray(v, dtype=np.float64)).cuda(), torch.as_tensor(np.ascontiguousarray(t, dtype=np.int64)).reshape(-1, 3).cuda())
+    if a.remesh_edge is None and a.remesh_edge_mean is None:
+        return {"triangle_quality": triangle_quality(*on_device(verts, faces))}
+    plain = argparse.Namespace(**dict(vars(a), remesh_edge=None, remesh_edge_mean=None))
+    bv, bt = on_device(*shape_mesh(plain))
+    L = a.remesh_edge if a.remesh_edge is not None else a.remesh_edge_mean * mean_edge_length(bv, bt)
+    return {"remesh_edge_length": L, "triangle_quality_before_remesh": triangle_quality(bv, bt, L),
+            "triangle_quality": triangle_quality(*on_device(verts, faces), L)}
 
 
 def item_metrics(path, verts, faces, field, seed, mesh_quality=False, accel="tiles", topology=False):
@@ -232,7 +289,7 @@ def run(a):
     for k, item in enumerate(ids):
         field = make_udf_func(decoder, latents[k], sample=k)
 
-        def shape_mesh():
+        def shape_mesh(a=a):
             if a.watertight and a.device_mc:
                 v, t = get_watertight_mesh(field, a.resolution, max_batch=2 ** 16, device=True)
                 if a.simplify_cells is not None and len(t):
@@ -241,12 +298,16 @@ def run(a):
                 if a.simplify_faces is not None and len(t):
                     from surfd_amd.meshsimplify import simplify_quadric_decimation
                     v, t = simplify_quadric_decimation(v, t, a.simplify_faces)
+                v, t = remesh_on_device(a, v, t)
                 return v.cpu().numpy(), t.cpu().numpy()
             if a.watertight:
                 return get_watertight_mesh(field, a.resolution, max_batch=2 ** 16)
             v, t = get_mesh_from_udf(field, coords_range=(-1, 1), max_dist=0.1, N=a.resolution, max_batch=2 ** 16, differentiable=False,
-                                     device_clean=a.simplify_cells is not None or a.simplify_faces is not None, simplify_cells=a.simplify_cells,
-                                     simplify_faces=a.simplify_faces)
+                                     device_clean=a.simplify_cells is not None or a.simplify_faces is not None or a.remesh_edge is not None or
+                                     a.remesh_edge_mean is not None, simplify_cells=a.simplify_cells, simplify_faces=a.simplify_faces,
+                                     **remesh_in_call(a))
+            if not remesh_in_call(a):
+                v, t = remesh_on_device(a, v, t)
             return v.cpu().numpy(), t.cpu().numpy()
 
         (verts, faces), _ = run_guarded(f"{item} (decoder grids)", shape_mesh, decoder.saturation_count,
@@ -262,6 +323,8 @@ def run(a):
             written += render.save_views(a.output_dir, os.path.splitext(os.path.basename(path))[0], views)
         if a.metrics:
             m = item_metrics(files[k], verts, faces, field, a.seed, a.mesh_quality, a.accel, a.topology)
+            if m is not None and a.mesh_quality and len(faces):
+                m.update(triangle_quality_of(a, verts, faces, shape_mesh))
             if m is not None:
                 metrics[item] = m
     if a.metrics:

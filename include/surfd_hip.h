@@ -854,6 +854,46 @@ int surfd_meshsimplify_cluster(const double *vertices, int V, const int32_t *fac
 int surfd_meshsimplify_decimate(const double *vertices, int V, const int32_t *faces, int F, int64_t target_faces, double border_weight, double flip_cos,
                                 double rank_tol, int spread, int max_rounds, uint64_t seed, double *out_vertices, int32_t *out_faces,
                                 int32_t *vertex_map, int64_t *counts, surfd_stream s);
+/* no reference counterpart; incremental isotropic remeshing to a target edge length (Botsch and Kobbelt 2004) as rounds of independent operations:
+ * a handle, because the mesh grows and the caller steps between iterations (the projection onto the input surface is the
+ * caller's).  tests/meshremesh_ref.py restates the contract sequentially in numpy, csrc/meshremesh.hip
+ * carries its text and the passes; vertices, faces, origin and counts equal the restatement bit for bit.  vertices fp64 [V,3] and
+ * faces int32 [F,3] on the device are copied: a face that names a non-finite vertex or one vertex twice goes.  low2 and high2 are
+ * the squares of the shortest and the longest edge length aimed at, made once by the caller (0 < low2 < high2, finite); flip_cos
+ * in [0, 1) bounds the turn of a face against its standing normal and against the normal it had in the input.  A vertex keeps its
+ * index for the life of the handle; new ones are appended.  3 F >= 2^31: SURFD_ERR_UNSUPPORTED; an index outside [0, V) (found on
+ * the device before anything is indexed by it; with V = 0 every index of F > 0 faces is one) and the knobs: SURFD_ERR_ARG, *out stays
+ * null.  HOST-SYNCS.  One stream at a time. */
+typedef struct surfd_meshremesh surfd_meshremesh;
+int surfd_meshremesh_create(const double *vertices, int V, const int32_t *faces, int F, double low2, double high2, double flip_cos, uint64_t seed,
+                            surfd_stream s, surfd_meshremesh **out);
+void surfd_meshremesh_destroy(surfd_meshremesh *m);
+/* no reference counterpart; one iteration of the isotropic remeshing (tests/meshremesh_ref.py, Remesher.iterate):
+ * up to split_rounds rounds that split every edge longer than high2 at its midpoint (1 + k children per face with
+ * k marked half-edges), up to collapse_rounds rounds that collapse independent edges shorter than low2 (the rules of
+ * surfd_meshsimplify_decimate, and no neighbour further than high2 from the point), up to flip_rounds rounds that flip independent
+ * edges towards valence 6 (4 on a border), relax_sweeps Jacobi sweeps that move interior vertices towards the mean of their
+ * neighbours in their tangent plane, relax in (0, 1] of the way.  A stage ends with the round that finds nothing.  counts[24]
+ * (host): vertices named by a face, faces, splits, collapses, border collapses, flips, relaxed, relax refusals, split / collapse /
+ * flip rounds made, the marks of the last split round, the refusals of the last collapse round by valence, link, border, opposite
+ * vertex, long edge, flip and of the last flip round by orientation, equal corners, existing edge, degree, long diagonal, fold.
+ * The arrays of the handle grow geometrically in a split round that needs it (the stream is drained first); a result with
+ * 3 F >= 2^31 is SURFD_ERR_UNSUPPORTED and leaves the state of before that round.  HOST-SYNCS 1 TO 2 TIMES PER ROUND. */
+int surfd_meshremesh_iterate(surfd_meshremesh *m, int split_rounds, int collapse_rounds, int flip_rounds, int relax_sweeps, double relax,
+                             int64_t *counts, surfd_stream s);
+/* no reference counterpart; the sizes of the isotropic remeshing's state (tests/meshremesh_ref.py, Remesher):
+ * the vertex slots (named by a face or not) and the faces the handle holds now: the sizes of the buffers below */
+int surfd_meshremesh_sizes(const surfd_meshremesh *m, int64_t *vertices, int64_t *faces);
+/* no reference counterpart; the working positions of the isotropic remeshing, for the caller's projection (tests/meshremesh_ref.py, Remesher.X and origin):
+ * positions[V_now,3] fp64 and origin[V_now] int32 (either nullable) of every vertex slot: origin is the input index while the
+ * vertex is an input vertex at its input position, else -1.  set_positions takes positions[V_now,3] back (the caller changes
+ * those of origin -1 only).  Device to device on the stream; no sync. */
+int surfd_meshremesh_get_positions(const surfd_meshremesh *m, double *positions, int32_t *origin, surfd_stream s);
+int surfd_meshremesh_set_positions(surfd_meshremesh *m, const double *positions, surfd_stream s);
+/* no reference counterpart; the compact result of the isotropic remeshing (tests/meshremesh_ref.py, Remesher.emit):
+ * out_vertices[V_now,3] (the vertices a face names, in ascending index), out_faces[F_now,3] renamed,
+ * out_origin[V_now] (nullable); counts[2] (host): vertices and faces written.  The handle stays usable.  host-sync. */
+int surfd_meshremesh_emit(surfd_meshremesh *m, double *out_vertices, int32_t *out_faces, int32_t *out_origin, int64_t *counts, surfd_stream s);
 
 /* ------------------------------------------------------------------------------------ */
 /* Point-cloud metrics: nearest neighbours between clouds and the matrix of directed      */

@@ -185,6 +185,13 @@ _SIGS = {
     "surfd_meshsimplify_cluster": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int, C.c_double, _P, _P, _P, c_i64p, _P]),
     "surfd_meshsimplify_decimate": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_uint64,
                                               _P, _P, _P, c_i64p, _P]),
+    "surfd_meshremesh_create": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_double, C.c_double, C.c_double, C.c_uint64, _P, C.POINTER(_P)]),
+    "surfd_meshremesh_destroy": (None, [_P]),
+    "surfd_meshremesh_iterate": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, c_i64p, _P]),
+    "surfd_meshremesh_sizes": (C.c_int, [_P, c_i64p, c_i64p]),
+    "surfd_meshremesh_get_positions": (C.c_int, [_P, _P, _P, _P]),
+    "surfd_meshremesh_set_positions": (C.c_int, [_P, _P, _P]),
+    "surfd_meshremesh_emit": (C.c_int, [_P, _P, _P, _P, c_i64p, _P]),
     "surfd_cloud_nn": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "surfd_cloud_nn_matrix": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_float, _P, _P, _P]),
     "surfd_cloud_nn_matrix_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),

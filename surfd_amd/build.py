@@ -41,6 +41,7 @@ SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshsmooth.hip")        # Laplacian
 SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshclean.hip")         # merge / duplicate / degenerate faces, small holes (surfd_amd/meshclean.py)
 SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshsimplify.hip")      # vertex clustering with mean / quadric representatives (surfd_amd/meshsimplify.py)
 SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshdecimate.hip")     # edge-collapse decimation to a face count (surfd_amd/meshsimplify.py)
+SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshremesh.hip")       # isotropic remeshing to an edge length (surfd_amd/meshremesh.py)
 FILE_FLAGS = {"cloudnn.hip": ["-fno-slp-vectorize"], "cloudnormals.hip": ["-fno-slp-vectorize"]}
 
 

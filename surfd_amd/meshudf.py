@@ -356,7 +356,8 @@ def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[
                       N: int = 128, smooth_borders: bool = True, differentiable: bool = True,
                       max_batch: int = 2 ** 12, use_fast_grid_filler: bool = True, device_post: bool = False,
                       device_clean: bool = False, simplify_cells: Optional[int] = None,
-                      simplify_faces: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+                      simplify_faces: Optional[int] = None, remesh_edge: Optional[float] = None,
+                      remesh_iterations: int = 5) -> Tuple[Tensor, Tensor]:
     """Triangulated mesh of the zero set of a UDF — same signature, defaults and return value as the reference
     (meshudf/meshudf.py:307-514): (vertices [V,3] float32, faces [F,3] int64) on the device.
 
@@ -376,7 +377,10 @@ def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[
     (surfd_amd.meshsimplify.simplify_vertex_clustering); the simplified vertices are no longer tied to udf samples, so the
     re-attached gradients have no meaning for them.  ``simplify_faces=N`` (no reference counterpart; the same two preconditions,
     not together with ``simplify_cells``): at the same place the mesh is decimated by edge collapses to at most N faces
-    (surfd_amd.meshsimplify.simplify_quadric_decimation): borders stay where they were and sheets are not glued together."""
+    (surfd_amd.meshsimplify.simplify_quadric_decimation): borders stay where they were and sheets are not glued together.
+    ``remesh_edge=L`` (no reference counterpart; the same two preconditions, combinable with either simplification): after it and
+    before the border smoothing the mesh is remeshed towards edges of length L in ``remesh_iterations`` iterations
+    (surfd_amd.meshremesh.remesh_isotropic with its other defaults): triangles of roughly one size, vertices of valence 6."""
     from . import meshproc as mp
     from .mcubes import udf_mc_lewiner
     if simplify_cells is not None:
@@ -393,6 +397,15 @@ def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[
             raise ValueError("simplify_faces moves vertices off the udf samples: pass differentiable=False")
         if int(simplify_faces) != simplify_faces or simplify_faces < 0:
             raise ValueError(f"simplify_faces must be an integer that is not negative, got {simplify_faces}")
+    if remesh_edge is not None:
+        if not device_clean:
+            raise ValueError("remesh_edge runs on the device mesh: pass device_clean=True")
+        if differentiable:
+            raise ValueError("remesh_edge moves vertices off the udf samples: pass differentiable=False")
+        if not (0 < float(remesh_edge) < float("inf")):
+            raise ValueError(f"remesh_edge must be positive and finite, got {remesh_edge}")
+        if int(remesh_iterations) != remesh_iterations or remesh_iterations < 0:
+            raise ValueError(f"remesh_iterations must be an integer that is not negative, got {remesh_iterations}")
     if not use_fast_grid_filler:
         udf, gradients = get_udf_and_grads(udf_func, coords_range, max_dist, N, max_batch)
     else:
@@ -414,6 +427,9 @@ def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[
         if simplify_faces is not None and len(f64):
             from .meshsimplify import simplify_quadric_decimation
             v64, f64 = simplify_quadric_decimation(v64, f64, int(simplify_faces))
+        if remesh_edge is not None and len(f64):
+            from .meshremesh import remesh_isotropic
+            v64, f64 = remesh_isotropic(v64, f64, float(remesh_edge), iterations=int(remesh_iterations))
         return _finish_mesh(udf_func, v64, f64, dev, N, smooth_borders, differentiable, max_batch, True)
     # faces whose corners or edge midpoints sit at large udf values are artefacts: drop them (meshudf.py:354-378)
     edges, edge_face = mp.edges_of_faces(faces)
