@@ -61,17 +61,19 @@
 //                part (or its survivor is named by no face).  counts[12]: output vertices, output faces, rounds, collapses, border
 //                collapses, stop, refusals by (a) (b) (c) (d) (e) (n) in the last round made.
 //
-// Passes (256-wide grids, one item per lane; sorts and scans are hipcub's through CubWorkspace).  Once: qd_vertex_flags ->
-// qd_face_mark (the only kernel that sees caller indices unchecked) -> exclusive sum -> qd_compact_kept -> HOST READ 0 (bad index,
-// kept faces) -> qd_box (block minimum and maximum of an order-preserving integer image, then integer atomics: no order) ->
-// qd_centre -> qd_centre_vertices -> qd_face_normals (n0).  Per round: qd_half_keys -> stable sort of (lo << 32 | hi, h) -> run_heads -> exclusive sum ->
-// qd_edge_fill (edge of every half-edge, start of every edge) -> stable sort of (vertex, corner) -> qd_run_bounds (corners of every
-// vertex) -> HOST READ 1 (E) -> qd_edge_info (valence, border vertices) -> qd_run_bounds over lo -> stable sort of (hi, edge) ->
-// qd_run_bounds (with the lo run: the incident edges and the neighbours of a vertex, ascending) -> round 0: qd_init_quadrics (one
-// lane per vertex walks its corners) -> qd_place (Jacobi, point, cost) -> qd_valid (merge, opposite vertices, both fans; the key)
-// -> stable 64-bit sort of (key, edge) -> qd_candidates -> qd_vertex_min -> qd_ring_min -> qd_select -> exclusive sum ->
-// qd_apply -> qd_rename_faces -> exclusive sum -> qd_compact_live -> qd_map_hop -> HOST READ 2 (selected, faces, refusals).
-// At the end: qd_mark_named -> exclusive sum -> qd_out_vertices, qd_out_faces, qd_vertex_map -> one read of the output size.
+// Passes (256-wide grids, one item per lane; sorts and scans are hipcub's through CubWorkspace; the er_ pieces are meshrounds.h's,
+// shared with csrc/meshremesh.hip).  Once: qd_nonfinite -> er_kept_faces (er_face_mark, the only kernel that sees caller indices
+// unchecked -> exclusive sum -> er_compact_kept) -> HOST READ 0 (bad index, kept faces) -> qd_box (block minimum and maximum of an
+// order-preserving integer image, then integer atomics: no order) -> qd_centre -> qd_centre_vertices -> er_face_normals (n0).
+// Per round: er_structure (er_half_keys -> stable sort of (lo << 32 | hi, h) -> run_heads -> exclusive sum -> er_edge_fill (edge of
+// every half-edge, start of every edge) -> stable sort of (vertex, corner) -> er_run_bounds (corners of every vertex) -> HOST READ 1
+// (E) -> er_edge_info (valence, border vertices) -> er_run_bounds over lo -> stable sort of (hi, edge) -> er_run_bounds (with the lo
+// run: the incident edges and the neighbours of a vertex, ascending)) -> round 0: qd_init_quadrics (one lane per vertex walks its
+// corners) -> qd_place (Jacobi, point, cost) -> qd_valid (er_refused_abcd: merge, opposite vertices; rule (n); er_fans_keep_side:
+// both fans; the key) -> stable 64-bit sort of (key, edge) -> qd_candidates -> er_vertex_min -> er_ring_min -> qd_select ->
+// exclusive sum -> qd_apply -> er_rename_faces -> exclusive sum -> er_compact_live -> qd_map_hop -> HOST READ 2 (selected, faces,
+// refusals).  At the end: er_count_named (er_mark_named -> exclusive sum) -> qd_final_vertices, er_out_faces, qd_vertex_map -> one
+// read of the output size.
 // qd_place is apart from qd_valid so that neither spills (DESIGN.md section 8.18 has the compiler's numbers).
 // No float atomics, no lane waits on another: every sum is one lane's loop in a fixed order, every device loop runs over a CSR
 // run (the corners, edges or neighbours of one vertex, the half-edges of one edge of valence <= 2) or six sweeps.
@@ -79,11 +81,12 @@
 // the first sort, the largest: 168 V + 452 F bytes (an edge array has 3 F entries: the bound).  Freed when the call returns.
 // Limits: F >= 0, V >= 0 (F = 0 or V = 0: empty outputs, the map all -1); 3 F < 2^31, beyond: SURFD_ERR_UNSUPPORTED.
 // Bounds: every kernel guards its thread index; arrays of V entries are indexed by caller indices only behind the comparison in
-// qd_face_mark (a face that fails it is not kept, and only kept faces are read again) or by names of kept faces; arrays of 3 F
+// er_face_mark (a face that fails it is not kept, and only kept faces are read again) or by names of kept faces; arrays of 3 F
 // entries by corners 3 f + k of current faces, by sorted positions below 3 F_now, or by edges below E <= 3 F_now.
 #include "common.h"
 #include "devscratch.h"
 #include "meshedit.h"
+#include "meshrounds.h"
 #include "meshscene.h"
 #include <cmath>
 
@@ -101,37 +104,10 @@ __device__ __forceinline__ double qd_unordered(qd_u64 o) {
     const qd_u64 b = (o >> 63) ? (o & ~0x8000000000000000ull) : ~o;
     return __longlong_as_double((long long)b);
 }
-__device__ __forceinline__ qd_u64 qd_fin(qd_u64 x) {
-    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27; x *= 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
-// salt = fin(seed + 0x9e3779b97f4a7c15 (round + 1)), made on the host
-__device__ __forceinline__ qd_u64 qd_mix(qd_u64 salt, int lo, int hi) { return qd_fin(salt ^ (((qd_u64)(unsigned)lo << 32) | (qd_u64)(unsigned)hi)); }
 
-__global__ void qd_vertex_flags_kernel(const double *__restrict__ vertices, int V, int *__restrict__ nonfinite) {
+__global__ void qd_nonfinite_kernel(const double *__restrict__ vertices, int V, int *__restrict__ nonfinite) {
     if (dev_tid() >= V) return;
     nonfinite[dev_tid()] = vertex_nonfinite(vertices, dev_tid());
-}
-
-// The kernel that sees the caller's indices: a face with one outside [0, V) raises *bad and is not looked at further.
-__global__ void qd_face_mark_kernel(const int32_t *__restrict__ faces, int F, int V, const int *__restrict__ nonfinite, int *__restrict__ keep,
-                                    int *__restrict__ part, int *__restrict__ bad) {
-    if (dev_tid() >= F) return;
-    const long f = dev_tid();
-    const int t0 = faces[3 * f], t1 = faces[3 * f + 1], t2 = faces[3 * f + 2];
-    if (t0 < 0 || t0 >= V || t1 < 0 || t1 >= V || t2 < 0 || t2 >= V) { *bad = 1; keep[f] = 0; return; }
-    const int k = (nonfinite[t0] | nonfinite[t1] | nonfinite[t2] || t0 == t1 || t1 == t2 || t0 == t2) ? 0 : 1;
-    keep[f] = k;
-    if (k) { part[t0] = 1; part[t1] = 1; part[t2] = 1; }      // every writer stores the same 1
-}
-
-__global__ void qd_compact_kept_kernel(const int32_t *__restrict__ faces, int F, const int *__restrict__ keep, const int *__restrict__ kpos,
-                                       int32_t *__restrict__ out) {
-    if (dev_tid() >= F || !keep[dev_tid()]) return;
-    const long f = dev_tid(), n = kpos[f];                     // n <= f
-#pragma unroll
-    for (int c = 0; c < 3; ++c) out[3 * n + c] = faces[3 * f + c];
 }
 
 // box[0..2] preset to all ones, box[3..5] to zero: the smallest and the largest image per axis over the vertices that take part
@@ -179,67 +155,6 @@ __global__ void qd_centre_vertices_kernel(const double *__restrict__ vertices, i
     vmap[v] = (int)v; rename[v] = (int)v; moved[v] = 0;
 }
 
-__global__ void qd_iota_kernel(int *__restrict__ iota, long n) {
-    if (dev_tid() < n) iota[dev_tid()] = (int)dev_tid();
-}
-
-// one lane per corner h = 3 f + k: the key of its half-edge and the vertex it names
-__global__ void qd_half_keys_kernel(const int32_t *__restrict__ fa, long n, qd_u64 *__restrict__ hkey, unsigned *__restrict__ vkey) {
-    if (dev_tid() >= n) return;
-    const long h = dev_tid(), f = h / 3;
-    const int k = (int)(h - 3 * f);
-    const int a = fa[h], b = fa[3 * f + (k + 1) % 3];
-    hkey[h] = ((qd_u64)(unsigned)(a < b ? a : b) << 32) | (qd_u64)(unsigned)(a < b ? b : a);
-    vkey[h] = (unsigned)a;
-}
-
-// sorted position i -> the edge of its half-edge; at the head of a run the edge's start and names; the last lane closes the starts
-__global__ void qd_edge_fill_kernel(const qd_u64 *__restrict__ skey, const int *__restrict__ sh, const int *__restrict__ head, const int *__restrict__ hpos,
-                                    long n, int *__restrict__ eoh, int *__restrict__ estart, int *__restrict__ elo, int *__restrict__ ehi) {
-    if (dev_tid() >= n) return;
-    const long i = dev_tid();
-    const int e = hpos[i] + head[i] - 1;
-    eoh[sh[i]] = e;
-    if (head[i]) { estart[e] = (int)i; elo[e] = (int)(skey[i] >> 32); ehi[e] = (int)(skey[i] & 0xffffffffull); }
-    if (i == n - 1) estart[e + 1] = (int)n;                   // e + 1 <= n: estart has 3 F + 1 entries
-}
-
-// first[k], last[k]: the run of the key k in the sorted keys (both preset to 0: an empty run)
-__global__ void qd_run_bounds_kernel(const unsigned *__restrict__ skey, long n, int *__restrict__ first, int *__restrict__ last) {
-    if (dev_tid() >= n) return;
-    const long i = dev_tid();
-    const unsigned k = skey[i];
-    if (i == 0 || skey[i - 1] != k) first[k] = (int)i;
-    if (i == n - 1 || skey[i + 1] != k) last[k] = (int)(i + 1);
-}
-
-__global__ void qd_edge_info_kernel(const int *__restrict__ estart, const int *__restrict__ elo, const int *__restrict__ ehi, int E, int *__restrict__ eval,
-                                    int *__restrict__ vborder, unsigned *__restrict__ hikey) {
-    if (dev_tid() >= E) return;
-    const long e = dev_tid();
-    const int val = estart[e + 1] - estart[e];
-    eval[e] = val;
-    hikey[e] = (unsigned)ehi[e];
-    if (val == 1) { vborder[elo[e]] = 1; vborder[ehi[e]] = 1; }      // every writer stores the same 1
-}
-
-// the normal of a face of centred corners
-struct qd_v3 { double x, y, z; };
-__device__ __forceinline__ qd_v3 qd_load(const double *__restrict__ P, long v) { return {P[3 * v], P[3 * v + 1], P[3 * v + 2]}; }
-__device__ __forceinline__ qd_v3 qd_normal(const qd_v3 &q0, const qd_v3 &q1, const qd_v3 &q2) {
-    const double ax = q1.x - q0.x, ay = q1.y - q0.y, az = q1.z - q0.z, bx = q2.x - q0.x, by = q2.y - q0.y, bz = q2.z - q0.z;
-    return {ay * bz - az * by, az * bx - ax * bz, ax * by - ay * bx};
-}
-__device__ __forceinline__ double qd_dot(const qd_v3 &a, const qd_v3 &b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-
-// n0 of every kept face
-__global__ void qd_face_normals_kernel(const double *__restrict__ P, const int32_t *__restrict__ fa, int F, double *__restrict__ nref) {
-    if (dev_tid() >= F) return;
-    const long f = dev_tid();
-    const qd_v3 n = qd_normal(qd_load(P, fa[3 * f]), qd_load(P, fa[3 * f + 1]), qd_load(P, fa[3 * f + 2]));
-    nref[3 * f] = n.x; nref[3 * f + 1] = n.y; nref[3 * f + 2] = n.z;
-}
-
 // one lane per vertex: the face terms of its corners in ascending 3 f + corner, then the border terms in ascending half-edge
 __global__ void __launch_bounds__(256) qd_init_quadrics_kernel(const double *__restrict__ P, const int32_t *__restrict__ fa, int V, const int *__restrict__ vfirst,
                                                                const int *__restrict__ vlast, const int *__restrict__ vf, const int *__restrict__ eoh,
@@ -252,11 +167,11 @@ __global__ void __launch_bounds__(256) qd_init_quadrics_kernel(const double *__r
     const int i0 = vfirst[v], i1 = vlast[v];
     for (int i = i0; i < i1; ++i) {
         const long f = vf[i] / 3;
-        const qd_v3 q0 = qd_load(P, fa[3 * f]), q1 = qd_load(P, fa[3 * f + 1]), q2 = qd_load(P, fa[3 * f + 2]);
-        const qd_v3 n = qd_normal(q0, q1, q2);
-        const double l = sqrt(qd_dot(n, n));
+        const er_v3 q0 = er_load(P, fa[3 * f]), q1 = er_load(P, fa[3 * f + 1]), q2 = er_load(P, fa[3 * f + 2]);
+        const er_v3 n = er_normal(q0, q1, q2);
+        const double l = sqrt(er_dot(n, n));
         if (l == 0.0) continue;
-        const double d = -qd_dot(n, q0);
+        const double d = -er_dot(n, q0);
         q[0] = q[0] + (n.x * n.x) / l; q[1] = q[1] + (n.x * n.y) / l; q[2] = q[2] + (n.x * n.z) / l;
         q[3] = q[3] + (n.y * n.y) / l; q[4] = q[4] + (n.y * n.z) / l; q[5] = q[5] + (n.z * n.z) / l;
         q[6] = q[6] + (n.x * d) / l; q[7] = q[7] + (n.y * d) / l; q[8] = q[8] + (n.z * d) / l;
@@ -269,16 +184,16 @@ __global__ void __launch_bounds__(256) qd_init_quadrics_kernel(const double *__r
         for (int k = 0; k < 3; ++k) {
             const int from = t[k], to = t[(k + 1) % 3];
             if ((from != (int)v && to != (int)v) || eval[eoh[3 * f + k]] != 1) continue;
-            const qd_v3 q0 = qd_load(P, t[0]), q1 = qd_load(P, t[1]), q2 = qd_load(P, t[2]);
-            const qd_v3 n = qd_normal(q0, q1, q2);
-            const double l = sqrt(qd_dot(n, n));
-            const qd_v3 pf = qd_load(P, from), pt = qd_load(P, to);
+            const er_v3 q0 = er_load(P, t[0]), q1 = er_load(P, t[1]), q2 = er_load(P, t[2]);
+            const er_v3 n = er_normal(q0, q1, q2);
+            const double l = sqrt(er_dot(n, n));
+            const er_v3 pf = er_load(P, from), pt = er_load(P, to);
             const double tx = pt.x - pf.x, ty = pt.y - pf.y, tz = pt.z - pf.z;
-            const qd_v3 m = {ty * n.z - tz * n.y, tz * n.x - tx * n.z, tx * n.y - ty * n.x};
-            const double mm = qd_dot(m, m);
+            const er_v3 m = {ty * n.z - tz * n.y, tz * n.x - tx * n.z, tx * n.y - ty * n.x};
+            const double mm = er_dot(m, m);
             if (mm == 0.0) continue;
             const double s = (border_weight * l) / mm;
-            const double d = -qd_dot(m, pf);
+            const double d = -er_dot(m, pf);
             q[0] = q[0] + (m.x * m.x) * s; q[1] = q[1] + (m.x * m.y) * s; q[2] = q[2] + (m.x * m.z) * s;
             q[3] = q[3] + (m.y * m.y) * s; q[4] = q[4] + (m.y * m.z) * s; q[5] = q[5] + (m.z * m.z) * s;
             q[6] = q[6] + (m.x * d) * s; q[7] = q[7] + (m.y * d) * s; q[8] = q[8] + (m.z * d) * s;
@@ -327,7 +242,7 @@ __global__ void __launch_bounds__(256) qd_place_kernel(const double *__restrict_
     double q[10];
 #pragma unroll
     for (int j = 0; j < 10; ++j) q[j] = Q[10 * lo + j] + Q[10 * hi + j];
-    const qd_v3 a = qd_load(P, lo), b = qd_load(P, hi);
+    const er_v3 a = er_load(P, lo), b = er_load(P, hi);
     const double m0 = (a.x + b.x) * 0.5, m1 = (a.y + b.y) * 0.5, m2 = (a.z + b.z) * 0.5;
     const double r0 = -(q[6] + ((q[0] * m0 + q[1] * m1) + q[2] * m2)), r1 = -(q[7] + ((q[1] * m0 + q[3] * m1) + q[4] * m2)),
                  r2 = -(q[8] + ((q[2] * m0 + q[4] * m1) + q[5] * m2));
@@ -371,34 +286,8 @@ __global__ void __launch_bounds__(256) qd_place_kernel(const double *__restrict_
     ecost[e] = cost;
 }
 
-// the ascending neighbours and incident edges of a vertex: the edges that name it as hi (lower neighbours), then those that name
-// it as lo, a run of the edge list itself
-struct qd_ring {
-    const int *elo, *ehi, *hie;
-    int h0, nh, l0, n;
-    __device__ __forceinline__ int edge(int j) const { return j < nh ? hie[h0 + j] : l0 + (j - nh); }
-    __device__ __forceinline__ int other(int j) const { return j < nh ? elo[hie[h0 + j]] : ehi[l0 + (j - nh)]; }
-};
-struct qd_rings {
-    const int *elo, *ehi, *hie, *hfirst, *hlast, *lfirst, *llast;
-    __device__ __forceinline__ qd_ring at(long v) const {
-        const int h0 = hfirst[v], nh = hlast[v] - h0, l0 = lfirst[v], nl = llast[v] - l0;
-        return {elo, ehi, hie, h0, nh, l0, nh + nl};
-    }
-    __device__ __forceinline__ int degree(long v) const { return (hlast[v] - hfirst[v]) + (llast[v] - lfirst[v]); }
-};
-
-// does moving corner k of face f to p keep its side?  (rule (e))
-__device__ __forceinline__ bool qd_keeps_side(const double *__restrict__ P, const int t[3], int k, const qd_v3 &p, const qd_v3 &n0, double flip2) {
-    const qd_v3 q0 = qd_load(P, t[0]), q1 = qd_load(P, t[1]), q2 = qd_load(P, t[2]);
-    const qd_v3 n = qd_normal(q0, q1, q2);
-    const qd_v3 w = qd_normal(k == 0 ? p : q0, k == 1 ? p : q1, k == 2 ? p : q2);
-    const double g = qd_dot(n, w), ww = qd_dot(w, w), g0 = qd_dot(n0, w);
-    return g > 0.0 && g * g > flip2 * (qd_dot(n, n) * ww) && g0 > 0.0 && g0 * g0 > flip2 * (qd_dot(n0, n0) * ww);
-}
-
 // one lane per edge: rules (a) (b) (c) (d) (n) (e), the first refusal counted; the sort key
-__global__ void __launch_bounds__(256) qd_valid_kernel(const double *__restrict__ P, const int32_t *__restrict__ fa, qd_rings rings, const int *__restrict__ estart,
+__global__ void __launch_bounds__(256) qd_valid_kernel(const double *__restrict__ P, const int32_t *__restrict__ fa, er_rings rings, const int *__restrict__ estart,
                                                        const int *__restrict__ sh, const int *__restrict__ eval, const int *__restrict__ vborder,
                                                        const int *__restrict__ vfirst, const int *__restrict__ vlast, const int *__restrict__ vf,
                                                        const double *__restrict__ nref, const double *__restrict__ ept, const double *__restrict__ ecost, int E, double flip2, qd_u64 salt,
@@ -406,44 +295,13 @@ __global__ void __launch_bounds__(256) qd_valid_kernel(const double *__restrict_
     if (dev_tid() >= E) return;
     const long e = dev_tid();
     const int lo = rings.elo[e], hi = rings.ehi[e], val = eval[e];
-    const qd_u64 hash = qd_mix(salt, lo, hi);
+    const qd_u64 hash = er_mix(salt, lo, hi);
     ehash[e] = hash;
-    int refused = -1;
-    if (val != 1 && val != 2) refused = QD_REF_A;
-    if (refused < 0) {
-        const qd_ring a = rings.at(lo), b = rings.at(hi);
-        int i = 0, j = 0, common = 0;
-        while (i < a.n && j < b.n) {                          // at most a.n + b.n steps
-            const int x = a.other(i), y = b.other(j);
-            if (x == y) { ++common; ++i; ++j; }
-            else if (x < y) ++i;
-            else ++j;
-        }
-        if (common != val) refused = QD_REF_B;
-    }
-    if (refused < 0 && val == 2 && vborder[lo] && vborder[hi]) refused = QD_REF_C;
-    if (refused < 0) {
-        for (int i = estart[e]; i < estart[e + 1]; ++i) {     // val <= 2 half-edges
-            const long h = sh[i], f = h / 3;
-            const int o = fa[3 * f + ((int)(h - 3 * f) + 2) % 3];
-            if (rings.degree(o) < (vborder[o] ? 3 : 4)) refused = QD_REF_D;
-        }
-    }
+    int refused = er_refused_abcd(rings, fa, estart, sh, vborder, e, lo, hi, val);
+    if (refused >= 0) refused += QD_REF_A;                   // QD_REF_A .. QD_REF_D are consecutive
     const double cost = ecost[e];
     if (refused < 0 && cost != cost) refused = QD_REF_N;
-    if (refused < 0) {
-        const qd_v3 p = {ept[3 * e], ept[3 * e + 1], ept[3 * e + 2]};
-#pragma unroll 1
-        for (int side = 0; side < 2 && refused < 0; ++side) {
-            const int end = side ? hi : lo, other = side ? lo : hi;
-            for (int i = vfirst[end]; i < vlast[end]; ++i) {
-                const long h = vf[i], f = h / 3;
-                const int t[3] = {fa[3 * f], fa[3 * f + 1], fa[3 * f + 2]};
-                if (t[0] == other || t[1] == other || t[2] == other) continue;
-                if (!qd_keeps_side(P, t, (int)(h - 3 * f), p, {nref[3 * f], nref[3 * f + 1], nref[3 * f + 2]}, flip2)) { refused = QD_REF_E; break; }
-            }
-        }
-    }
+    if (refused < 0 && !er_fans_keep_side(P, fa, vfirst, vlast, vf, nref, lo, hi, {ept[3 * e], ept[3 * e + 1], ept[3 * e + 2]}, flip2)) refused = QD_REF_E;
     if (refused >= 0) { atomicAdd(cnt + refused, 1); ekey[e] = ~0ull; return; }      // an integer count has no order
     atomicAdd(cnt + QD_VALID, 1);
     float c32 = (float)cost;
@@ -457,34 +315,6 @@ __global__ void qd_candidates_kernel(const int *__restrict__ erank, int E, const
     const long i = dev_tid();
     const long n = cnt[QD_VALID] < cap ? cnt[QD_VALID] : cap;
     cand[erank[i]] = i < n ? 1 : 0;
-}
-
-__device__ __forceinline__ bool qd_before(const qd_u64 *__restrict__ ehash, int a, int b) {      // b may be -1: nothing yet
-    return b < 0 || ehash[a] < ehash[b] || (ehash[a] == ehash[b] && a < b);
-}
-
-// m(v): the candidate of least priority at v, or -1
-__global__ void qd_vertex_min_kernel(qd_rings rings, int V, const int *__restrict__ cand, const qd_u64 *__restrict__ ehash, int *__restrict__ mbest) {
-    if (dev_tid() >= V) return;
-    const qd_ring r = rings.at(dev_tid());
-    int best = -1;
-    for (int j = 0; j < r.n; ++j) {
-        const int e = r.edge(j);
-        if (cand[e] && qd_before(ehash, e, best)) best = e;
-    }
-    mbest[dev_tid()] = best;
-}
-
-// M(v): the least m over v and its neighbours
-__global__ void qd_ring_min_kernel(qd_rings rings, int V, const int *__restrict__ mbest, const qd_u64 *__restrict__ ehash, int *__restrict__ Mbest) {
-    if (dev_tid() >= V) return;
-    const qd_ring r = rings.at(dev_tid());
-    int best = mbest[dev_tid()];
-    for (int j = 0; j < r.n; ++j) {
-        const int e = mbest[r.other(j)];
-        if (e >= 0 && qd_before(ehash, e, best)) best = e;
-    }
-    Mbest[dev_tid()] = best;
 }
 
 __global__ void qd_select_kernel(const int *__restrict__ erank, int E, const int *__restrict__ cand, const int *__restrict__ elo, const int *__restrict__ ehi,
@@ -510,41 +340,17 @@ __global__ void qd_apply_kernel(const int *__restrict__ erank, int E, const int 
     if (eval[e] == 1) atomicAdd(cnt + QD_BORDER, 1);
 }
 
-__global__ void qd_rename_faces_kernel(int32_t *__restrict__ fa, int F, const int *__restrict__ rename, int *__restrict__ live) {
-    if (dev_tid() >= F) return;
-    const long f = dev_tid();
-    const int a = rename[fa[3 * f]], b = rename[fa[3 * f + 1]], c = rename[fa[3 * f + 2]];
-    fa[3 * f] = a; fa[3 * f + 1] = b; fa[3 * f + 2] = c;
-    live[f] = (a != b && b != c && a != c) ? 1 : 0;
-}
-
-__global__ void qd_compact_live_kernel(const int32_t *__restrict__ fa, const double *__restrict__ nref, int F, const int *__restrict__ live,
-                                       const int *__restrict__ lpos, int32_t *__restrict__ out, double *__restrict__ nout) {
-    if (dev_tid() >= F || !live[dev_tid()]) return;
-    const long f = dev_tid(), n = lpos[f];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { out[3 * n + c] = fa[3 * f + c]; nout[3 * n + c] = nref[3 * f + c]; }
-}
-
 __global__ void qd_map_hop_kernel(int *__restrict__ vmap, int V, const int *__restrict__ rename) {
     if (dev_tid() < V) vmap[dev_tid()] = rename[vmap[dev_tid()]];
 }
 
-__global__ void qd_mark_named_kernel(const int32_t *__restrict__ fa, long n, int *__restrict__ stays) {
-    if (dev_tid() < n) stays[fa[dev_tid()]] = 1;              // every writer stores the same 1
-}
-
-__global__ void qd_out_vertices_kernel(const double *__restrict__ vertices, const double *__restrict__ P, const double *__restrict__ c0,
+__global__ void qd_final_vertices_kernel(const double *__restrict__ vertices, const double *__restrict__ P, const double *__restrict__ c0,
                                        const int *__restrict__ moved, int V, const int *__restrict__ stays, const int *__restrict__ newid,
                                        double *__restrict__ out) {
     if (dev_tid() >= V || !stays[dev_tid()]) return;
     const long v = dev_tid(), n = newid[v];                    // n <= v
 #pragma unroll
     for (int j = 0; j < 3; ++j) out[3 * n + j] = moved[v] ? c0[j] + P[3 * v + j] : vertices[3 * v + j];
-}
-
-__global__ void qd_out_faces_kernel(const int32_t *__restrict__ fa, long n, const int *__restrict__ newid, int32_t *__restrict__ out) {
-    if (dev_tid() < n) out[dev_tid()] = newid[fa[dev_tid()]];
 }
 
 __global__ void qd_vertex_map_kernel(const int *__restrict__ vmap, int V, const int *__restrict__ part, const int *__restrict__ stays,
@@ -557,6 +363,18 @@ __global__ void qd_vertex_map_kernel(const int *__restrict__ vmap, int V, const 
 }  // namespace surfd
 
 using namespace surfd;
+
+// the arrays of a call, carved from its arena; er_structure (meshrounds.h) sees those of a round through their names
+struct qd_arrays {
+    int *cnt, *nonfinite, *part, *moved, *vmap, *rename, *mbest, *Mbest, *stays, *newid;
+    int *vborder, *vfirst, *vlast, *lfirst, *llast, *hfirst, *hlast;                  // zeroed together every round
+    int *vheavy = nullptr;                                   // no slot: the decimation does not ask for the vertices at heavy edges
+    int *keep, *kpos, *iota, *sh, *head, *hpos, *eoh, *vf, *estart, *elo, *ehi, *eval, *hie, *erank, *cand, *sel, *selpos;
+    unsigned *vkey, *vkeys;
+    qd_u64 *box, *hkey, *hkeys, *ehash;
+    double *c0, *P, *Q, *ept, *ecost, *nra, *nrb;
+    int32_t *fa, *fb;
+};
 
 extern "C" int surfd_meshsimplify_decimate(const double *vertices, int V, const int32_t *faces, int F, int64_t target_faces, double border_weight,
                                            double flip_cos, double rank_tol, int spread, int max_rounds, uint64_t seed, double *out_vertices,
@@ -580,107 +398,81 @@ extern "C" int surfd_meshsimplify_decimate(const double *vertices, int V, const 
     const long H = 3L * F;                                   // corners; edges are at most as many
     DeviceScratch scratch;
     CubWorkspace cub{&scratch};
-    int *cnt, *nonfinite, *part, *moved, *vmap, *rename, *mbest, *Mbest, *stays, *newid;
-    int *vborder, *vfirst, *vlast, *lfirst, *llast, *hfirst, *hlast;                  // zeroed together every round
-    int *keep, *kpos, *iota, *sh, *head, *hpos, *eoh, *vf, *estart, *elo, *ehi, *eval, *hie, *erank, *cand, *sel, *selpos;
-    unsigned *vkey, *vkeys;
-    qd_u64 *box, *hkey, *hkeys, *ehash;
-    double *c0, *P, *Q, *ept, *ecost, *nra, *nrb;
-    int32_t *fa, *fb;
+    qd_arrays a;
     ScratchArena arena("meshdecimate");
     SURFD_TRY(arena.open(scratch, dev_slot<int>(QD_WORDS) + dev_slot<qd_u64>(6) + dev_slot<double>(3) + 16 * dev_slot<int>(V) + dev_slot<double>(3L * V) +
                                       dev_slot<double>(10L * V) + 2 * dev_slot<int>(F) + 2 * dev_slot<int32_t>(H) + 14 * dev_slot<int>(H) + dev_slot<int>(H + 1) +
                                       2 * dev_slot<unsigned>(H) + 3 * dev_slot<qd_u64>(H) + dev_slot<double>(3 * H) + dev_slot<double>(H) + 2 * dev_slot<double>(H)));
-    SURFD_TRY(zeroed_words(arena, &cnt, QD_WORDS, st)); SURFD_TRY(arena.get(&box, 6)); SURFD_TRY(arena.get(&c0, 3));
-    SURFD_TRY(arena.get(&nonfinite, V)); SURFD_TRY(arena.get(&part, V)); SURFD_TRY(arena.get(&moved, V)); SURFD_TRY(arena.get(&vmap, V));
-    SURFD_TRY(arena.get(&rename, V)); SURFD_TRY(arena.get(&mbest, V)); SURFD_TRY(arena.get(&Mbest, V)); SURFD_TRY(arena.get(&stays, V));
-    SURFD_TRY(arena.get(&newid, V));
-    SURFD_TRY(arena.get(&vborder, V)); SURFD_TRY(arena.get(&vfirst, V)); SURFD_TRY(arena.get(&vlast, V)); SURFD_TRY(arena.get(&lfirst, V));
-    SURFD_TRY(arena.get(&llast, V)); SURFD_TRY(arena.get(&hfirst, V)); SURFD_TRY(arena.get(&hlast, V));
+    SURFD_TRY(zeroed_words(arena, &a.cnt, QD_WORDS, st)); SURFD_TRY(arena.get(&a.box, 6)); SURFD_TRY(arena.get(&a.c0, 3));
+    SURFD_TRY(arena.get(&a.nonfinite, V)); SURFD_TRY(arena.get(&a.part, V)); SURFD_TRY(arena.get(&a.moved, V)); SURFD_TRY(arena.get(&a.vmap, V));
+    SURFD_TRY(arena.get(&a.rename, V)); SURFD_TRY(arena.get(&a.mbest, V)); SURFD_TRY(arena.get(&a.Mbest, V)); SURFD_TRY(arena.get(&a.stays, V));
+    SURFD_TRY(arena.get(&a.newid, V));
+    SURFD_TRY(arena.get(&a.vborder, V)); SURFD_TRY(arena.get(&a.vfirst, V)); SURFD_TRY(arena.get(&a.vlast, V)); SURFD_TRY(arena.get(&a.lfirst, V));
+    SURFD_TRY(arena.get(&a.llast, V)); SURFD_TRY(arena.get(&a.hfirst, V)); SURFD_TRY(arena.get(&a.hlast, V));
     const size_t round_zero = 7 * dev_slot<int>(V);          // vborder .. hlast are consecutive slots
-    SURFD_TRY(arena.get(&P, 3L * V)); SURFD_TRY(arena.get(&Q, 10L * V));
-    SURFD_TRY(arena.get(&keep, F)); SURFD_TRY(arena.get(&kpos, F)); SURFD_TRY(arena.get(&fa, H)); SURFD_TRY(arena.get(&fb, H));
-    SURFD_TRY(arena.get(&iota, H)); SURFD_TRY(arena.get(&sh, H)); SURFD_TRY(arena.get(&head, H)); SURFD_TRY(arena.get(&hpos, H));
-    SURFD_TRY(arena.get(&eoh, H)); SURFD_TRY(arena.get(&vf, H)); SURFD_TRY(arena.get(&elo, H)); SURFD_TRY(arena.get(&ehi, H));
-    SURFD_TRY(arena.get(&eval, H)); SURFD_TRY(arena.get(&hie, H)); SURFD_TRY(arena.get(&erank, H)); SURFD_TRY(arena.get(&cand, H));
-    SURFD_TRY(arena.get(&sel, H)); SURFD_TRY(arena.get(&selpos, H)); SURFD_TRY(arena.get(&estart, H + 1));
-    SURFD_TRY(arena.get(&vkey, H)); SURFD_TRY(arena.get(&vkeys, H));
-    SURFD_TRY(arena.get(&hkey, H)); SURFD_TRY(arena.get(&hkeys, H)); SURFD_TRY(arena.get(&ehash, H));
-    SURFD_TRY(arena.get(&ept, 3 * H)); SURFD_TRY(arena.get(&ecost, H)); SURFD_TRY(arena.get(&nra, H)); SURFD_TRY(arena.get(&nrb, H));
-    int *live = keep, *lpos = kpos;                          // the flags of a round's faces, once the kept faces are compacted
-    qd_u64 *ekey = hkey, *ekeys = hkeys;                     // the half-edge keys are spent when the candidate keys are made
-    unsigned *hikey = vkey, *hikeys = vkeys;                 // likewise the corner keys
+    SURFD_TRY(arena.get(&a.P, 3L * V)); SURFD_TRY(arena.get(&a.Q, 10L * V));
+    SURFD_TRY(arena.get(&a.keep, F)); SURFD_TRY(arena.get(&a.kpos, F)); SURFD_TRY(arena.get(&a.fa, H)); SURFD_TRY(arena.get(&a.fb, H));
+    SURFD_TRY(arena.get(&a.iota, H)); SURFD_TRY(arena.get(&a.sh, H)); SURFD_TRY(arena.get(&a.head, H)); SURFD_TRY(arena.get(&a.hpos, H));
+    SURFD_TRY(arena.get(&a.eoh, H)); SURFD_TRY(arena.get(&a.vf, H)); SURFD_TRY(arena.get(&a.elo, H)); SURFD_TRY(arena.get(&a.ehi, H));
+    SURFD_TRY(arena.get(&a.eval, H)); SURFD_TRY(arena.get(&a.hie, H)); SURFD_TRY(arena.get(&a.erank, H)); SURFD_TRY(arena.get(&a.cand, H));
+    SURFD_TRY(arena.get(&a.sel, H)); SURFD_TRY(arena.get(&a.selpos, H)); SURFD_TRY(arena.get(&a.estart, H + 1));
+    SURFD_TRY(arena.get(&a.vkey, H)); SURFD_TRY(arena.get(&a.vkeys, H));
+    SURFD_TRY(arena.get(&a.hkey, H)); SURFD_TRY(arena.get(&a.hkeys, H)); SURFD_TRY(arena.get(&a.ehash, H));
+    SURFD_TRY(arena.get(&a.ept, 3 * H)); SURFD_TRY(arena.get(&a.ecost, H)); SURFD_TRY(arena.get(&a.nra, H)); SURFD_TRY(arena.get(&a.nrb, H));
+    int *cnt = a.cnt, *live = a.keep, *lpos = a.kpos;        // the flags of a round's faces, once the kept faces are compacted
+    qd_u64 *ekey = a.hkey, *ekeys = a.hkeys;                 // the half-edge keys are spent when the candidate keys are made
 
-    HIP_TRY(hipMemsetAsync(part, 0, dev_bytes<int>(V), st));
-    DEV_LAUNCH(qd_vertex_flags_kernel, V, vertices, V, nonfinite);
-    DEV_LAUNCH(qd_face_mark_kernel, F, faces, F, V, (const int *)nonfinite, keep, part, cnt + QD_BAD);
-    SURFD_TRY(cub.sort_pairs(hkey, hkeys, iota, sh, (int)H, 64, st, true));      // room for the largest sort of the call
-    SURFD_TRY(cub.exclusive_sum(keep, kpos, F, st));
-    SURFD_TRY(scan_total(keep, kpos, F, cnt + QD_KEPT, st));
-    DEV_LAUNCH(qd_compact_kept_kernel, F, faces, F, (const int *)keep, (const int *)kpos, fa);
+    HIP_TRY(hipMemsetAsync(a.part, 0, dev_bytes<int>(V), st));
+    DEV_LAUNCH(qd_nonfinite_kernel, V, vertices, V, a.nonfinite);
+    SURFD_TRY(cub.sort_pairs(a.hkey, a.hkeys, a.iota, a.sh, (int)H, 64, st, true));      // room for the largest sort of the call, before the first scan
+    SURFD_TRY(er_kept_faces(cub, faces, F, V, a.nonfinite, a.keep, a.kpos, a.part, cnt + QD_BAD, cnt + QD_KEPT, a.fa, st));
     int hc[QD_WORDS];
     SURFD_TRY(read_words(cnt, hc, QD_WORDS, st));                         // host read 0
     if (hc[QD_BAD]) return mesh_bad_index(who, V);
     int Fn = hc[QD_KEPT];
-    HIP_TRY(hipMemsetAsync(box, 0xFF, 3 * sizeof(qd_u64), st));
-    HIP_TRY(hipMemsetAsync(box + 3, 0, 3 * sizeof(qd_u64), st));
-    DEV_LAUNCH(qd_box_kernel, V, vertices, V, (const int *)part, box);
-    hipLaunchKernelGGL(qd_centre_kernel, dim3(1), dim3(64), 0, st, (const qd_u64 *)box, c0);
+    HIP_TRY(hipMemsetAsync(a.box, 0xFF, 3 * sizeof(qd_u64), st));
+    HIP_TRY(hipMemsetAsync(a.box + 3, 0, 3 * sizeof(qd_u64), st));
+    DEV_LAUNCH(qd_box_kernel, V, vertices, V, (const int *)a.part, a.box);
+    hipLaunchKernelGGL(qd_centre_kernel, dim3(1), dim3(64), 0, st, (const qd_u64 *)a.box, a.c0);
     LAUNCH_CHECK();
-    DEV_LAUNCH(qd_centre_vertices_kernel, V, vertices, V, (const double *)c0, P, vmap, rename, moved);
-    DEV_LAUNCH(qd_iota_kernel, H, iota, H);
-    if (Fn > 0) DEV_LAUNCH(qd_face_normals_kernel, Fn, (const double *)P, (const int32_t *)fa, Fn, nra);
+    DEV_LAUNCH(qd_centre_vertices_kernel, V, vertices, V, (const double *)a.c0, a.P, a.vmap, a.rename, a.moved);
+    DEV_LAUNCH(er_iota_kernel, H, a.iota, H);
+    if (Fn > 0) DEV_LAUNCH(er_face_normals_kernel, Fn, (const double *)a.P, (const int32_t *)a.fa, Fn, a.nra);
 
-    int vbits = 1;                                           // of a vertex index below V; never a sort over zero bits
-    while ((1L << vbits) < V) ++vbits;
     const double flip2 = flip_cos * flip_cos;
-    const qd_rings rings = {elo, ehi, hie, hfirst, hlast, lfirst, llast};
+    const er_rings rings = {a.elo, a.ehi, a.hie, a.hfirst, a.hlast, a.lfirst, a.llast};
     int rounds = 0, stop = 0;
     int64_t collapses = 0;
     while (Fn > target_faces) {
         if (rounds >= max_rounds) { stop = 2; break; }
-        const long n = 3L * Fn;
         const long remaining = ((long)Fn - target_faces + 1) / 2;
         const long cap = (long)spread * remaining;
-        qd_u64 salt = seed + 0x9e3779b97f4a7c15ull * (qd_u64)(rounds + 1);
-        salt ^= salt >> 30; salt *= 0xbf58476d1ce4e5b9ull; salt ^= salt >> 27; salt *= 0x94d049bb133111ebull; salt ^= salt >> 31;
-        HIP_TRY(hipMemsetAsync(vborder, 0, round_zero, st));
+        const qd_u64 salt = er_salt(seed, (uint64_t)rounds);
+        int E;
+        HIP_TRY(hipMemsetAsync(a.vborder, 0, round_zero, st));
         HIP_TRY(hipMemsetAsync(cnt + QD_VALID, 0, (QD_WORDS - QD_VALID) * sizeof(int), st));
-        DEV_LAUNCH(qd_half_keys_kernel, n, (const int32_t *)fa, n, hkey, vkey);
-        SURFD_TRY(cub.sort_pairs(hkey, hkeys, iota, sh, (int)n, 32 + vbits, st));
-        DEV_LAUNCH(run_heads_kernel<~0ull>, n, (const qd_u64 *)hkeys, (int)n, head);
-        SURFD_TRY(cub.exclusive_sum(head, hpos, (int)n, st));
-        SURFD_TRY(scan_total(head, hpos, (int)n, cnt + QD_E, st));
-        DEV_LAUNCH(qd_edge_fill_kernel, n, (const qd_u64 *)hkeys, (const int *)sh, (const int *)head, (const int *)hpos, n, eoh, estart, elo, ehi);
-        SURFD_TRY(cub.sort_pairs(vkey, vkeys, iota, vf, (int)n, vbits, st));
-        DEV_LAUNCH(qd_run_bounds_kernel, n, (const unsigned *)vkeys, n, vfirst, vlast);
-        SURFD_TRY(read_words(cnt, hc, QD_WORDS, st));                     // host read 1
-        const int E = hc[QD_E];
-        DEV_LAUNCH(qd_edge_info_kernel, E, (const int *)estart, (const int *)elo, (const int *)ehi, E, eval, vborder, hikey);
-        DEV_LAUNCH(qd_run_bounds_kernel, E, (const unsigned *)elo, (long)E, lfirst, llast);
-        SURFD_TRY(cub.sort_pairs(hikey, hikeys, iota, hie, E, vbits, st));
-        DEV_LAUNCH(qd_run_bounds_kernel, E, (const unsigned *)hikeys, (long)E, hfirst, hlast);
+        SURFD_TRY(er_structure(a, cub, V, Fn, true, cnt, QD_WORDS, QD_E, hc, &E, st));      // host read 1
         if (rounds == 0)
-            DEV_LAUNCH(qd_init_quadrics_kernel, V, (const double *)P, (const int32_t *)fa, V, (const int *)vfirst, (const int *)vlast, (const int *)vf,
-                       (const int *)eoh, (const int *)eval, border_weight, Q);
-        DEV_LAUNCH(qd_place_kernel, E, (const double *)P, (const double *)Q, (const int *)elo, (const int *)ehi, E, rank_tol, ept, ecost);
-        DEV_LAUNCH(qd_valid_kernel, E, (const double *)P, (const int32_t *)fa, rings, (const int *)estart, (const int *)sh, (const int *)eval,
-                   (const int *)vborder, (const int *)vfirst, (const int *)vlast, (const int *)vf, (const double *)nra, (const double *)ept, (const double *)ecost, E, flip2, salt,
-                   ekey, ehash, cnt);
-        SURFD_TRY(cub.sort_pairs(ekey, ekeys, iota, erank, E, 64, st));
-        DEV_LAUNCH(qd_candidates_kernel, E, (const int *)erank, E, (const int *)cnt, cap, cand);
-        DEV_LAUNCH(qd_vertex_min_kernel, V, rings, V, (const int *)cand, (const qd_u64 *)ehash, mbest);
-        DEV_LAUNCH(qd_ring_min_kernel, V, rings, V, (const int *)mbest, (const qd_u64 *)ehash, Mbest);
-        DEV_LAUNCH(qd_select_kernel, E, (const int *)erank, E, (const int *)cand, (const int *)elo, (const int *)ehi, (const int *)Mbest, sel);
-        SURFD_TRY(cub.exclusive_sum(sel, selpos, E, st));
-        SURFD_TRY(scan_total(sel, selpos, E, cnt + QD_SEL, st));
-        DEV_LAUNCH(qd_apply_kernel, E, (const int *)erank, E, (const int *)sel, (const int *)selpos, remaining, (const int *)elo, (const int *)ehi,
-                   (const int *)eval, (const double *)ept, P, Q, rename, moved, cnt);
-        DEV_LAUNCH(qd_rename_faces_kernel, Fn, fa, Fn, (const int *)rename, live);
+            DEV_LAUNCH(qd_init_quadrics_kernel, V, (const double *)a.P, (const int32_t *)a.fa, V, (const int *)a.vfirst, (const int *)a.vlast, (const int *)a.vf,
+                       (const int *)a.eoh, (const int *)a.eval, border_weight, a.Q);
+        DEV_LAUNCH(qd_place_kernel, E, (const double *)a.P, (const double *)a.Q, (const int *)a.elo, (const int *)a.ehi, E, rank_tol, a.ept, a.ecost);
+        DEV_LAUNCH(qd_valid_kernel, E, (const double *)a.P, (const int32_t *)a.fa, rings, (const int *)a.estart, (const int *)a.sh, (const int *)a.eval,
+                   (const int *)a.vborder, (const int *)a.vfirst, (const int *)a.vlast, (const int *)a.vf, (const double *)a.nra, (const double *)a.ept,
+                   (const double *)a.ecost, E, flip2, salt, ekey, a.ehash, cnt);
+        SURFD_TRY(cub.sort_pairs(ekey, ekeys, a.iota, a.erank, E, 64, st));
+        DEV_LAUNCH(qd_candidates_kernel, E, (const int *)a.erank, E, (const int *)cnt, cap, a.cand);
+        DEV_LAUNCH(er_vertex_min_kernel, V, rings, V, (const int *)a.cand, (const qd_u64 *)a.ehash, a.mbest);
+        DEV_LAUNCH(er_ring_min_kernel, V, rings, V, (const int *)a.mbest, (const qd_u64 *)a.ehash, a.Mbest);
+        DEV_LAUNCH(qd_select_kernel, E, (const int *)a.erank, E, (const int *)a.cand, (const int *)a.elo, (const int *)a.ehi, (const int *)a.Mbest, a.sel);
+        SURFD_TRY(cub.exclusive_sum(a.sel, a.selpos, E, st));
+        SURFD_TRY(scan_total(a.sel, a.selpos, E, cnt + QD_SEL, st));
+        DEV_LAUNCH(qd_apply_kernel, E, (const int *)a.erank, E, (const int *)a.sel, (const int *)a.selpos, remaining, (const int *)a.elo, (const int *)a.ehi,
+                   (const int *)a.eval, (const double *)a.ept, a.P, a.Q, a.rename, a.moved, cnt);
+        DEV_LAUNCH(er_rename_faces_kernel, Fn, a.fa, Fn, (const int *)a.rename, live);
         SURFD_TRY(cub.exclusive_sum(live, lpos, Fn, st));
         SURFD_TRY(scan_total(live, lpos, Fn, cnt + QD_FNEW, st));
-        DEV_LAUNCH(qd_compact_live_kernel, Fn, (const int32_t *)fa, (const double *)nra, Fn, (const int *)live, (const int *)lpos, fb, nrb);
-        DEV_LAUNCH(qd_map_hop_kernel, V, vmap, V, (const int *)rename);
+        DEV_LAUNCH(er_compact_live_kernel, Fn, (const int32_t *)a.fa, (const double *)a.nra, Fn, (const int *)live, (const int *)lpos, a.fb, a.nrb);
+        DEV_LAUNCH(qd_map_hop_kernel, V, a.vmap, V, (const int *)a.rename);
         SURFD_TRY(read_words(cnt, hc, QD_WORDS, st));                     // host read 2
         ++rounds;
         for (int i = 0; i < 4; ++i) counts[6 + i] = hc[QD_REF_A + i];
@@ -689,19 +481,16 @@ extern "C" int surfd_meshsimplify_decimate(const double *vertices, int V, const 
         const long chosen = hc[QD_SEL] < remaining ? hc[QD_SEL] : remaining;
         if (chosen == 0) { stop = 1; break; }                // fa is what it was: nothing was renamed
         collapses += chosen;
-        std::swap(fa, fb);
-        std::swap(nra, nrb);
+        std::swap(a.fa, a.fb);
+        std::swap(a.nra, a.nrb);
         Fn = hc[QD_FNEW];
     }
 
-    HIP_TRY(hipMemsetAsync(stays, 0, dev_bytes<int>(V), st));
-    if (Fn > 0) DEV_LAUNCH(qd_mark_named_kernel, 3L * Fn, (const int32_t *)fa, 3L * Fn, stays);
-    SURFD_TRY(cub.exclusive_sum(stays, newid, V, st));
-    SURFD_TRY(scan_total(stays, newid, V, cnt + QD_VOUT, st));
-    DEV_LAUNCH(qd_out_vertices_kernel, V, vertices, (const double *)P, (const double *)c0, (const int *)moved, V, (const int *)stays, (const int *)newid,
+    SURFD_TRY(er_count_named(cub, a.fa, Fn, V, a.stays, a.newid, cnt + QD_VOUT, st));
+    DEV_LAUNCH(qd_final_vertices_kernel, V, vertices, (const double *)a.P, (const double *)a.c0, (const int *)a.moved, V, (const int *)a.stays, (const int *)a.newid,
                out_vertices);
-    if (Fn > 0) DEV_LAUNCH(qd_out_faces_kernel, 3L * Fn, (const int32_t *)fa, 3L * Fn, (const int *)newid, out_faces);
-    if (vertex_map) DEV_LAUNCH(qd_vertex_map_kernel, V, (const int *)vmap, V, (const int *)part, (const int *)stays, (const int *)newid, vertex_map);
+    if (Fn > 0) DEV_LAUNCH(er_out_faces_kernel, 3L * Fn, (const int32_t *)a.fa, 3L * Fn, (const int *)a.newid, out_faces);
+    if (vertex_map) DEV_LAUNCH(qd_vertex_map_kernel, V, (const int *)a.vmap, V, (const int *)a.part, (const int *)a.stays, (const int *)a.newid, vertex_map);
     SURFD_TRY(read_words(cnt, hc, QD_WORDS, st));                         // the output size
     counts[0] = hc[QD_VOUT];
     counts[1] = Fn;

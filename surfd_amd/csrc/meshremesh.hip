@@ -65,17 +65,18 @@
 //                rounds made, the marks of the last split round made, the refusals of the last collapse round by (a) (b) (c) (d)
 //                (f) (e) and of the last flip round by orient, same, edge, degree, long, fold.
 //
-// Passes (256-wide grids, one item per lane; sorts and scans are hipcub's through the handle's CubWorkspace).  Create:
-// rm_vertex_flags -> rm_face_mark (the only kernel that sees caller indices unchecked) -> exclusive sum -> rm_compact_kept -> HOST
-// READ (bad index, kept faces) -> rm_face_normals (n0).  The structure of a round: rm_half_keys -> stable sort of (lo << 32 | hi, h)
-// -> run_heads -> exclusive sum -> rm_edge_fill -> HOST READ (E) -> rm_edge_info; with rings also: stable sort of (vertex, corner)
-// -> rm_run_bounds, rm_run_bounds over lo, stable sort of (hi, edge) -> rm_run_bounds.  Split: rm_split_mark -> two exclusive sums (the
+// Passes (256-wide grids, one item per lane; sorts and scans are hipcub's through the handle's CubWorkspace; the er_ pieces are
+// meshrounds.h's, shared with csrc/meshdecimate.hip).  Create: rm_vertex_flags -> er_kept_faces (er_face_mark, the only kernel that
+// sees caller indices unchecked -> exclusive sum -> er_compact_kept) -> HOST READ (bad index, kept faces) -> er_face_normals (n0).
+// The structure of a round (er_structure): er_half_keys -> stable sort of (lo << 32 | hi, h) -> run_heads -> exclusive sum ->
+// er_edge_fill -> HOST READ (E) -> er_edge_info; with rings also: stable sort of (vertex, corner) -> er_run_bounds, er_run_bounds
+// over lo, stable sort of (hi, edge) -> er_run_bounds.  Split: rm_split_mark -> two exclusive sums (the
 // marks, their half-edges) -> HOST READ (marks, F' = F + the marked half-edges, taken in 64 bits) -> growth if the arrays are short (the stream is drained, one new block is
 // carved, the state copied, the round's structure made again) -> rm_split_count -> exclusive sum -> rm_split_vertices -> rm_split_faces.  Collapse: rm_collapse_valid
-// -> rm_vertex_min -> rm_ring_min -> rm_collapse_select -> rm_collapse_apply -> rm_rename_faces -> exclusive sum -> rm_compact_live
-// -> HOST READ (selected, faces, refusals).  Flip: rm_flip_valid (64-bit atomicMin of the key at a, b, c, d: a minimum has no
+// (er_refused_abcd, rule (f), er_fans_keep_side) -> er_vertex_min -> er_ring_min -> rm_collapse_select -> rm_collapse_apply ->
+// er_rename_faces -> exclusive sum -> er_compact_live -> HOST READ (selected, faces, refusals).  Flip: rm_flip_valid (64-bit atomicMin of the key at a, b, c, d: a minimum has no
 // order) -> rm_flip_apply -> HOST READ.  Relax: rm_relax per sweep (X -> X2, swapped), one HOST READ at the end of the iteration
-// with the count of named vertices (rm_mark_named -> sum).  rm_relax and rm_flip_valid are kernels of their own so that neither
+// with the count of named vertices (er_count_named: er_mark_named -> sum).  rm_relax and rm_flip_valid are kernels of their own so that neither
 // spills (profiles/meshremesh_regs.txt has the compiler's numbers).
 // No float atomics, no lane waits on another: every sum is one lane's loop in a fixed order, every device loop runs over a CSR
 // run (the corners, edges or neighbours of one vertex, the half-edges of one edge of valence <= 2).
@@ -84,12 +85,13 @@
 // whose result does not fit; nothing is allocated in a round that does not grow.
 // Limits: F >= 0, V >= 0; 3 F < 2^31 at any time, beyond: SURFD_ERR_UNSUPPORTED.  ONE STREAM AT A TIME PER HANDLE.
 // Bounds: every kernel guards its 64-bit thread index; arrays of Vcap entries are indexed by caller indices only behind the
-// comparison in rm_face_mark or by names of current faces (< V_now <= Vcap; new names are V_now + position < V' <= Vcap, checked on
+// comparison in er_face_mark or by names of current faces (< V_now <= Vcap; new names are V_now + position < V' <= Vcap, checked on
 // the host before they are written); arrays of 3 Fcap entries by corners of current faces, by sorted positions below 3 F_now, or by
 // edges below E <= 3 F_now; split children go to positions below F' <= Fcap.
 #include "common.h"
 #include "devscratch.h"
 #include "meshedit.h"
+#include "meshrounds.h"
 #include "meshscene.h"
 #include "meshremesh_layout.h"
 #include <cmath>
@@ -100,34 +102,14 @@ enum { RM_BAD = 0, RM_KEPT, RM_E, RM_SEL, RM_FNEW, RM_BORDER, RM_VOUT, RM_RELAXE
 // RM_REF + 0..5: collapse refusals (a) (b) (c) (d) (f) (e); RM_REF + 6..11: flip refusals orient, same, edge, degree, long, fold
 enum { RM_COUNTS = 24 };
 
-__device__ __forceinline__ rm_u64 rm_fin(rm_u64 x) {
-    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27; x *= 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
-// salt = fin(seed + 0x9e3779b97f4a7c15 (round + 1)), made on the host
-__device__ __forceinline__ rm_u64 rm_mix(rm_u64 salt, int lo, int hi) { return rm_fin(salt ^ (((rm_u64)(unsigned)lo << 32) | (rm_u64)(unsigned)hi)); }
-
-struct rm_v3 { double x, y, z; };
-__device__ __forceinline__ rm_v3 rm_load(const double *__restrict__ X, long v) { return {X[3 * v], X[3 * v + 1], X[3 * v + 2]}; }
-__device__ __forceinline__ rm_v3 rm_normal(const rm_v3 &q0, const rm_v3 &q1, const rm_v3 &q2) {
-    const double ax = q1.x - q0.x, ay = q1.y - q0.y, az = q1.z - q0.z, bx = q2.x - q0.x, by = q2.y - q0.y, bz = q2.z - q0.z;
-    return {ay * bz - az * by, az * bx - ax * bz, ax * by - ay * bx};
-}
-__device__ __forceinline__ double rm_dot(const rm_v3 &a, const rm_v3 &b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ double rm_len2(const rm_v3 &p, const rm_v3 &q) {
+__device__ __forceinline__ double rm_len2(const er_v3 &p, const er_v3 &q) {
     const double dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z;
     return (dx * dx + dy * dy) + dz * dz;
 }
-__device__ __forceinline__ rm_v3 rm_mid(const rm_v3 &a, const rm_v3 &b) { return {(a.x + b.x) * 0.5, (a.y + b.y) * 0.5, (a.z + b.z) * 0.5}; }
-__device__ __forceinline__ bool rm_same_bits(const rm_v3 &a, const rm_v3 &b) {
+__device__ __forceinline__ er_v3 rm_mid(const er_v3 &a, const er_v3 &b) { return {(a.x + b.x) * 0.5, (a.y + b.y) * 0.5, (a.z + b.z) * 0.5}; }
+__device__ __forceinline__ bool rm_same_bits(const er_v3 &a, const er_v3 &b) {
     return __double_as_longlong(a.x) == __double_as_longlong(b.x) && __double_as_longlong(a.y) == __double_as_longlong(b.y) &&
            __double_as_longlong(a.z) == __double_as_longlong(b.z);
-}
-// the two comparisons of rule (e): does the new normal w keep the side of n?
-__device__ __forceinline__ bool rm_keeps(const rm_v3 &n, const rm_v3 &w, double ww, double flip2) {
-    const double g = rm_dot(n, w);
-    return g > 0.0 && g * g > flip2 * (rm_dot(n, n) * ww);
 }
 
 __global__ void rm_vertex_flags_kernel(const double *__restrict__ vertices, int V, int *__restrict__ nonfinite, double *__restrict__ X, int *__restrict__ origin) {
@@ -139,100 +121,13 @@ __global__ void rm_vertex_flags_kernel(const double *__restrict__ vertices, int 
     origin[v] = (int)v;
 }
 
-// The kernel that sees the caller's indices: a face with one outside [0, V) raises *bad and is not looked at further.
-__global__ void rm_face_mark_kernel(const int32_t *__restrict__ faces, int F, int V, const int *__restrict__ nonfinite, int *__restrict__ keep, int *__restrict__ bad) {
-    if (dev_tid() >= F) return;
-    const long f = dev_tid();
-    const int t0 = faces[3 * f], t1 = faces[3 * f + 1], t2 = faces[3 * f + 2];
-    if (t0 < 0 || t0 >= V || t1 < 0 || t1 >= V || t2 < 0 || t2 >= V) { *bad = 1; keep[f] = 0; return; }
-    keep[f] = (nonfinite[t0] | nonfinite[t1] | nonfinite[t2] || t0 == t1 || t1 == t2 || t0 == t2) ? 0 : 1;
-}
-
-__global__ void rm_compact_kept_kernel(const int32_t *__restrict__ faces, int F, const int *__restrict__ keep, const int *__restrict__ kpos,
-                                       int32_t *__restrict__ out) {
-    if (dev_tid() >= F || !keep[dev_tid()]) return;
-    const long f = dev_tid(), n = kpos[f];                     // n <= f
-#pragma unroll
-    for (int c = 0; c < 3; ++c) out[3 * n + c] = faces[3 * f + c];
-}
-
-__global__ void rm_iota_kernel(int *__restrict__ iota, long n) {
-    if (dev_tid() < n) iota[dev_tid()] = (int)dev_tid();
-}
-
-// n0 of every kept face
-__global__ void rm_face_normals_kernel(const double *__restrict__ X, const int32_t *__restrict__ fa, int F, double *__restrict__ nref) {
-    if (dev_tid() >= F) return;
-    const long f = dev_tid();
-    const rm_v3 n = rm_normal(rm_load(X, fa[3 * f]), rm_load(X, fa[3 * f + 1]), rm_load(X, fa[3 * f + 2]));
-    nref[3 * f] = n.x; nref[3 * f + 1] = n.y; nref[3 * f + 2] = n.z;
-}
-
-// one lane per corner h = 3 f + k: the key of its half-edge and the vertex it names
-__global__ void rm_half_keys_kernel(const int32_t *__restrict__ fa, long n, rm_u64 *__restrict__ hkey, unsigned *__restrict__ vkey) {
-    if (dev_tid() >= n) return;
-    const long h = dev_tid(), f = h / 3;
-    const int k = (int)(h - 3 * f);
-    const int a = fa[h], b = fa[3 * f + (k + 1) % 3];
-    hkey[h] = ((rm_u64)(unsigned)(a < b ? a : b) << 32) | (rm_u64)(unsigned)(a < b ? b : a);
-    vkey[h] = (unsigned)a;
-}
-
-// sorted position i -> the edge of its half-edge; at the head of a run the edge's start and names; the last lane closes the starts
-__global__ void rm_edge_fill_kernel(const rm_u64 *__restrict__ skey, const int *__restrict__ sh, const int *__restrict__ head, const int *__restrict__ hpos,
-                                    long n, int *__restrict__ eoh, int *__restrict__ estart, int *__restrict__ elo, int *__restrict__ ehi) {
-    if (dev_tid() >= n) return;
-    const long i = dev_tid();
-    const int e = hpos[i] + head[i] - 1;
-    eoh[sh[i]] = e;
-    if (head[i]) { estart[e] = (int)i; elo[e] = (int)(skey[i] >> 32); ehi[e] = (int)(skey[i] & 0xffffffffull); }
-    if (i == n - 1) estart[e + 1] = (int)n;                   // e + 1 <= n: estart has 3 Fcap + 1 entries
-}
-
-// first[k], last[k]: the run of the key k in the sorted keys (both preset to 0: an empty run)
-__global__ void rm_run_bounds_kernel(const unsigned *__restrict__ skey, long n, int *__restrict__ first, int *__restrict__ last) {
-    if (dev_tid() >= n) return;
-    const long i = dev_tid();
-    const unsigned k = skey[i];
-    if (i == 0 || skey[i - 1] != k) first[k] = (int)i;
-    if (i == n - 1 || skey[i + 1] != k) last[k] = (int)(i + 1);
-}
-
-__global__ void rm_edge_info_kernel(const int *__restrict__ estart, const int *__restrict__ elo, const int *__restrict__ ehi, int E, int *__restrict__ eval,
-                                    int *__restrict__ vborder, int *__restrict__ vheavy, unsigned *__restrict__ hikey) {
-    if (dev_tid() >= E) return;
-    const long e = dev_tid();
-    const int val = estart[e + 1] - estart[e];
-    eval[e] = val;
-    hikey[e] = (unsigned)ehi[e];
-    if (val == 1) { vborder[elo[e]] = 1; vborder[ehi[e]] = 1; }      // every writer stores the same 1
-    if (val >= 3) { vheavy[elo[e]] = 1; vheavy[ehi[e]] = 1; }
-}
-
-// the ascending neighbours and incident edges of a vertex: the edges that name it as hi (lower neighbours), then those that name
-// it as lo, a run of the edge list itself
-struct rm_ring {
-    const int *elo, *ehi, *hie;
-    int h0, nh, l0, n;
-    __device__ __forceinline__ int edge(int j) const { return j < nh ? hie[h0 + j] : l0 + (j - nh); }
-    __device__ __forceinline__ int other(int j) const { return j < nh ? elo[hie[h0 + j]] : ehi[l0 + (j - nh)]; }
-};
-struct rm_rings {
-    const int *elo, *ehi, *hie, *hfirst, *hlast, *lfirst, *llast;
-    __device__ __forceinline__ rm_ring at(long v) const {
-        const int h0 = hfirst[v], nh = hlast[v] - h0, l0 = lfirst[v], nl = llast[v] - l0;
-        return {elo, ehi, hie, h0, nh, l0, nh + nl};
-    }
-    __device__ __forceinline__ int degree(long v) const { return (hlast[v] - hfirst[v]) + (llast[v] - lfirst[v]); }
-};
-
 // ---- A: split ---------------------------------------------------------------------------------------------------------------------
 // mark[e]; mval[e]: the half-edges of a marked edge, the faces it adds
 __global__ void rm_split_mark_kernel(const double *__restrict__ X, const int *__restrict__ elo, const int *__restrict__ ehi, const int *__restrict__ eval, int E,
                                      double high2, int *__restrict__ mark, int *__restrict__ mval) {
     if (dev_tid() >= E) return;
     const long e = dev_tid();
-    const int on = rm_len2(rm_load(X, elo[e]), rm_load(X, ehi[e])) > high2 ? 1 : 0;
+    const int on = rm_len2(er_load(X, elo[e]), er_load(X, ehi[e])) > high2 ? 1 : 0;
     mark[e] = on;
     mval[e] = on ? eval[e] : 0;
 }
@@ -248,12 +143,12 @@ __global__ void rm_split_vertices_kernel(double *__restrict__ X, int *__restrict
                                          const int *__restrict__ mark, const int *__restrict__ mpos, int Vn) {
     if (dev_tid() >= E || !mark[dev_tid()]) return;
     const long e = dev_tid(), v = (long)Vn + mpos[e];
-    const rm_v3 m = rm_mid(rm_load(X, elo[e]), rm_load(X, ehi[e]));
+    const er_v3 m = rm_mid(er_load(X, elo[e]), er_load(X, ehi[e]));
     X[3 * v] = m.x; X[3 * v + 1] = m.y; X[3 * v + 2] = m.z;
     origin[v] = -1;
 }
 
-__device__ __forceinline__ void rm_put(int32_t *__restrict__ out, double *__restrict__ nout, long p, int a, int b, int c, const rm_v3 &n) {
+__device__ __forceinline__ void rm_put(int32_t *__restrict__ out, double *__restrict__ nout, long p, int a, int b, int c, const er_v3 &n) {
     out[3 * p] = a; out[3 * p + 1] = b; out[3 * p + 2] = c;
     nout[3 * p] = n.x; nout[3 * p + 1] = n.y; nout[3 * p + 2] = n.z;
 }
@@ -272,7 +167,7 @@ __global__ void rm_split_faces_kernel(const double *__restrict__ X, const int32_
         m[i] = mark[e] ? Vn + mpos[e] : -1;
         k += mark[e];
     }
-    const rm_v3 n = {nref[3 * f], nref[3 * f + 1], nref[3 * f + 2]};
+    const er_v3 n = {nref[3 * f], nref[3 * f + 1], nref[3 * f + 2]};
     if (k == 0) {
         rm_put(out, nout, p, c[0], c[1], c[2], n);
     } else if (k == 1) {
@@ -287,7 +182,7 @@ __global__ void rm_split_faces_kernel(const double *__restrict__ X, const int32_
     } else {
         const int j = m[0] < 0 ? 0 : (m[1] < 0 ? 1 : 2);
         const int a = c[j], b = c[(j + 1) % 3], cc = c[(j + 2) % 3], m1 = m[(j + 1) % 3], m2 = m[(j + 2) % 3];
-        const double la = rm_len2(rm_load(X, a), rm_load(X, m1)), lb = rm_len2(rm_load(X, b), rm_load(X, m2));
+        const double la = rm_len2(er_load(X, a), er_load(X, m1)), lb = rm_len2(er_load(X, b), er_load(X, m2));
         const bool first = la < lb || (la == lb && a < b);
         rm_put(out, nout, p, m1, cc, m2, n);
         rm_put(out, nout, p + 1, a, b, first ? m1 : m2, n);
@@ -296,23 +191,14 @@ __global__ void rm_split_faces_kernel(const double *__restrict__ X, const int32_
 }
 
 // ---- B: collapse ------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ rm_v3 rm_collapse_point(const double *__restrict__ X, const int *__restrict__ vborder, int lo, int hi) {
-    const rm_v3 a = rm_load(X, lo), b = rm_load(X, hi);
+__device__ __forceinline__ er_v3 rm_collapse_point(const double *__restrict__ X, const int *__restrict__ vborder, int lo, int hi) {
+    const er_v3 a = er_load(X, lo), b = er_load(X, hi);
     const int ba = vborder[lo], bb = vborder[hi];
     return ba == bb ? rm_mid(a, b) : (ba ? a : b);
 }
 
-// does moving corner k of face f to p keep its side?  (rule (e))
-__device__ __forceinline__ bool rm_keeps_side(const double *__restrict__ X, const int t[3], int k, const rm_v3 &p, const rm_v3 &n0, double flip2) {
-    const rm_v3 q0 = rm_load(X, t[0]), q1 = rm_load(X, t[1]), q2 = rm_load(X, t[2]);
-    const rm_v3 n = rm_normal(q0, q1, q2);
-    const rm_v3 w = rm_normal(k == 0 ? p : q0, k == 1 ? p : q1, k == 2 ? p : q2);
-    const double ww = rm_dot(w, w);
-    return rm_keeps(n, w, ww, flip2) && rm_keeps(n0, w, ww, flip2);
-}
-
 // one lane per edge: short edges through rules (a) (b) (c) (d) (f) (e), the first refusal counted
-__global__ void __launch_bounds__(256) rm_collapse_valid_kernel(const double *__restrict__ X, const int32_t *__restrict__ fa, rm_rings rings, const int *__restrict__ estart,
+__global__ void __launch_bounds__(256) rm_collapse_valid_kernel(const double *__restrict__ X, const int32_t *__restrict__ fa, er_rings rings, const int *__restrict__ estart,
                                                                 const int *__restrict__ sh, const int *__restrict__ eval, const int *__restrict__ vborder,
                                                                 const int *__restrict__ vfirst, const int *__restrict__ vlast, const int *__restrict__ vf,
                                                                 const double *__restrict__ nref, int E, double low2, double high2, double flip2, rm_u64 salt,
@@ -320,82 +206,25 @@ __global__ void __launch_bounds__(256) rm_collapse_valid_kernel(const double *__
     if (dev_tid() >= E) return;
     const long e = dev_tid();
     const int lo = rings.elo[e], hi = rings.ehi[e], val = eval[e];
-    ehash[e] = rm_mix(salt, lo, hi);
+    ehash[e] = er_mix(salt, lo, hi);
     cand[e] = 0;
-    if (!(rm_len2(rm_load(X, lo), rm_load(X, hi)) < low2)) return;
-    int refused = -1;
-    if (val != 1 && val != 2) refused = 0;
+    if (!(rm_len2(er_load(X, lo), er_load(X, hi)) < low2)) return;
+    int refused = er_refused_abcd(rings, fa, estart, sh, vborder, e, lo, hi, val);
     if (refused < 0) {
-        const rm_ring a = rings.at(lo), b = rings.at(hi);
-        int i = 0, j = 0, common = 0;
-        while (i < a.n && j < b.n) {                          // at most a.n + b.n steps
-            const int x = a.other(i), y = b.other(j);
-            if (x == y) { ++common; ++i; ++j; }
-            else if (x < y) ++i;
-            else ++j;
-        }
-        if (common != val) refused = 1;
-    }
-    if (refused < 0 && val == 2 && vborder[lo] && vborder[hi]) refused = 2;
-    if (refused < 0) {
-        for (int i = estart[e]; i < estart[e + 1]; ++i) {     // val <= 2 half-edges
-            const long h = sh[i], f = h / 3;
-            const int o = fa[3 * f + ((int)(h - 3 * f) + 2) % 3];
-            if (rings.degree(o) < (vborder[o] ? 3 : 4)) refused = 3;
-        }
-    }
-    if (refused < 0) {
-        const rm_v3 p = rm_collapse_point(X, vborder, lo, hi);
+        const er_v3 p = rm_collapse_point(X, vborder, lo, hi);
 #pragma unroll 1
         for (int side = 0; side < 2 && refused < 0; ++side) {
-            const rm_ring r = rings.at(side ? hi : lo);
+            const er_ring r = rings.at(side ? hi : lo);
             for (int j = 0; j < r.n; ++j) {
                 const int w = r.other(j);
                 if (w == lo || w == hi) continue;
-                if (!(rm_len2(rm_load(X, w), p) <= high2)) { refused = 4; break; }
+                if (!(rm_len2(er_load(X, w), p) <= high2)) { refused = 4; break; }
             }
         }
-#pragma unroll 1
-        for (int side = 0; side < 2 && refused < 0; ++side) {
-            const int end = side ? hi : lo, other = side ? lo : hi;
-            for (int i = vfirst[end]; i < vlast[end]; ++i) {
-                const long h = vf[i], f = h / 3;
-                const int t[3] = {fa[3 * f], fa[3 * f + 1], fa[3 * f + 2]};
-                if (t[0] == other || t[1] == other || t[2] == other) continue;
-                if (!rm_keeps_side(X, t, (int)(h - 3 * f), p, {nref[3 * f], nref[3 * f + 1], nref[3 * f + 2]}, flip2)) { refused = 5; break; }
-            }
-        }
+        if (refused < 0 && !er_fans_keep_side(X, fa, vfirst, vlast, vf, nref, lo, hi, p, flip2)) refused = 5;
     }
     if (refused >= 0) { atomicAdd(cnt + RM_REF + refused, 1); return; }      // an integer count has no order
     cand[e] = 1;
-}
-
-__device__ __forceinline__ bool rm_before(const rm_u64 *__restrict__ ehash, int a, int b) {      // b may be -1: nothing yet
-    return b < 0 || ehash[a] < ehash[b] || (ehash[a] == ehash[b] && a < b);
-}
-
-// m(v): the valid edge of least priority at v, or -1
-__global__ void rm_vertex_min_kernel(rm_rings rings, int V, const int *__restrict__ cand, const rm_u64 *__restrict__ ehash, int *__restrict__ mbest) {
-    if (dev_tid() >= V) return;
-    const rm_ring r = rings.at(dev_tid());
-    int best = -1;
-    for (int j = 0; j < r.n; ++j) {
-        const int e = r.edge(j);
-        if (cand[e] && rm_before(ehash, e, best)) best = e;
-    }
-    mbest[dev_tid()] = best;
-}
-
-// M(v): the least m over v and its neighbours
-__global__ void rm_ring_min_kernel(rm_rings rings, int V, const int *__restrict__ mbest, const rm_u64 *__restrict__ ehash, int *__restrict__ Mbest) {
-    if (dev_tid() >= V) return;
-    const rm_ring r = rings.at(dev_tid());
-    int best = mbest[dev_tid()];
-    for (int j = 0; j < r.n; ++j) {
-        const int e = mbest[r.other(j)];
-        if (e >= 0 && rm_before(ehash, e, best)) best = e;
-    }
-    Mbest[dev_tid()] = best;
 }
 
 __global__ void rm_collapse_select_kernel(int E, const int *__restrict__ cand, const int *__restrict__ elo, const int *__restrict__ ehi, const int *__restrict__ eval,
@@ -416,33 +245,17 @@ __global__ void rm_collapse_apply_kernel(int E, const int *__restrict__ sel, con
     if (dev_tid() >= E || !sel[dev_tid()]) return;
     const long e = dev_tid();
     const int lo = elo[e], hi = ehi[e];
-    const rm_v3 p = rm_collapse_point(X, vborder, lo, hi);
-    if (!rm_same_bits(p, rm_load(X, lo))) origin[lo] = -1;
+    const er_v3 p = rm_collapse_point(X, vborder, lo, hi);
+    if (!rm_same_bits(p, er_load(X, lo))) origin[lo] = -1;
     X[3L * lo] = p.x; X[3L * lo + 1] = p.y; X[3L * lo + 2] = p.z;
     rename[hi] = lo;
-}
-
-__global__ void rm_rename_faces_kernel(int32_t *__restrict__ fa, int F, const int *__restrict__ rename, int *__restrict__ live) {
-    if (dev_tid() >= F) return;
-    const long f = dev_tid();
-    const int a = rename[fa[3 * f]], b = rename[fa[3 * f + 1]], c = rename[fa[3 * f + 2]];
-    fa[3 * f] = a; fa[3 * f + 1] = b; fa[3 * f + 2] = c;
-    live[f] = (a != b && b != c && a != c) ? 1 : 0;
-}
-
-__global__ void rm_compact_live_kernel(const int32_t *__restrict__ fa, const double *__restrict__ nref, int F, const int *__restrict__ live,
-                                       const int *__restrict__ lpos, int32_t *__restrict__ out, double *__restrict__ nout) {
-    if (dev_tid() >= F || !live[dev_tid()]) return;
-    const long f = dev_tid(), n = lpos[f];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { out[3 * n + c] = fa[3 * f + c]; nout[3 * n + c] = nref[3 * f + c]; }
 }
 
 // ---- C: flip ----------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int rm_dev2(int deg, int border) { const int x = deg - (border ? 4 : 6); return x * x; }
 
 // one lane per edge of valence 2: orient, the gain, rules same, edge, degree, long, fold; a valid flip lowers m at a, b, c, d
-__global__ void __launch_bounds__(256) rm_flip_valid_kernel(const double *__restrict__ X, const int32_t *__restrict__ fa, rm_rings rings, const int *__restrict__ estart,
+__global__ void __launch_bounds__(256) rm_flip_valid_kernel(const double *__restrict__ X, const int32_t *__restrict__ fa, er_rings rings, const int *__restrict__ estart,
                                                             const int *__restrict__ sh, const int *__restrict__ eval, const int *__restrict__ vborder,
                                                             const double *__restrict__ nref, int E, double high2, double flip2, rm_u64 salt,
                                                             int *__restrict__ cand, int *__restrict__ qc, int *__restrict__ qd, rm_u64 *__restrict__ vmin, int *cnt) {
@@ -464,26 +277,26 @@ __global__ void __launch_bounds__(256) rm_flip_valid_kernel(const double *__rest
     int refused = -1;
     if (c == d) refused = 7;
     if (refused < 0) {
-        const rm_ring r = rings.at(c);
+        const er_ring r = rings.at(c);
         for (int j = 0; j < r.n; ++j)
             if (r.other(j) == d) { refused = 8; break; }
     }
     if (refused < 0 && (da < (ba ? 3 : 4) || db < (bb ? 3 : 4))) refused = 9;
-    const rm_v3 xa = rm_load(X, a), xb = rm_load(X, b), xc = rm_load(X, c), xd = rm_load(X, d);
+    const er_v3 xa = er_load(X, a), xb = er_load(X, b), xc = er_load(X, c), xd = er_load(X, d);
     if (refused < 0 && !(rm_len2(xc, xd) <= high2)) refused = 10;
     if (refused < 0) {
-        const rm_v3 n1 = rm_normal(rm_load(X, fa[3 * f1]), rm_load(X, fa[3 * f1 + 1]), rm_load(X, fa[3 * f1 + 2]));
-        const rm_v3 n2 = rm_normal(rm_load(X, fa[3 * f2]), rm_load(X, fa[3 * f2 + 1]), rm_load(X, fa[3 * f2 + 2]));
-        const rm_v3 np = {nref[3 * f1] + nref[3 * f2], nref[3 * f1 + 1] + nref[3 * f2 + 1], nref[3 * f1 + 2] + nref[3 * f2 + 2]};
-        const rm_v3 w1 = rm_normal(xc, xa, xd), w2 = rm_normal(xd, xb, xc);
-        const double ww1 = rm_dot(w1, w1), ww2 = rm_dot(w2, w2);
-        if (!(rm_keeps(n1, w1, ww1, flip2) && rm_keeps(n2, w1, ww1, flip2) && rm_keeps(np, w1, ww1, flip2) && rm_keeps(n1, w2, ww2, flip2) &&
-              rm_keeps(n2, w2, ww2, flip2) && rm_keeps(np, w2, ww2, flip2)))
+        const er_v3 n1 = er_normal(er_load(X, fa[3 * f1]), er_load(X, fa[3 * f1 + 1]), er_load(X, fa[3 * f1 + 2]));
+        const er_v3 n2 = er_normal(er_load(X, fa[3 * f2]), er_load(X, fa[3 * f2 + 1]), er_load(X, fa[3 * f2 + 2]));
+        const er_v3 np = {nref[3 * f1] + nref[3 * f2], nref[3 * f1 + 1] + nref[3 * f2 + 1], nref[3 * f1 + 2] + nref[3 * f2 + 2]};
+        const er_v3 w1 = er_normal(xc, xa, xd), w2 = er_normal(xd, xb, xc);
+        const double ww1 = er_dot(w1, w1), ww2 = er_dot(w2, w2);
+        if (!(er_keeps(n1, w1, ww1, flip2) && er_keeps(n2, w1, ww1, flip2) && er_keeps(np, w1, ww1, flip2) && er_keeps(n1, w2, ww2, flip2) &&
+              er_keeps(n2, w2, ww2, flip2) && er_keeps(np, w2, ww2, flip2)))
             refused = 11;
     }
     if (refused >= 0) { atomicAdd(cnt + RM_REF + refused, 1); return; }
     cand[e] = 1; qc[e] = c; qd[e] = d;
-    const rm_u64 key = ((rm_mix(salt, a, b) & 0xffffffffull) << 32) | (rm_u64)(unsigned)e;
+    const rm_u64 key = ((er_mix(salt, a, b) & 0xffffffffull) << 32) | (rm_u64)(unsigned)e;
     atomicMin(vmin + a, key); atomicMin(vmin + b, key); atomicMin(vmin + c, key); atomicMin(vmin + d, key);      // a minimum has no order
 }
 
@@ -494,7 +307,7 @@ __global__ void rm_flip_apply_kernel(int32_t *__restrict__ fa, double *__restric
     if (dev_tid() >= E || !cand[dev_tid()]) return;
     const long e = dev_tid();
     const int a = elo[e], b = ehi[e], c = qc[e], d = qd[e];
-    const rm_u64 key = ((rm_mix(salt, a, b) & 0xffffffffull) << 32) | (rm_u64)(unsigned)e;
+    const rm_u64 key = ((er_mix(salt, a, b) & 0xffffffffull) << 32) | (rm_u64)(unsigned)e;
     if (vmin[a] != key || vmin[b] != key || vmin[c] != key || vmin[d] != key) return;
     const long h1 = sh[estart[e]], h2 = sh[estart[e] + 1];
     const long f1 = (fa[h1] == a ? h1 : h2) / 3, f2 = (fa[h1] == a ? h2 : h1) / 3;
@@ -510,39 +323,39 @@ __global__ void rm_flip_apply_kernel(int32_t *__restrict__ fa, double *__restric
 
 // ---- D: relax ---------------------------------------------------------------------------------------------------------------------
 // one lane per vertex: X -> Xn (every vertex is written: the moved ones their p', the others what they were)
-__global__ void __launch_bounds__(256) rm_relax_kernel(const double *__restrict__ X, double *__restrict__ Xn, const int32_t *__restrict__ fa, rm_rings rings, int V,
+__global__ void __launch_bounds__(256) rm_relax_kernel(const double *__restrict__ X, double *__restrict__ Xn, const int32_t *__restrict__ fa, er_rings rings, int V,
                                                        const int *__restrict__ vborder, const int *__restrict__ vheavy, const int *__restrict__ vfirst,
                                                        const int *__restrict__ vlast, const int *__restrict__ vf, const double *__restrict__ nref, double relax,
                                                        double flip2, int *__restrict__ origin, int *cnt) {
     if (dev_tid() >= V) return;
     const long v = dev_tid();
-    const rm_v3 p = rm_load(X, v);
-    rm_v3 out = p;
+    const er_v3 p = er_load(X, v);
+    er_v3 out = p;
     const int i0 = vfirst[v], i1 = vlast[v];
     if (i1 > i0 && !vborder[v] && !vheavy[v]) {
-        const rm_ring r = rings.at(v);
+        const er_ring r = rings.at(v);
         double sx = 0.0, sy = 0.0, sz = 0.0;
         for (int j = 0; j < r.n; ++j) {
-            const rm_v3 w = rm_load(X, r.other(j));
+            const er_v3 w = er_load(X, r.other(j));
             sx = sx + w.x; sy = sy + w.y; sz = sz + w.z;
         }
         const double deg = (double)r.n;
-        rm_v3 n = {0.0, 0.0, 0.0};
+        er_v3 n = {0.0, 0.0, 0.0};
         for (int i = i0; i < i1; ++i) {
             const long f = vf[i] / 3;
-            const rm_v3 m = rm_normal(rm_load(X, fa[3 * f]), rm_load(X, fa[3 * f + 1]), rm_load(X, fa[3 * f + 2]));
+            const er_v3 m = er_normal(er_load(X, fa[3 * f]), er_load(X, fa[3 * f + 1]), er_load(X, fa[3 * f + 2]));
             n.x = n.x + m.x; n.y = n.y + m.y; n.z = n.z + m.z;
         }
-        const double nn = rm_dot(n, n);
+        const double nn = er_dot(n, n);
         if (nn > 0.0 && isfinite(nn)) {
-            const rm_v3 d = {sx / deg - p.x, sy / deg - p.y, sz / deg - p.z};
-            const double t = rm_dot(d, n) / nn;
-            const rm_v3 q = {p.x + relax * (d.x - n.x * t), p.y + relax * (d.y - n.y * t), p.z + relax * (d.z - n.z * t)};
+            const er_v3 d = {sx / deg - p.x, sy / deg - p.y, sz / deg - p.z};
+            const double t = er_dot(d, n) / nn;
+            const er_v3 q = {p.x + relax * (d.x - n.x * t), p.y + relax * (d.y - n.y * t), p.z + relax * (d.z - n.z * t)};
             bool fine = true;
             for (int i = i0; i < i1 && fine; ++i) {
                 const long h = vf[i], f = h / 3;
                 const int t3[3] = {fa[3 * f], fa[3 * f + 1], fa[3 * f + 2]};
-                fine = rm_keeps_side(X, t3, (int)(h - 3 * f), q, {nref[3 * f], nref[3 * f + 1], nref[3 * f + 2]}, flip2);
+                fine = er_keeps_side(X, t3, (int)(h - 3 * f), q, {nref[3 * f], nref[3 * f + 1], nref[3 * f + 2]}, flip2);
             }
             if (!fine) atomicAdd(cnt + RM_RELAX_REF, 1);
             else if (!rm_same_bits(q, p)) { out = q; origin[v] = -1; atomicAdd(cnt + RM_RELAXED, 1); }
@@ -552,10 +365,6 @@ __global__ void __launch_bounds__(256) rm_relax_kernel(const double *__restrict_
 }
 
 // ---- output -----------------------------------------------------------------------------------------------------------------------
-__global__ void rm_mark_named_kernel(const int32_t *__restrict__ fa, long n, int *__restrict__ stays) {
-    if (dev_tid() < n) stays[fa[dev_tid()]] = 1;              // every writer stores the same 1
-}
-
 __global__ void rm_out_vertices_kernel(const double *__restrict__ X, const int *__restrict__ origin, int V, const int *__restrict__ stays,
                                        const int *__restrict__ newid, double *__restrict__ out, int32_t *__restrict__ out_origin) {
     if (dev_tid() >= V || !stays[dev_tid()]) return;
@@ -563,10 +372,6 @@ __global__ void rm_out_vertices_kernel(const double *__restrict__ X, const int *
 #pragma unroll
     for (int j = 0; j < 3; ++j) out[3 * n + j] = X[3 * v + j];
     if (out_origin) out_origin[n] = origin[v];
-}
-
-__global__ void rm_out_faces_kernel(const int32_t *__restrict__ fa, long n, const int *__restrict__ newid, int32_t *__restrict__ out) {
-    if (dev_tid() < n) out[dev_tid()] = newid[fa[dev_tid()]];
 }
 
 }  // namespace surfd
@@ -629,7 +434,7 @@ static int rm_reserve(surfd_meshremesh *m, long V, long F, hipStream_t st) {
         if (e == hipSuccess && m->Fn > 0) e = hipMemcpyAsync(n.nra, o.nra, dev_bytes<double>(3L * m->Fn), hipMemcpyDeviceToDevice, st);
     }
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(rm_iota_kernel, dim3(dev_grid(3 * F)), dim3(256), 0, st, n.iota, 3 * F);
+        hipLaunchKernelGGL(er_iota_kernel, dim3(dev_grid(3 * F)), dim3(256), 0, st, n.iota, 3 * F);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -648,43 +453,11 @@ extern "C" void surfd_meshremesh_destroy(surfd_meshremesh *m) {
 
 static int rm_read(surfd_meshremesh *m, int *hc, hipStream_t st) { return read_words(m->a.cnt, hc, RM_WORDS, st); }
 
-static rm_u64 rm_salt(uint64_t seed, uint64_t rnd) {
-    rm_u64 salt = seed + 0x9e3779b97f4a7c15ull * (rm_u64)(rnd + 1);
-    salt ^= salt >> 30; salt *= 0xbf58476d1ce4e5b9ull; salt ^= salt >> 27; salt *= 0x94d049bb133111ebull; salt ^= salt >> 31;
-    return salt;
-}
-
-// the structure of a round over the current faces (Fn > 0): the edges, and with `rings` the corners, neighbours and flags of every vertex
-static int rm_structure(surfd_meshremesh *m, bool rings, int *E_out, hipStream_t st) {
-    const rm_arrays &a = m->a;
-    CubWorkspace &cub = m->cub;
-    const int V = m->Vn;
-    const long n = 3L * m->Fn;
-    int vbits = 1;                                           // of a vertex index below V; never a sort over zero bits
-    while ((1L << vbits) < V) ++vbits;
+// the structure of a round over the handle's faces (Fn > 0): the flags zeroed, then er_structure over the arrays as they are now
+static int rm_round_structure(surfd_meshremesh *m, bool rings, int *E, hipStream_t st) {
     int hc[RM_WORDS];
-    HIP_TRY(hipMemsetAsync(a.vborder, 0, rm_round_zero_bytes(m->Vcap), st));      // vborder .. hlast (meshremesh_layout.h)
-    DEV_LAUNCH(rm_half_keys_kernel, n, (const int32_t *)a.fa, n, a.hkey, a.vkey);
-    SURFD_TRY(cub.sort_pairs(a.hkey, a.hkeys, a.iota, a.sh, (int)n, 32 + vbits, st));
-    DEV_LAUNCH(run_heads_kernel<~0ull>, n, (const rm_u64 *)a.hkeys, (int)n, a.head);
-    SURFD_TRY(cub.exclusive_sum(a.head, a.hpos, (int)n, st));
-    SURFD_TRY(scan_total(a.head, a.hpos, (int)n, a.cnt + RM_E, st));
-    DEV_LAUNCH(rm_edge_fill_kernel, n, (const rm_u64 *)a.hkeys, (const int *)a.sh, (const int *)a.head, (const int *)a.hpos, n, a.eoh, a.estart, a.elo, a.ehi);
-    if (rings) {
-        SURFD_TRY(cub.sort_pairs(a.vkey, a.vkeys, a.iota, a.vf, (int)n, vbits, st));
-        DEV_LAUNCH(rm_run_bounds_kernel, n, (const unsigned *)a.vkeys, n, a.vfirst, a.vlast);
-    }
-    SURFD_TRY(rm_read(m, hc, st));
-    const int E = hc[RM_E];
-    *E_out = E;
-    unsigned *hikey = a.vkey, *hikeys = a.vkeys;             // the corner keys are spent
-    DEV_LAUNCH(rm_edge_info_kernel, E, (const int *)a.estart, (const int *)a.elo, (const int *)a.ehi, E, a.eval, a.vborder, a.vheavy, hikey);
-    if (rings) {
-        DEV_LAUNCH(rm_run_bounds_kernel, E, (const unsigned *)a.elo, (long)E, a.lfirst, a.llast);
-        SURFD_TRY(cub.sort_pairs(hikey, hikeys, a.iota, a.hie, E, vbits, st));
-        DEV_LAUNCH(rm_run_bounds_kernel, E, (const unsigned *)hikeys, (long)E, a.hfirst, a.hlast);
-    }
-    return SURFD_OK;
+    HIP_TRY(hipMemsetAsync(m->a.vborder, 0, rm_round_zero_bytes(m->Vcap), st));      // vborder .. hlast (meshremesh_layout.h)
+    return er_structure(m->a, m->cub, m->Vn, m->Fn, rings, m->a.cnt, RM_WORDS, RM_E, hc, E, st);
 }
 
 extern "C" int surfd_meshremesh_create(const double *vertices, int V, const int32_t *faces, int F, double low2, double high2, double flip_cos,
@@ -707,15 +480,12 @@ extern "C" int surfd_meshremesh_create(const double *vertices, int V, const int3
     if (F > 0) {                                             // with V == 0 too: every index is then outside [0, V)
         int *nonfinite = a.mbest, *keep = a.live, *kpos = a.lpos;
         DEV_LAUNCH(rm_vertex_flags_kernel, V, vertices, V, nonfinite, a.X, a.origin);
-        DEV_LAUNCH(rm_face_mark_kernel, F, faces, F, V, (const int *)nonfinite, keep, a.cnt + RM_BAD);
-        SURFD_TRY(m->cub.exclusive_sum(keep, kpos, F, st));
-        SURFD_TRY(scan_total(keep, kpos, F, a.cnt + RM_KEPT, st));
-        DEV_LAUNCH(rm_compact_kept_kernel, F, faces, F, (const int *)keep, (const int *)kpos, a.fa);
+        SURFD_TRY(er_kept_faces(m->cub, faces, F, V, nonfinite, keep, kpos, nullptr, a.cnt + RM_BAD, a.cnt + RM_KEPT, a.fa, st));
         int hc[RM_WORDS];
         SURFD_TRY(rm_read(m.get(), hc, st));
         if (hc[RM_BAD]) return mesh_bad_index(who, V);
         m->Fn = hc[RM_KEPT];
-        if (m->Fn > 0) DEV_LAUNCH(rm_face_normals_kernel, m->Fn, (const double *)a.X, (const int32_t *)a.fa, m->Fn, a.nra);
+        if (m->Fn > 0) DEV_LAUNCH(er_face_normals_kernel, m->Fn, (const double *)a.X, (const int32_t *)a.fa, m->Fn, a.nra);
     } else if (V > 0) {
         DEV_LAUNCH(rm_vertex_flags_kernel, V, vertices, V, a.mbest, a.X, a.origin);
     }
@@ -733,7 +503,7 @@ extern "C" int surfd_meshremesh_sizes(const surfd_meshremesh *m, int64_t *vertic
 static int rm_split_round(surfd_meshremesh *m, int *marked, hipStream_t st) {
     int hc[RM_WORDS], E;
     for (;;) {
-        SURFD_TRY(rm_structure(m, false, &E, st));
+        SURFD_TRY(rm_round_structure(m, false, &E, st));
         const rm_arrays &a = m->a;
         int *mark = a.sel, *mpos = a.selpos, *mval = a.cand, *mvpos = a.hie, *fcnt = a.live, *fpos = a.lpos;
         DEV_LAUNCH(rm_split_mark_kernel, E, (const double *)a.X, (const int *)a.elo, (const int *)a.ehi, (const int *)a.eval, E, m->high2, mark, mval);
@@ -768,24 +538,24 @@ static int rm_split_round(surfd_meshremesh *m, int *marked, hipStream_t st) {
 
 static int rm_collapse_round(surfd_meshremesh *m, int64_t *counts, int *selected, hipStream_t st) {
     int hc[RM_WORDS], E;
-    const rm_u64 salt = rm_salt(m->seed, m->tick++);
-    SURFD_TRY(rm_structure(m, true, &E, st));
+    const rm_u64 salt = er_salt(m->seed, m->tick++);
+    SURFD_TRY(rm_round_structure(m, true, &E, st));
     const rm_arrays &a = m->a;
     const int V = m->Vn, Fn = m->Fn;
-    const rm_rings rings = {a.elo, a.ehi, a.hie, a.hfirst, a.hlast, a.lfirst, a.llast};
+    const er_rings rings = {a.elo, a.ehi, a.hie, a.hfirst, a.hlast, a.lfirst, a.llast};
     HIP_TRY(hipMemsetAsync(a.cnt + RM_SEL, 0, (RM_WORDS - RM_SEL) * sizeof(int), st));
     DEV_LAUNCH(rm_collapse_valid_kernel, E, (const double *)a.X, (const int32_t *)a.fa, rings, (const int *)a.estart, (const int *)a.sh, (const int *)a.eval,
                (const int *)a.vborder, (const int *)a.vfirst, (const int *)a.vlast, (const int *)a.vf, (const double *)a.nra, E, m->low2, m->high2, m->flip2,
                salt, a.cand, a.ehash, a.cnt);
-    DEV_LAUNCH(rm_vertex_min_kernel, V, rings, V, (const int *)a.cand, (const rm_u64 *)a.ehash, a.mbest);
-    DEV_LAUNCH(rm_ring_min_kernel, V, rings, V, (const int *)a.mbest, (const rm_u64 *)a.ehash, a.Mbest);
+    DEV_LAUNCH(er_vertex_min_kernel, V, rings, V, (const int *)a.cand, (const rm_u64 *)a.ehash, a.mbest);
+    DEV_LAUNCH(er_ring_min_kernel, V, rings, V, (const int *)a.mbest, (const rm_u64 *)a.ehash, a.Mbest);
     DEV_LAUNCH(rm_collapse_select_kernel, E, E, (const int *)a.cand, (const int *)a.elo, (const int *)a.ehi, (const int *)a.eval, (const int *)a.Mbest, a.sel, a.cnt);
-    DEV_LAUNCH(rm_iota_kernel, V, a.rename, (long)V);
+    DEV_LAUNCH(er_iota_kernel, V, a.rename, (long)V);
     DEV_LAUNCH(rm_collapse_apply_kernel, E, E, (const int *)a.sel, (const int *)a.elo, (const int *)a.ehi, (const int *)a.vborder, a.X, a.origin, a.rename);
-    DEV_LAUNCH(rm_rename_faces_kernel, Fn, a.fa, Fn, (const int *)a.rename, a.live);
+    DEV_LAUNCH(er_rename_faces_kernel, Fn, a.fa, Fn, (const int *)a.rename, a.live);
     SURFD_TRY(m->cub.exclusive_sum(a.live, a.lpos, Fn, st));
     SURFD_TRY(scan_total(a.live, a.lpos, Fn, a.cnt + RM_FNEW, st));
-    DEV_LAUNCH(rm_compact_live_kernel, Fn, (const int32_t *)a.fa, (const double *)a.nra, Fn, (const int *)a.live, (const int *)a.lpos, a.fb, a.nrb);
+    DEV_LAUNCH(er_compact_live_kernel, Fn, (const int32_t *)a.fa, (const double *)a.nra, Fn, (const int *)a.live, (const int *)a.lpos, a.fb, a.nrb);
     SURFD_TRY(rm_read(m, hc, st));
     for (int i = 0; i < 6; ++i) counts[12 + i] = hc[RM_REF + i];
     counts[3] += hc[RM_SEL];
@@ -801,10 +571,10 @@ static int rm_collapse_round(surfd_meshremesh *m, int64_t *counts, int *selected
 
 static int rm_flip_round(surfd_meshremesh *m, int64_t *counts, int *selected, hipStream_t st) {
     int hc[RM_WORDS], E;
-    const rm_u64 salt = rm_salt(m->seed, m->tick++);
-    SURFD_TRY(rm_structure(m, true, &E, st));
+    const rm_u64 salt = er_salt(m->seed, m->tick++);
+    SURFD_TRY(rm_round_structure(m, true, &E, st));
     const rm_arrays &a = m->a;
-    const rm_rings rings = {a.elo, a.ehi, a.hie, a.hfirst, a.hlast, a.lfirst, a.llast};
+    const er_rings rings = {a.elo, a.ehi, a.hie, a.hfirst, a.hlast, a.lfirst, a.llast};
     int *qc = a.head, *qd = a.hpos;                          // the heads of the edge runs are spent
     HIP_TRY(hipMemsetAsync(a.cnt + RM_SEL, 0, (RM_WORDS - RM_SEL) * sizeof(int), st));
     HIP_TRY(hipMemsetAsync(a.vmin, 0xFF, dev_bytes<rm_u64>(m->Vn), st));
@@ -816,19 +586,6 @@ static int rm_flip_round(surfd_meshremesh *m, int64_t *counts, int *selected, hi
     for (int i = 0; i < 6; ++i) counts[18 + i] = hc[RM_REF + 6 + i];
     counts[5] += hc[RM_SEL];
     *selected = hc[RM_SEL];
-    return SURFD_OK;
-}
-
-// the number of vertices the faces name -> cnt[RM_VOUT]; stays is left set
-static int rm_count_named(surfd_meshremesh *m, hipStream_t st) {
-    const rm_arrays &a = m->a;
-    HIP_TRY(hipMemsetAsync(a.stays, 0, dev_bytes<int>(m->Vn), st));
-    HIP_TRY(hipMemsetAsync(a.cnt + RM_VOUT, 0, sizeof(int), st));
-    if (m->Fn > 0) {
-        DEV_LAUNCH(rm_mark_named_kernel, 3L * m->Fn, (const int32_t *)a.fa, 3L * m->Fn, a.stays);
-        SURFD_TRY(m->cub.exclusive_sum(a.stays, a.newid, m->Vn, st));
-        SURFD_TRY(scan_total(a.stays, a.newid, m->Vn, a.cnt + RM_VOUT, st));
-    }
     return SURFD_OK;
 }
 
@@ -866,8 +623,8 @@ extern "C" int surfd_meshremesh_iterate(surfd_meshremesh *m, int split_rounds, i
     HIP_TRY(hipMemsetAsync(m->a.cnt + RM_RELAXED, 0, 2 * sizeof(int), st));
     if (relax_sweeps > 0 && m->Fn > 0) {
         int E;
-        SURFD_TRY(rm_structure(m, true, &E, st));
-        const rm_rings rings = {m->a.elo, m->a.ehi, m->a.hie, m->a.hfirst, m->a.hlast, m->a.lfirst, m->a.llast};
+        SURFD_TRY(rm_round_structure(m, true, &E, st));
+        const er_rings rings = {m->a.elo, m->a.ehi, m->a.hie, m->a.hfirst, m->a.hlast, m->a.lfirst, m->a.llast};
         for (int r = 0; r < relax_sweeps; ++r) {
             const rm_arrays &a = m->a;
             DEV_LAUNCH(rm_relax_kernel, m->Vn, (const double *)a.X, a.X2, (const int32_t *)a.fa, rings, m->Vn, (const int *)a.vborder, (const int *)a.vheavy,
@@ -875,7 +632,7 @@ extern "C" int surfd_meshremesh_iterate(surfd_meshremesh *m, int split_rounds, i
             std::swap(m->a.X, m->a.X2);
         }
     }
-    SURFD_TRY(rm_count_named(m, st));
+    SURFD_TRY(er_count_named(m->cub, m->a.fa, m->Fn, m->Vn, m->a.stays, m->a.newid, m->a.cnt + RM_VOUT, st));
     int hc[RM_WORDS];
     SURFD_TRY(rm_read(m, hc, st));
     counts[0] = hc[RM_VOUT];
@@ -909,9 +666,9 @@ extern "C" int surfd_meshremesh_emit(surfd_meshremesh *m, double *out_vertices, 
     if (!out_vertices || !out_faces) SURFD_FAIL(SURFD_ERR_ARG, "%s: null argument", who);
     hipStream_t st = as_stream(s);
     const rm_arrays &a = m->a;
-    SURFD_TRY(rm_count_named(m, st));
+    SURFD_TRY(er_count_named(m->cub, a.fa, m->Fn, m->Vn, a.stays, a.newid, a.cnt + RM_VOUT, st));
     DEV_LAUNCH(rm_out_vertices_kernel, m->Vn, (const double *)a.X, (const int *)a.origin, m->Vn, (const int *)a.stays, (const int *)a.newid, out_vertices, out_origin);
-    DEV_LAUNCH(rm_out_faces_kernel, 3L * m->Fn, (const int32_t *)a.fa, 3L * m->Fn, (const int *)a.newid, out_faces);
+    DEV_LAUNCH(er_out_faces_kernel, 3L * m->Fn, (const int32_t *)a.fa, 3L * m->Fn, (const int *)a.newid, out_faces);
     int hc[RM_WORDS];
     SURFD_TRY(rm_read(m, hc, st));
     counts[0] = hc[RM_VOUT];
