@@ -74,6 +74,9 @@ def parse(argv=None):
     ap.add_argument("--simplify_faces", type=int, default=None, metavar="N",
                     help="make the mesh smaller on the GPU before it is written: edge collapses down to N faces, borders kept, sheets not glued "
                          "(surfd_amd.meshsimplify.simplify_quadric_decimation); the same rules as --simplify_cells, and not together with it")
+    ap.add_argument("--fill_holes", type=int, default=None, metavar="N",
+                    help="close every border loop of up to N edges (3 .. 1024) on the GPU by its minimum-area triangulation before the mesh is "
+                         "simplified, remeshed or written (surfd_amd.meshfill.fill_holes); the same rules as --simplify_cells")
     ap.add_argument("--remesh_edge", type=float, default=None, metavar="L",
                     help="remesh on the GPU before the mesh is written: triangles of roughly one size, edges of length L, vertices of valence 6 "
                          "(surfd_amd.meshremesh.remesh_isotropic); after --simplify_cells / --simplify_faces where given, the same rules as they")
@@ -103,6 +106,10 @@ def parse(argv=None):
         ap.error("--simplify_faces works on the device mesh: add --device_clean (open meshes) or --device_mc (--watertight)")
     if a.simplify_faces is not None and a.simplify_faces < 0:
         ap.error("--simplify_faces must not be negative")
+    if a.fill_holes is not None and not (a.device_mc if a.watertight else a.device_clean):
+        ap.error("--fill_holes works on the device mesh: add --device_clean (open meshes) or --device_mc (--watertight)")
+    if a.fill_holes is not None and not 3 <= a.fill_holes <= 1024:
+        ap.error("--fill_holes must lie in [3, 1024]")
     remesh = a.remesh_edge is not None or a.remesh_edge_mean is not None
     if a.remesh_edge is not None and a.remesh_edge_mean is not None:
         ap.error("--remesh_edge and --remesh_edge_mean exclude each other")
@@ -246,6 +253,9 @@ def run(a):
         def shape_mesh():
             if a.watertight and a.device_mc:
                 verts, faces = get_watertight_mesh(field, a.resolution, max_batch=2 ** 16, device=True, min_faces=5000)
+                if getattr(a, "fill_holes", None) is not None and len(faces):
+                    from surfd_amd.meshfill import fill_holes
+                    faces = fill_holes(verts, faces, max_edges=a.fill_holes)
                 if a.simplify_cells is not None and len(faces):
                     from surfd_amd.meshsimplify import simplify_vertex_clustering
                     verts, faces = simplify_vertex_clustering(verts, faces, cells=a.simplify_cells)
@@ -261,7 +271,7 @@ def run(a):
             device_post = bool(getattr(a, "device_post", False)) or device_clean
             v, t = get_mesh_from_udf(field, coords_range=(-1, 1), max_dist=0.1, N=a.resolution, max_batch=2 ** 16, differentiable=False,
                                      device_post=device_post, device_clean=device_clean, simplify_cells=getattr(a, "simplify_cells", None),
-                                     simplify_faces=getattr(a, "simplify_faces", None), **remesh_in_call(a))
+                                     simplify_faces=getattr(a, "simplify_faces", None), fill_holes=getattr(a, "fill_holes", None), **remesh_in_call(a))
             if not remesh_in_call(a):
                 v, t = remesh_on_device(a, v, t)
             if device_post:                                   # the mesh goes to the host once, for write_obj

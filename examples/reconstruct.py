@@ -50,6 +50,9 @@ def parse(argv=None):
     ap.add_argument("--simplify_faces", type=int, default=None, metavar="N",
                     help="make the mesh smaller on the GPU before it is written: edge collapses down to N faces, borders kept, sheets not glued "
                          "(surfd_amd.meshsimplify.simplify_quadric_decimation); the same rules as --simplify_cells, and not together with it")
+    ap.add_argument("--fill_holes", type=int, default=None, metavar="N",
+                    help="close every border loop of up to N edges (3 .. 1024) on the GPU by its minimum-area triangulation before the mesh is "
+                         "simplified, remeshed or written (surfd_amd.meshfill.fill_holes); the same rules as --simplify_cells")
     ap.add_argument("--remesh_edge", type=float, default=None, metavar="L",
                     help="remesh on the GPU before the mesh is written: triangles of roughly one size, edges of length L, vertices of valence 6 "
                          "(surfd_amd.meshremesh.remesh_isotropic); after --simplify_cells / --simplify_faces where given, the same rules as they")
@@ -87,6 +90,10 @@ def parse(argv=None):
         ap.error("--simplify_faces works on the device mesh: add --device_mc")
     if a.simplify_faces is not None and a.simplify_faces < 0:
         ap.error("--simplify_faces must not be negative")
+    if a.fill_holes is not None and a.watertight and not a.device_mc:
+        ap.error("--fill_holes works on the device mesh: add --device_mc")
+    if a.fill_holes is not None and not 3 <= a.fill_holes <= 1024:
+        ap.error("--fill_holes must lie in [3, 1024]")
     remesh = a.remesh_edge is not None or a.remesh_edge_mean is not None
     if a.remesh_edge is not None and a.remesh_edge_mean is not None:
         ap.error("--remesh_edge and --remesh_edge_mean exclude each other")
@@ -200,7 +207,7 @@ def triangle_quality_of(a, verts, faces, shape_mesh):
             "triangle_quality": triangle_quality(*on_device(verts, faces), L)}
 
 
-def item_metrics(path, verts, faces, field, seed, mesh_quality=False, accel="tiles", topology=False):
+def item_metrics(path, verts, faces, field, seed, mesh_quality=False, accel="tiles", topology=False, hole_filling=None):
     """what --metrics records for one item, or None where the input carries no mesh: mesh_distance between the reconstruction
     and the original; the IoU of their surface voxels on a 64^3 grid over [-1, 1]^3 (voxel_iou_surface_64); the normal
     consistency of 16 Ki = 16 384 surface points per mesh with their face normals, unsigned (normal_consistency_16: the number
@@ -208,7 +215,9 @@ def item_metrics(path, verts, faces, field, seed, mesh_quality=False, accel="til
     decoder's UDF at those queries.  ``mesh_quality`` adds self_intersecting_faces: the share of the reconstruction's faces with
     area that pass through or touch another of its faces beyond what neighbours share (surfd_amd.meshintersect).  ``topology``
     adds topology: the numbers of surfd_amd.meshtopo.MeshTopology.summary() for the reconstruction without its per-patch list
-    (edges by class, Euler characteristic, components, border loops, closed, edge_manifold, orientable, ...).  ``accel``:
+    (edges by class, Euler characteristic, components, border loops, closed, edge_manifold, orientable, ...) and, with
+    ``hole_filling`` (the counts of --fill_holes: loops_filled, caps, loops_too_long, irregular_border_edges, ...), those counts as
+    hole_filling and the lengths of the border loops that are left as border_loop_sizes (surfd_amd.meshfill.hole_sizes).  ``accel``:
     how mesh_distance searches the two meshes ("tiles" or "bvh": the same numbers)"""
     from surfd_amd import meshprep
     if not path.endswith(".npz"):
@@ -237,6 +246,10 @@ def item_metrics(path, verts, faces, field, seed, mesh_quality=False, accel="til
         if topology:
             from surfd_amd import meshtopo
             out["topology"] = {k: v for k, v in meshtopo.MeshTopology(rt, len(verts)).summary().items() if k != "patches"}
+            if hole_filling is not None:
+                from surfd_amd import meshfill
+                out["topology"]["hole_filling"] = dict(hole_filling)
+                out["topology"]["border_loop_sizes"] = meshfill.hole_sizes(rv, rt)
     if coords is not None:
         pred = torch.cat([field(coords[i:i + 2 ** 16]) for i in range(0, len(coords), 2 ** 16)])
         out["udf_mean_abs_error"] = float((pred.reshape(-1) - labels).abs().double().mean())
@@ -288,10 +301,15 @@ def run(a):
     metrics = {}
     for k, item in enumerate(ids):
         field = make_udf_func(decoder, latents[k], sample=k)
+        filled = {}                                          # the counts of --fill_holes for this item
 
         def shape_mesh(a=a):
             if a.watertight and a.device_mc:
                 v, t = get_watertight_mesh(field, a.resolution, max_batch=2 ** 16, device=True)
+                if getattr(a, "fill_holes", None) is not None and len(t):
+                    from surfd_amd.meshfill import fill_holes
+                    t, counts = fill_holes(v, t, max_edges=a.fill_holes, return_stats=True)
+                    filled.update(counts)
                 if a.simplify_cells is not None and len(t):
                     from surfd_amd.meshsimplify import simplify_vertex_clustering
                     v, t = simplify_vertex_clustering(v, t, cells=a.simplify_cells)
@@ -302,10 +320,15 @@ def run(a):
                 return v.cpu().numpy(), t.cpu().numpy()
             if a.watertight:
                 return get_watertight_mesh(field, a.resolution, max_batch=2 ** 16)
-            v, t = get_mesh_from_udf(field, coords_range=(-1, 1), max_dist=0.1, N=a.resolution, max_batch=2 ** 16, differentiable=False,
+            fill = getattr(a, "fill_holes", None)
+            v, t, *counts = get_mesh_from_udf(field, coords_range=(-1, 1), max_dist=0.1, N=a.resolution, max_batch=2 ** 16, differentiable=False,
                                      device_clean=a.simplify_cells is not None or a.simplify_faces is not None or a.remesh_edge is not None or
-                                     a.remesh_edge_mean is not None, simplify_cells=a.simplify_cells, simplify_faces=a.simplify_faces,
+                                     a.remesh_edge_mean is not None or fill is not None,
+                                     simplify_cells=a.simplify_cells, simplify_faces=a.simplify_faces,
+                                     **({"fill_holes": fill, "return_fill_stats": True} if fill is not None else {}),
                                      **remesh_in_call(a))
+            if counts:
+                filled.update(counts[0])
             if not remesh_in_call(a):
                 v, t = remesh_on_device(a, v, t)
             return v.cpu().numpy(), t.cpu().numpy()
@@ -322,7 +345,7 @@ def run(a):
                                        torch.as_tensor(np.ascontiguousarray(faces, dtype=np.int64)).reshape(-1, 3).cuda(), n_views=a.preview, size=512)
             written += render.save_views(a.output_dir, os.path.splitext(os.path.basename(path))[0], views)
         if a.metrics:
-            m = item_metrics(files[k], verts, faces, field, a.seed, a.mesh_quality, a.accel, a.topology)
+            m = item_metrics(files[k], verts, faces, field, a.seed, a.mesh_quality, a.accel, a.topology, filled if a.fill_holes is not None else None)
             if m is not None and a.mesh_quality and len(faces):
                 m.update(triangle_quality_of(a, verts, faces, shape_mesh))
             if m is not None:

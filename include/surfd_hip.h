@@ -808,6 +808,41 @@ int surfd_meshclean_drop_degenerate_faces(const double *vertices, int V, const i
 int surfd_meshclean_fill_small_holes(const int32_t *faces, int F, int V, int32_t *caps, int64_t cap_rows, int64_t *counts, surfd_stream s);
 
 /* ------------------------------------------------------------------------------------ */
+/* Hole filling: every border loop of up to max_edges edges is closed by its             */
+/* minimum-total-area triangulation (Barequet and Sharir 1995; no reference counterpart:  */
+/* the reference and trimesh close loops of 3 and 4 edges only, which is                  */
+/* surfd_meshclean_fill_small_holes).  tests/meshfill_ref.py restates the contract        */
+/* sequentially in numpy, csrc/meshfill.hip carries its text and the passes; the caps,    */
+/* their order, cap_loop and every count equal the restatement bit for bit.  Vertices     */
+/* fp64 [V,3], faces int32 [F,3], on the device; F >= 0, V >= 0, 3 F < 2^31.  An index    */
+/* outside [0, V) is SURFD_ERR_ARG, found on the device before anything is indexed by it. */
+/* fp64 + - * sqrt, integer sorts and scans; no float atomics, no result depends on the   */
+/* launch geometry.  One stream at a time per handle.                                     */
+/* ------------------------------------------------------------------------------------ */
+/* no reference counterpart; the plan of the hole filling (tests/meshfill_ref.py, loops):
+ * border half-edges as surfd_meshclean_fill_small_holes; a loop is a cycle of n >= 3 vertices that exactly one border half-edge
+ * leaves and exactly one enters, listed from its smallest vertex, numbered in ascending order of that vertex.  Finds the loops,
+ * bins those with n <= max_edges (3 .. 1024) by length and copies their points into the handle (the vertex array may go after
+ * the call).  counts[7] (host): loops_filled, caps, loops_too_long (n > max_edges), loops_nonfinite (0 here), irregular_border_edges
+ * (border half-edges on no loop), border_edges, longest_filled; caps is exact unless a loop turns out non-finite in run.  F = 0
+ * or V = 0 give an empty plan.  On a refusal *out stays null.  host-sync (one read). */
+typedef struct surfd_meshfill surfd_meshfill;
+int surfd_meshfill_plan(const double *vertices, int V, const int32_t *faces, int F, int max_edges, int64_t *counts, surfd_stream s,
+                        surfd_meshfill **out);
+/* no reference counterpart; the lengths of the hole filling's loops (tests/meshfill_ref.py, hole_sizes):
+ * sizes[rows] int32 on the device, rows >= loops_filled + loops_too_long of the plan: the length of every loop in loop order, the
+ * too long ones included.  Device to device on the stream; no sync. */
+int surfd_meshfill_loop_sizes(const surfd_meshfill *m, int32_t *sizes, int64_t rows, surfd_stream s);
+/* no reference counterpart; the triangulation and the caps of the hole filling (tests/meshfill_ref.py, fill_holes):
+ * per planned loop the table W[i][j] = min over k of (W[i][k] + W[k][j]) + area(i, k, j) over the reversed listing of its border, the
+ * least (sum, k) winning (a number before a NaN); n - 2 rows per loop in preorder of the recursion, loops in ascending number,
+ * written to caps[cap_rows,3] with cap_rows >= the planned caps; cap_loop[cap_rows] (nullable): the loop number of every row.  A
+ * loop whose total is not finite stays open.  counts[7] (host) as in plan, final.  The handle stays usable.  host-sync (one read;
+ * none where nothing was planned). */
+int surfd_meshfill_run(surfd_meshfill *m, int32_t *caps, int64_t cap_rows, int32_t *cap_loop, int64_t *counts, surfd_stream s);
+void surfd_meshfill_destroy(surfd_meshfill *m);
+
+/* ------------------------------------------------------------------------------------ */
 /* Mesh simplification: vertex clustering on a uniform grid with one representative per  */
 /* occupied cell (no reference counterpart: the reference writes its meshes at the full   */
 /* resolution of the grid).  tests/meshsimplify_ref.py restates the contract sequentially */

@@ -182,6 +182,10 @@ _SIGS = {
     "surfd_meshclean_drop_duplicate_faces": (C.c_int, [_P, C.c_int, _P, c_i64p, _P]),
     "surfd_meshclean_drop_degenerate_faces": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_double, _P, c_i64p, _P]),
     "surfd_meshclean_fill_small_holes": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, c_i64p, _P]),
+    "surfd_meshfill_plan": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, c_i64p, _P, C.POINTER(_P)]),
+    "surfd_meshfill_loop_sizes": (C.c_int, [_P, _P, C.c_int64, _P]),
+    "surfd_meshfill_run": (C.c_int, [_P, _P, C.c_int64, _P, c_i64p, _P]),
+    "surfd_meshfill_destroy": (None, [_P]),
     "surfd_meshsimplify_cluster": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int, C.c_double, _P, _P, _P, c_i64p, _P]),
     "surfd_meshsimplify_decimate": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_uint64,
                                               _P, _P, _P, c_i64p, _P]),

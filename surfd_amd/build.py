@@ -42,6 +42,7 @@ SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshclean.hip")         # merge / d
 SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshsimplify.hip")      # vertex clustering with mean / quadric representatives (surfd_amd/meshsimplify.py)
 SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshdecimate.hip")     # edge-collapse decimation to a face count (surfd_amd/meshsimplify.py)
 SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshremesh.hip")       # isotropic remeshing to an edge length (surfd_amd/meshremesh.py)
+SOURCES.insert(SOURCES.index("mcubes.cpp"), "meshfill.hip")         # hole filling: minimum-area caps for border loops (surfd_amd/meshfill.py)
 FILE_FLAGS = {"cloudnn.hip": ["-fno-slp-vectorize"], "cloudnormals.hip": ["-fno-slp-vectorize"]}
 
 

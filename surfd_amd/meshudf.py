@@ -357,7 +357,8 @@ def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[
                       max_batch: int = 2 ** 12, use_fast_grid_filler: bool = True, device_post: bool = False,
                       device_clean: bool = False, simplify_cells: Optional[int] = None,
                       simplify_faces: Optional[int] = None, remesh_edge: Optional[float] = None,
-                      remesh_iterations: int = 5) -> Tuple[Tensor, Tensor]:
+                      remesh_iterations: int = 5, fill_holes: Optional[int] = None,
+                      return_fill_stats: bool = False) -> Tuple[Tensor, ...]:
     """Triangulated mesh of the zero set of a UDF — same signature, defaults and return value as the reference
     (meshudf/meshudf.py:307-514): (vertices [V,3] float32, faces [F,3] int64) on the device.
 
@@ -380,7 +381,11 @@ def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[
     (surfd_amd.meshsimplify.simplify_quadric_decimation): borders stay where they were and sheets are not glued together.
     ``remesh_edge=L`` (no reference counterpart; the same two preconditions, combinable with either simplification): after it and
     before the border smoothing the mesh is remeshed towards edges of length L in ``remesh_iterations`` iterations
-    (surfd_amd.meshremesh.remesh_isotropic with its other defaults): triangles of roughly one size, vertices of valence 6."""
+    (surfd_amd.meshremesh.remesh_isotropic with its other defaults): triangles of roughly one size, vertices of valence 6.
+    ``fill_holes=N`` (no reference counterpart; the same two preconditions, combinable with the others): right after the cleaning
+    every border loop of up to N edges (3 .. 1024) is closed by its minimum-area triangulation (surfd_amd.meshfill.fill_holes);
+    the vertices stay, the caps follow the faces.  ``return_fill_stats`` (with ``fill_holes``): the call returns (vertices, faces, counts), counts
+    being fill_holes' dict (loops_filled, caps, loops_too_long, ...)."""
     from . import meshproc as mp
     from .mcubes import udf_mc_lewiner
     if simplify_cells is not None:
@@ -406,6 +411,16 @@ def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[
             raise ValueError(f"remesh_edge must be positive and finite, got {remesh_edge}")
         if int(remesh_iterations) != remesh_iterations or remesh_iterations < 0:
             raise ValueError(f"remesh_iterations must be an integer that is not negative, got {remesh_iterations}")
+    if fill_holes is not None:
+        if not device_clean:
+            raise ValueError("fill_holes runs on the device mesh: pass device_clean=True")
+        if differentiable:
+            raise ValueError("fill_holes adds faces off the udf samples: pass differentiable=False")
+    if return_fill_stats and fill_holes is None:
+        raise ValueError("return_fill_stats goes with fill_holes")
+    if fill_holes is not None:
+        if isinstance(fill_holes, bool) or int(fill_holes) != fill_holes or not 3 <= fill_holes <= 1024:
+            raise ValueError(f"fill_holes must be an integer in [3, 1024], got {fill_holes}")
     if not use_fast_grid_filler:
         udf, gradients = get_udf_and_grads(udf_func, coords_range, max_dist, N, max_batch)
     else:
@@ -421,6 +436,12 @@ def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[
 
     if device_clean:
         v64, f64 = _clean_on_device(udf_func, vertices, faces, dev, N, max_batch)
+        fill_counts = None
+        if fill_holes is not None:
+            from . import meshfill
+            fill_counts = dict.fromkeys(meshfill.COUNT_KEYS, 0)      # of an empty mesh
+        if fill_holes is not None and len(f64):
+            f64, fill_counts = meshfill.fill_holes(v64, f64, max_edges=int(fill_holes), return_stats=True)
         if simplify_cells is not None and len(f64):
             from .meshsimplify import simplify_vertex_clustering
             v64, f64 = simplify_vertex_clustering(v64, f64, cells=int(simplify_cells))
@@ -430,7 +451,8 @@ def get_mesh_from_udf(udf_func: Callable[[Tensor], Tensor], coords_range: Tuple[
         if remesh_edge is not None and len(f64):
             from .meshremesh import remesh_isotropic
             v64, f64 = remesh_isotropic(v64, f64, float(remesh_edge), iterations=int(remesh_iterations))
-        return _finish_mesh(udf_func, v64, f64, dev, N, smooth_borders, differentiable, max_batch, True)
+        mesh = _finish_mesh(udf_func, v64, f64, dev, N, smooth_borders, differentiable, max_batch, True)
+        return mesh + (fill_counts,) if return_fill_stats else mesh
     # faces whose corners or edge midpoints sit at large udf values are artefacts: drop them (meshudf.py:354-378)
     edges, edge_face = mp.edges_of_faces(faces)
     pa, pb = vertices[edges[:, 0]], vertices[edges[:, 1]]
